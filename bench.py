@@ -91,7 +91,14 @@ def parse():
     ap.add_argument("--eager", action="store_true",
                     help="loop / detector workloads: launch every kernel eagerly (default: SLIM inference and the detector's "
                          "backbone + head + loss fwd/bwd replay from hipGraphs; bit-identical results)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, float64 where the step's values are float64 "
+                         "or int64), at most 64 MiB: the loss, the trained network's state after the step and, in the loop, the boxes "
+                         "mined from each sweep pair; --workload iou3d: the IoU matrix and NMS keep list of the 1000-box size")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -274,12 +281,13 @@ def cpu_baseline_loop(cfg, trainer, s0, s1, torch):
             "stage_seconds": {k: round(v, 4) for k, v in stages.items()}}
 
 
-def bench_iou3d(dev, torch, with_cpu=True):
+def bench_iou3d(dev, torch, with_cpu=True, reps=None, warmup=3, outputs=None):
     """BASELINE.json metric, second half (SURVEY.md 8d ii): boxes/s of one nms_gpu-equivalent call INCLUDING the device
     greedy sweep, pairs/s of the rotated IoU matrix, at N in {256, 1000, 4096}; random car-like boxes (the oracle's
     generator, xy in +-50 m), sorted by score; HIP events on the launch stream, inputs resident in HBM.  VALU fraction at
     SURVEY's fixed 600 flop per pair vs the 157.3 TFLOP/s fp32 vector peak; the C oracle (single thread, like the
-    reference's serial boxes_iou_bev_cpu + greedy loop) timed beside it."""
+    reference's serial boxes_iou_bev_cpu + greedy loop) timed beside it.  `reps` timed calls per size (default 50, 20 at
+    N = 4096) behind `warmup` untimed ones; `outputs` (a dict) receives the IoU matrix and keep list of N = 1000."""
     import numpy as np
 
     from liso_amd import iou3d_nms_cuda as M
@@ -291,13 +299,13 @@ def bench_iou3d(dev, torch, with_cpu=True):
         b = b[np.argsort(-s, kind="stable")]
         tb = torch.from_numpy(b).to(dev)
         iou = torch.zeros(n, n, device=dev)
-        reps = 50 if n <= 1000 else 20
+        n_reps = reps or (50 if n <= 1000 else 20)
 
         def timed(fn):
-            for _ in range(3):
+            for _ in range(warmup):
                 fn()
             torch.cuda.synchronize()
-            e = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+            e = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_reps)]
             for a, z in e:
                 a.record()
                 fn()
@@ -308,6 +316,9 @@ def bench_iou3d(dev, torch, with_cpu=True):
 
         t_nms = timed(lambda: M.nms_gpu_device(tb, 0.1))
         t_iou = timed(lambda: M.boxes_iou_bev_gpu(tb, tb, iou))
+        if outputs is not None and n == 1000:
+            keep_dev, num_dev = M.nms_gpu_device(tb, 0.1)
+            outputs.update({"nms_keep": keep_dev[:int(num_dev.item())], "iou_bev": iou})
         keep = torch.zeros(n, dtype=torch.int64)
         t0 = time.perf_counter()
         for _ in range(5):
@@ -344,6 +355,35 @@ def _sparse_overflow(dev):
     from liso_amd.utils import mfma_conv as MC
 
     return bool(MC.sparse_stem_overflowed(dev))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(workload, trainer, loss, torch):
+    """`--dump-outputs`: what the last timed step handed its caller -- the loss, the trained network's state after the step's optimizer
+    update and, in the loop, the boxes mined from each sweep pair of the batch -- copied to the host right behind the timed region
+    (later untimed passes update BatchNorm statistics)"""
+    out = {"loss": loss}
+    net = trainer.detector.net if workload == "loop" else trainer.net
+    out.update({f"state.{k}": v for k, v in net.state_dict().items()})
+    if workload == "loop":
+        for i, boxes in enumerate(trainer.last_boxes_batch):
+            out.update({f"mined_boxes{i}.{k}": v for k, v in vars(boxes).items() if torch.is_tensor(v)})
+    return {k: v.detach().to("cpu", copy=True) for k, v in out.items() if torch.is_tensor(v)}
+
+
+def dump_outputs(out_dir, arrays, torch):
+    """every tensor of `arrays` as <out_dir>/<name>.npy: float64 where the values are float64 or int64, float32 otherwise"""
+    import numpy as np
+
+    host = {k: (v.double() if v.dtype in (torch.float64, torch.int64) else v.float()).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        sys.exit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def child_leg(extra, steps=10, warmup=3, timeout_s=420):
@@ -525,10 +565,13 @@ def main():
 
     if args.workload == "iou3d":
         if rank == 0:
-            r = bench_iou3d(dev, torch, with_cpu=not args.no_cpu_baseline)
+            outputs = {} if args.dump_outputs else None
+            r = bench_iou3d(dev, torch, with_cpu=not args.no_cpu_baseline, reps=args.steps, warmup=args.warmup, outputs=outputs)
+            if outputs is not None:
+                dump_outputs(args.dump_outputs, outputs, torch)
             n = "1000"
             print(json.dumps({"metric": "iou3d_nms boxes/s", "value": r["sizes"][n]["nms_boxes_per_s"], "unit": "boxes/s",
-                              "n_gpus": 1, "steps": 50, "warmup": 3, "ms_per_step": r["sizes"][n]["nms_ms"],
+                              "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["sizes"][n]["nms_ms"],
                               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                               "config": {"workload": "iou3d_nms: rotated NMS incl. device greedy sweep, 1000 random boxes, IoU 0.1"},
                               "iou3d_nms": r}), flush=True)
@@ -673,6 +716,8 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(args.workload, trainer, loss, torch), torch)
     step_ms = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
     step_times = {"median_ms": step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2]),
                   "p90_ms": step_ms[min(len(step_ms) - 1, int(0.9 * len(step_ms)))], "min_ms": step_ms[0], "max_ms": step_ms[-1],

@@ -1,6 +1,6 @@
 #!/bin/bash
 # bash scripts/pmc_one.sh <tag> <kernel-regex> -- python3 script args... : two SQ counter passes of one command, kernel-filtered means
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; KRE=$2; shift; shift; shift
 OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 export PYTHONPATH=$R

@@ -3,7 +3,7 @@
 #   bash scripts/profile_round.sh <tag> <kernel regex for the PMC passes> [bench args...]   -> gpurun_out/<tag>/
 # plain bench line | rocprofv3 --kernel-trace --stats | separate PMC passes: FETCH_SIZE, WRITE_SIZE, MFMA counters, LDS.
 set -u
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-prof}
 KRE=${2:-conv_igemm_kernel}
 shift; shift

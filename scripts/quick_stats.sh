@@ -1,6 +1,6 @@
 #!/bin/bash
 # bash scripts/quick_stats.sh <tag> [bench args...] -> gpurun_out/<tag>_kernel_stats.csv: rocprofv3 --kernel-trace --stats of one bench command
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; shift
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT

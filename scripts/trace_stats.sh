@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs on the GPU box: rocprofv3 kernel statistics of one bench command, the rows matching a regex printed.
 #   bash scripts/trace_stats.sh <tag> <regex> [bench args...]    -> gpurun_out/<tag>_stats.csv
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; RE=$2; shift; shift
 OUT=$R/gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp

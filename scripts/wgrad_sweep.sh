@@ -1,6 +1,6 @@
 #!/bin/bash
 # bash scripts/wgrad_sweep.sh -> per-kernel times (rocprofv3 kernel trace) of the weight gradient of one layer under plan knobs
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 export PYTHONPATH=$R
 OUT=$R/gpurun_out/wgrad_sweep; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

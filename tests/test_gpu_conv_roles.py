@@ -116,7 +116,7 @@ def test_data_gradient(shape, dtype):
     assert _rel(gx.float(), ref) <= (2e-2 if dtype == torch.bfloat16 else 2e-5)
 
 
-def test_forced_tile_shapes_agree_bitwise_on_statistics_and_closely_on_values():
+def test_forced_tile_shapes_agree_bitwise_on_statistics_and_closely_on_values(tmp_path):
     """LISO_ROLES_MI / LISO_ROLES_NJ force the tile shape (a plan-time switch: one child process per shape).  Values must agree to
     fp32 rounding of the summation order (identical here: the order over (slab, tap) does not depend on the tile), and the statistics
     rows -- fixed 4 x 32-pixel sets, fixed tree -- bit for bit."""
@@ -133,7 +133,7 @@ torch.save({"y": y.cpu(), "s": part[:, :, :64].cpu(), "rows": part.shape[0]}, sy
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     for mi, nj in ((1, 1), (1, 2), (2, 1), (2, 2), (1, 3)):
-        path = f"/tmp/liso_roles_forced_{mi}{nj}.pt"
+        path = str(tmp_path / f"roles_forced_{mi}{nj}.pt")
         env = dict(os.environ, LISO_ROLES_MI=str(mi), LISO_ROLES_NJ=str(nj))
         r = subprocess.run([sys.executable, "-c", code % root, path], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
