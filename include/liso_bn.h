@@ -10,8 +10,9 @@
  * Batch statistics use block-shifted sums merged over the block means in fp64 (fixed order):
  * no E[x^2]-E[x]^2 cancellation (MIOpen's spatial BN loses ~2e-4 relative at mean/std = 50, measured), reproducible.
  *
- * x, y, dy, dx: [M, C] row-major (M = N*H*W pixels, channels-last), dtype fp32 (is_bf16 = 0) or bf16 (is_bf16 = 1);
- * C % 8 == 0, C <= 256 (V = 4 channels per lane in fp32, 8 in bf16; 256 / (C / V) rows per block pass).  gamma/beta/running_*: fp32 [C].  stats: fp32 [4*C] = scale | shift | mean | invstd.
+ * x, y, dy, dx: [M, C] row-major (M = N*H*W pixels, channels-last), dtype by element code (include/liso_conv.h): fp32 (is_bf16 = 0),
+ * bf16 (is_bf16 = 1) or fp16 (is_bf16 = 2; the BatchNorm entry points only -- the InstanceNorm ones return LISO_EINVAL for it);
+ * C % 8 == 0, C <= 256 (V = 4 channels per lane in fp32, 8 in bf16 / fp16; 256 / (C / V) rows per block pass).  gamma/beta/running_*: fp32 [C].  stats: fp32 [4*C] = scale | shift | mean | invstd.
  * All pointers are device pointers; nothing allocates or synchronises.
  */
 #ifndef LISO_BN_H

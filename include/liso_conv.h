@@ -18,6 +18,8 @@
  *   forward of a transposed conv:         reaches it (no multiplications by inserted zeros)
  *
  * Arithmetic: `mode` LISO_CONV_BF16 -- bf16 tensors, fp32 accumulation on v_mfma_f32_32x32x16_bf16;
+ *             `mode` LISO_CONV_F16 -- fp16 tensors, fp32 accumulation on v_mfma_f32_32x32x16_f16 (same kernels, tiles and plans as
+ *             BF16; fp32 -> fp16 rounds to nearest even; 11 significand bits instead of 8, range +-65504);
  *             `mode` LISO_CONV_F32X3 -- fp32 tensors; every operand is split on the fly into bf16 hi + lo parts and each
  *             product is evaluated as hi*hi + hi*lo + lo*hi (three MFMAs, fp32 accumulation): relative error per product
  *             <= 2^-16 (fp32: 2^-24; TF32, cuDNN's default for fp32 convolutions on Ampere: 2^-11) at 3/16 of the cost
@@ -31,6 +33,7 @@
  *
  * Packed weights (liso_conv_pack_weights): [plane][tap][ci_pad / 8][co_pad][8] bf16, plane 0 = hi (or the bf16 value),
  * plane 1 = lo (F32X3 only); ci_pad = round_up(ci, 16), co_pad = round_up(co, 64); padding is zero.
+ * LISO_CONV_F16: one plane of fp16 values in the layout of the bf16 plane.
  * LISO_CONV_F32: [tap][ci_pad / 4][co_pad][4] fp32 (unrounded), the same number of bytes as the two F32X3 planes.
  *
  * All pointers are device pointers; nothing allocates or synchronises; every call enqueues on `stream` and returns
@@ -51,6 +54,14 @@ extern "C" {
 #define LISO_CONV_BF16 0
 #define LISO_CONV_F32X3 1
 #define LISO_CONV_F32 2
+#define LISO_CONV_F16 3 /* fp16 tensors, fp32 accumulation on v_mfma_f32_32x32x16_f16: the BF16 kernels and plans with fp16 elements */
+
+/* Element codes of the `is_bf16` / `out_bf16` / `grad_bf16` arguments of the detector-path entry points (liso_sparse_conv_*,
+ * include/liso_bn.h, include/liso_pillars.h): 0 = fp32, 1 = bf16 (the original boolean meaning, unchanged), 2 = fp16.  An entry point
+ * that does not support a code returns LISO_EINVAL before it launches anything. */
+#define LISO_ELEM_F32 0
+#define LISO_ELEM_BF16 1
+#define LISO_ELEM_F16 2
 
 typedef struct {
     int batch, hi, wi, ci;      /* input  [batch, hi, wi, ci] */
@@ -66,8 +77,8 @@ typedef struct {
     int tap_dy[LISO_CONV_MAX_TAPS], tap_dx[LISO_CONV_MAX_TAPS]; /* input offset of the tap */
     int tap_w[LISO_CONV_MAX_TAPS];                              /* tap index inside the packed weights */
     int w_taps;                 /* taps in the packed weights (kh * kw) */
-    int mode;                   /* LISO_CONV_BF16 | LISO_CONV_F32X3 | LISO_CONV_F32 */
-    int out_f32;                /* BF16 mode: 1 = fp32 output, 0 = bf16 output (F32X3: always fp32) */
+    int mode;                   /* LISO_CONV_BF16 | LISO_CONV_F32X3 | LISO_CONV_F32 | LISO_CONV_F16 */
+    int out_f32;                /* BF16 / F16 mode: 1 = fp32 output, 0 = bf16 / fp16 output (F32X3: always fp32) */
     int in_relu, out_relu;
     int in_affine_batch_stride; /* 0: in_scale / in_shift are [ci], shared by all samples (BatchNorm);
                                    > 0: per-sample vectors, sample b reads in_scale[b * stride + c] (InstanceNorm) */

@@ -38,6 +38,37 @@ int liso_adamw_step_f32(float* param, const float* grad, float* exp_avg, float* 
 int liso_adamw_step_scaled_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                                double beta2, double eps, double weight_decay, double grad_scale, long step, void* stream);
 
+/* ---- dynamic loss scaling (fp16 training) ---------------------------------------------------------------------------------------
+ * The state lives in device memory and never travels to the host inside a step: the backward pass is seeded with `scale` (read from
+ * device memory, so a captured hipGraph replays with the current value), then
+ *   (a) liso_grad_nonfinite_f32     one pass over the flat fp32 gradient buffer: sets found_inf = 1 if any element is inf / NaN;
+ *   (b) liso_adamw_step_amp_f32     the AdamW update above on grad * grad_scale / scale at bias-correction step `step + 1` -- or, with
+ *                                   found_inf set, nothing at all (param, exp_avg, exp_avg_sq and `step` keep their bits);
+ *   (c) liso_loss_scale_update      torch.cuda.amp.GradScaler.update() semantics: found_inf -> scale *= backoff_factor, growth_tracker
+ *                                   = 0, skipped += 1; else step += 1 and growth_tracker += 1, reaching growth_interval -> scale *=
+ *                                   growth_factor (if the product is finite), growth_tracker = 0.  Clears found_inf for the next step.
+ * `step` advances on applied updates only, as torch.optim.AdamW's under GradScaler (its optimizer.step() is not called on a skipped
+ * step).  A fixed loss scale is growth_factor = backoff_factor = 1: overflowing steps are still skipped.
+ * Several ranks need nothing extra: the flat buffer is SUM-all-reduced before (a), so an inf / NaN on any rank is one on every rank, and
+ * every rank takes the same decision on identical states.
+ * One state per optimizer; the calls of one step are enqueued on one stream in the order (a), (b), (c).  Zero-initialised state with
+ * `scale` set is a valid start.  The state is a device pointer aligned to 16 bytes, like the flat buffers (every call returns LISO_EINVAL
+ * otherwise); the gradient / parameter / moment buffers of (a) and (b) are 16-byte aligned as for liso_adamw_step_f32. */
+typedef struct {
+    float scale;        /* the current loss scale */
+    int found_inf;      /* set by (a), consumed and cleared by (c) */
+    int growth_tracker; /* consecutive applied steps since the scale last changed */
+    int step;           /* applied AdamW updates (bias-correction counter) */
+    int skipped;        /* skipped steps (diagnostics) */
+    int reserved[3];
+} liso_loss_scale_state;
+
+int liso_grad_nonfinite_f32(const float* grad, size_t n, liso_loss_scale_state* state, void* stream);
+int liso_adamw_step_amp_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                            double beta2, double eps, double weight_decay, double grad_scale, const liso_loss_scale_state* state,
+                            void* stream);
+int liso_loss_scale_update(liso_loss_scale_state* state, double growth_factor, double backoff_factor, int growth_interval, void* stream);
+
 /* RMSprop over one flat fp32 buffer (SLIM's optimizer, liso/slim/experiment.py:200-219: torch.optim.RMSprop(lr) with its defaults
  * alpha 0.99, eps 1e-8, no momentum, not centered), the element-wise operations of torch's multi-tensor implementation:
  *     square_avg = square_avg * alpha + (1 - alpha) * g * g;   param = param - lr * g / (sqrt(square_avg) + eps),   g = grad * grad_scale

@@ -80,7 +80,9 @@ int liso_pfn_bn_prepare_f32(const float* feat, const int* pt_off, const liso_pil
 
 /* Fused Linear + BN + ReLU + max + dense scatter.  Every cell of canvas and occupancy is written exactly once (zeros
  * for empty cells: pillar_scatter.py:78-82 allocates zeros), so the caller need NOT pre-fill them.
- * cell_to_voxel comes from liso_pillars_voxelize_f32.  out_bf16 != 0: canvas is bfloat16, else float32. */
+ * cell_to_voxel comes from liso_pillars_voxelize_f32.  out_bf16 = element code of the canvas (include/liso_conv.h): 0 float32,
+ * 1 bfloat16, 2 float16 (rounded to nearest even); any other value: LISO_EINVAL, nothing launched.  grad_bf16 of the backward: the same
+ * codes for grad_canvas. */
 int liso_pfn_forward_scatter(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
                              const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas, int out_bf16,
                              float* occupancy, void* stream);

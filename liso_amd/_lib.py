@@ -235,6 +235,9 @@ SIGNATURES = {
     # include/liso_optim.h
     "liso_adamw_step_f32": (_i, [_vp, _vp, _vp, _vp, _sz] + [ctypes.c_double] * 5 + [ctypes.c_long, _vp]),
     "liso_adamw_step_scaled_f32": (_i, [_vp, _vp, _vp, _vp, _sz] + [ctypes.c_double] * 6 + [ctypes.c_long, _vp]),
+    "liso_grad_nonfinite_f32": (_i, [_vp, _sz, _vp, _vp]),
+    "liso_adamw_step_amp_f32": (_i, [_vp, _vp, _vp, _vp, _sz] + [ctypes.c_double] * 6 + [_vp, _vp]),
+    "liso_loss_scale_update": (_i, [_vp, ctypes.c_double, ctypes.c_double, _i, _vp]),
     "liso_rmsprop_step_f32": (_i, [_vp, _vp, _vp, _sz] + [ctypes.c_double] * 4 + [_vp]),
     "liso_multi_copy_rows": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liso_gather_f32": (_i, [_i, _vp, _vp, _vp, _vp]),
@@ -291,7 +294,24 @@ SIGNATURES = {
 }
 
 
-CONV_MAX_TAPS, CONV_MAX_CLASSES, CONV_BF16, CONV_F32X3, CONV_F32 = 49, 4, 0, 1, 2
+CONV_MAX_TAPS, CONV_MAX_CLASSES, CONV_BF16, CONV_F32X3, CONV_F32, CONV_F16 = 49, 4, 0, 1, 2, 3
+# element codes of the `is_bf16` / `out_bf16` / `grad_bf16` arguments (include/liso_conv.h: LISO_ELEM_*)
+ELEM_F32, ELEM_BF16, ELEM_F16 = 0, 1, 2
+_ELEM_CODES = {torch.float32: ELEM_F32, torch.bfloat16: ELEM_BF16, torch.float16: ELEM_F16}
+LOSS_SCALE_STATE_BYTES = 32  # sizeof(liso_loss_scale_state), include/liso_optim.h
+
+
+def elem_code(dtype):
+    """the element code of a detector-path tensor dtype: fp32 -> 0, bf16 -> 1, fp16 -> 2; anything else raises TypeError"""
+    code = _ELEM_CODES.get(dtype)
+    if code is None:
+        raise TypeError(f"no device kernel takes {dtype} tensors (float32, bfloat16 or float16)")
+    return code
+
+
+def is_half(dtype):
+    """a 16-bit storage type of the detector path (bf16 or fp16): 8 channels per lane, one MFMA per product"""
+    return elem_code(dtype) != ELEM_F32
 CONV_OPT_SHARED_GPU = 1
 CONV_OPT_ROLES_CUS = 2
 

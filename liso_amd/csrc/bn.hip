@@ -13,6 +13,7 @@
 
 #include "../../include/liso_bn.h"
 #include "../../include/liso_iou3d.h"
+#include "elem16.h"
 
 namespace {
 
@@ -53,6 +54,28 @@ template <> struct Vec<__hip_bfloat16> {
         *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
     }
 };
+
+template <> struct Vec<_Float16> {  // fp16: the bf16 layout, 8 channels per lane; stores round to nearest even
+    static constexpr int V = 8;
+    static __device__ __forceinline__ void load(const _Float16* p, float (&v)[8]) {
+        const uint4 t = *reinterpret_cast<const uint4*>(p);
+        const unsigned w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            v[2 * i] = liso_e16::F16::lo(w[i]);
+            v[2 * i + 1] = liso_e16::F16::hi(w[i]);
+        }
+    }
+    static __device__ __forceinline__ void store(_Float16* p, const float (&v)[8]) {
+        unsigned w[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) w[i] = liso_e16::F16::pack(v[2 * i], v[2 * i + 1]);
+        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+};
+
+// element code of the entry points (include/liso_conv.h: LISO_ELEM_F32 / BF16 / F16)
+static inline bool elem_ok(int e) { return e == LISO_ELEM_F32 || e == LISO_ELEM_BF16 || e == LISO_ELEM_F16; }
 
 struct Geom {
     int cg;        // column groups = C / V
@@ -522,14 +545,16 @@ int liso_bn_relu_fwd(const void* x, int is_bf16, long m, int c, const float* gam
                      void* y, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
     Geom g;
     int nblk;
-    if (m < 0 || !geom(c, is_bf16 ? 8 : 4, m, &g, &nblk)) return LISO_EINVAL;
+    if (!elem_ok(is_bf16) || m < 0 || !geom(c, is_bf16 ? 8 : 4, m, &g, &nblk)) return LISO_EINVAL;
     if (!gamma || !beta || !running_mean || !running_var || !stats || !workspace || (m > 0 && (!x || !y))) return LISO_EINVAL;
     if (workspace_bytes < liso_bn_workspace_bytes(c)) return LISO_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)workspace;
     if (training) {
         if (m == 0) return LISO_EINVAL;
-        if (is_bf16)
+        if (is_bf16 == LISO_ELEM_F16)
+            bn_stats_kernel<_Float16><<<nblk, kThreads, 0, st>>>((const _Float16*)x, m, c, g, partial);
+        else if (is_bf16)
             bn_stats_kernel<__hip_bfloat16><<<nblk, kThreads, 0, st>>>((const __hip_bfloat16*)x, m, c, g, partial);
         else
             bn_stats_kernel<float><<<nblk, kThreads, 0, st>>>((const float*)x, m, c, g, partial);
@@ -541,7 +566,8 @@ int liso_bn_relu_fwd(const void* x, int is_bf16, long m, int c, const float* gam
     if (m > 0) {
         const int grid = stream_grid(m, g);
 #define LISO_APPLY(T, R) bn_apply_kernel<T, R><<<grid, kThreads, 0, st>>>((const T*)x, m, c, g, stats, (T*)y)
-        if (is_bf16) { if (relu) LISO_APPLY(__hip_bfloat16, true); else LISO_APPLY(__hip_bfloat16, false); }
+        if (is_bf16 == LISO_ELEM_F16) { if (relu) LISO_APPLY(_Float16, true); else LISO_APPLY(_Float16, false); }
+        else if (is_bf16) { if (relu) LISO_APPLY(__hip_bfloat16, true); else LISO_APPLY(__hip_bfloat16, false); }
         else { if (relu) LISO_APPLY(float, true); else LISO_APPLY(float, false); }
 #undef LISO_APPLY
     }
@@ -553,7 +579,7 @@ static int bn_relu_bwd(const void* dy, const void* x, int is_bf16, long m, int c
                        size_t workspace_bytes, unsigned* ticket, void* stream, long dy_stride = 0, long x_stride = 0, long dx_stride = 0) {
     Geom g;
     int nblk;
-    if (m <= 0 || !geom(c, is_bf16 ? 8 : 4, m, &g, &nblk)) return LISO_EINVAL;
+    if (!elem_ok(is_bf16) || m <= 0 || !geom(c, is_bf16 ? 8 : 4, m, &g, &nblk)) return LISO_EINVAL;
     if (dy_stride || x_stride || dx_stride) {  // rows that are channel slices of wider channels-last tensors
         const int v = is_bf16 ? 8 : 4;
         if (dy_stride < c || x_stride < c || dx_stride < c || dy_stride % v || x_stride % v || dx_stride % v) return LISO_EINVAL;
@@ -576,7 +602,8 @@ static int bn_relu_bwd(const void* dy, const void* x, int is_bf16, long m, int c
                                                                      grad_beta, coef);                                    \
         bn_bwd_dx_kernel<T, R><<<grid, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, coef, (T*)dx);          \
     } while (0)
-    if (is_bf16) { if (relu) LISO_BWD(__hip_bfloat16, true); else LISO_BWD(__hip_bfloat16, false); }
+    if (is_bf16 == LISO_ELEM_F16) { if (relu) LISO_BWD(_Float16, true); else LISO_BWD(_Float16, false); }
+    else if (is_bf16) { if (relu) LISO_BWD(__hip_bfloat16, true); else LISO_BWD(__hip_bfloat16, false); }
     else { if (relu) LISO_BWD(float, true); else LISO_BWD(float, false); }
 #undef LISO_BWD
     return check_launch();
@@ -614,7 +641,8 @@ int liso_in_relu_fwd(const void* x, int is_bf16, int groups, long m, int c, cons
                      void* y, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
     Geom g;
     int nblk;
-    if (groups < 1 || m <= 0 || !geom(c, is_bf16 ? 8 : 4, m, &g, &nblk)) return LISO_EINVAL;
+    if ((is_bf16 != LISO_ELEM_F32 && is_bf16 != LISO_ELEM_BF16) || groups < 1 || m <= 0 || !geom(c, is_bf16 ? 8 : 4, m, &g, &nblk))
+        return LISO_EINVAL;  // (InstanceNorm: SLIM's encoders, fp32 / bf16 only)
     if (!gamma || !beta || !stats || !workspace || !x || !y) return LISO_EINVAL;
     if (workspace_bytes < liso_in_workspace_bytes(groups, c)) return LISO_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -636,7 +664,8 @@ static int in_relu_bwd(const void* dy, const void* x, int is_bf16, int groups, l
                      int relu, void* dx, float* grad_gamma, float* grad_beta, void* workspace, size_t workspace_bytes, int summed, void* stream) {
     Geom g;
     int nblk;
-    if (groups < 1 || m <= 0 || !geom(c, is_bf16 ? 8 : 4, m, &g, &nblk)) return LISO_EINVAL;
+    if ((is_bf16 != LISO_ELEM_F32 && is_bf16 != LISO_ELEM_BF16) || groups < 1 || m <= 0 || !geom(c, is_bf16 ? 8 : 4, m, &g, &nblk))
+        return LISO_EINVAL;  // (InstanceNorm: SLIM's encoders, fp32 / bf16 only)
     if (!dy || !x || !gamma || !stats || !dx || !grad_gamma || !grad_beta || !workspace) return LISO_EINVAL;
     if (workspace_bytes < liso_in_workspace_bytes(groups, c)) return LISO_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;

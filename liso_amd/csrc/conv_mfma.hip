@@ -29,6 +29,7 @@
 #include "../../include/liso_conv.h"
 #include "../../include/liso_iou3d.h"
 #include "conv_plan.h"
+#include "elem16.h"
 #include "per_device.h"
 
 namespace {
@@ -56,7 +57,7 @@ __device__ __forceinline__ bf8 as_bf8(const uint4& v) { return __builtin_bit_cas
 // ---- epilogue shared by the forward kernels ---------------------------------------------------------------------------------------
 // acc[i][j]: the 32 x 32 MFMA tiles of wave `wave` (tile row wave * MI + i of the block's TH = 4 MI rows, output channels n0 + 32 j ...).
 // `active` = this thread holds accumulators (waves 0-3 of the block, split-K group 0); every thread of the block must call (barriers).
-template <int MI, int NJ, bool OUT_F32, bool WAVE_STATS = false>
+template <typename E, int MI, int NJ, bool OUT_F32, bool WAVE_STATS = false>
 __device__ __forceinline__ void conv_epilogue(const liso_conv_desc& d, const FwdArgs& a, f16v (&acc)[MI][NJ], int cls, int b, int tx, int ty,
                                               int wave, int r, int h, bool active, int n0, int stats_row, int tid_all,
                                               unsigned char* smem) {
@@ -107,7 +108,7 @@ __device__ __forceinline__ void conv_epilogue(const liso_conv_desc& d, const Fwd
             for (int e = 0; e < 16; e++) {
                 float val = acc[i][j][e] + bias_v;
                 if (d.out_relu) val = fmaxf(val, 0.0f);
-                if constexpr (!OUT_F32) val = round_bf16(val);
+                if constexpr (!OUT_F32) val = E::round(val);
                 v[e] = val;
                 if constexpr (!WAVE_STATS) {
                     if (want_stats && ((rowmask >> e) & 1u)) {
@@ -150,7 +151,7 @@ __device__ __forceinline__ void conv_epilogue(const liso_conv_desc& d, const Fwd
 #pragma unroll
                     for (int e = 0; e < 16; e++)
                         if (((rowmask >> e) & 1u) && n_ok)
-                            yg[((e & 3) + 8 * (e >> 2)) * col_stride + n] = (unsigned short)(pack_bf16(v[e], 0.0f) & 0xffffu);
+                            yg[((e & 3) + 8 * (e >> 2)) * col_stride + n] = (unsigned short)(E::pack(v[e], 0.0f) & 0xffffu);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 16; e += 2) {
@@ -163,9 +164,9 @@ __device__ __forceinline__ void conv_epilogue(const liso_conv_desc& d, const Fwd
                         if ((rowmask >> ee) & 1u) {
                             unsigned short* dst = yg + koff * col_stride + n_even;
                             if (n_even + 1 < d.co)
-                                *reinterpret_cast<unsigned*>(dst) = pack_bf16(c_lo, c_hi);
+                                *reinterpret_cast<unsigned*>(dst) = E::pack(c_lo, c_hi);
                             else if (n_even < d.co)
-                                *dst = (unsigned short)(pack_bf16(c_lo, 0.0f) & 0xffffu);
+                                *dst = (unsigned short)(E::pack(c_lo, 0.0f) & 0xffffu);
                         }
                     }
                 }
@@ -219,6 +220,7 @@ __device__ __forceinline__ void conv_epilogue(const liso_conv_desc& d, const Fwd
 // the loads in flight per CU, half the slab iterations); group 1 hands its accumulators over through LDS before the epilogue.
 template <int MODE, int MI, int NJ, bool OUT_F32, int CS, int SK = 1>
 __global__ __launch_bounds__(kThreads * SK, SK == 1 ? 2 : 1) void conv_igemm_kernel(const liso_conv_desc d, const FwdArgs a) {
+    using E = typename liso_e16::Elem<MODE>::T;  // the 16-bit element (bf16 | fp16; F32X3: the bf16 of its hi / lo planes)
     constexpr int BNT = 32 * NJ;
     constexpr int TH = 4 * MI;
     constexpr bool X3 = MODE == LISO_CONV_F32X3;
@@ -371,13 +373,13 @@ __global__ __launch_bounds__(kThreads * SK, SK == 1 ? 2 : 1) void conv_igemm_ker
                     unsigned w[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
-                        float f0 = fmaf(bf16_lo(w[e]), sc[2 * e], sh[2 * e]);
-                        float f1 = fmaf(bf16_hi(w[e]), sc[2 * e + 1], sh[2 * e + 1]);
+                        float f0 = fmaf(E::lo(w[e]), sc[2 * e], sh[2 * e]);
+                        float f1 = fmaf(E::hi(w[e]), sc[2 * e + 1], sh[2 * e + 1]);
                         if (d.in_relu) {
                             f0 = fmaxf(f0, 0.0f);
                             f1 = fmaxf(f1, 0.0f);
                         }
-                        w[e] = pack_bf16(f0, f1);
+                        w[e] = E::pack(f0, f1);
                     }
                     o = make_uint4(w[0], w[1], w[2], w[3]);
                 }
@@ -484,8 +486,7 @@ __global__ __launch_bounds__(kThreads * SK, SK == 1 ? 2 : 1) void conv_igemm_ker
 #pragma unroll
                     for (int i = 0; i < MI; i++)
 #pragma unroll
-                        for (int j = 0; j < NJ; j++)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(af[kk][i]), as_bf8(bfr[kk][j]), acc[i][j], 0, 0, 0);
+                        for (int j = 0; j < NJ; j++) acc[i][j] = E::mfma(af[kk][i], bfr[kk][j], acc[i][j]);
             }
         }
     };
@@ -599,7 +600,7 @@ __global__ __launch_bounds__(kThreads * SK, SK == 1 ? 2 : 1) void conv_igemm_ker
     }
     __syncthreads();
 
-    conv_epilogue<MI, NJ, OUT_F32>(d, a, acc, cls, b, tx, ty, wave, r, h, grp == 0, n0, stats_row, tid_all, smem);
+    conv_epilogue<E, MI, NJ, OUT_F32>(d, a, acc, cls, b, tx, ty, wave, r, h, grp == 0, n0, stats_row, tid_all, smem);
 }
 
 // BatchNorm / InstanceNorm partial sums of conv_roles_kernel: one statistics row per 4 tile rows x 32 pixels = sum of the four 32-pixel row
@@ -631,7 +632,7 @@ __device__ __forceinline__ void roles_flush_stats(const FwdArgs& a, int b, int t
 // as 16 bytes per lane): 4 (fp32) or 2 (bf16) 16-byte store instructions per tile, whole 128-B / 64-B runs per pixel.  No barrier: a wave
 // only reads what it wrote.  Bias, ReLU, rounding and the statistics sums (pairwise per lane, one LDS row per 32-pixel tile row: see
 // roles_flush_stats) as in conv_epilogue.  `wide` false (channel counts / strides that do not allow 16-byte stores): conv_epilogue.
-template <int MI, int NJ, bool OUT_F32>
+template <typename E, int MI, int NJ, bool OUT_F32>
 __device__ __forceinline__ void roles_epilogue(const liso_conv_desc& d, const FwdArgs& a, f16v (&acc)[MI][NJ], int b, int tx, int ty, int wave,
                                                int lane, int n0, unsigned char* smem, unsigned char* patch) {
     constexpr int BNT = 32 * NJ;
@@ -660,7 +661,7 @@ __device__ __forceinline__ void roles_epilogue(const liso_conv_desc& d, const Fw
             for (int e = 0; e < 16; e++) {
                 float val = acc[i][j][e] + bias_v;
                 if (d.out_relu) val = fmaxf(val, 0.0f);
-                if constexpr (!OUT_F32) val = round_bf16(val);
+                if constexpr (!OUT_F32) val = E::round(val);
                 v[e] = val;
                 const int vx = tx * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
                 const float dd = (row_ok && vx < d.wv && vx + oox < d.wo) ? val - shift_v : 0.0f;
@@ -702,7 +703,7 @@ __device__ __forceinline__ void roles_epilogue(const liso_conv_desc& d, const Fw
                         const float c_lo = odd ? recv : v[e], c_hi = odd ? v[e + 1] : recv;
                         const int ee = odd ? e8 + 1 : e8;
                         const int px = (ee & 3) + 8 * (ee >> 2) + 4 * h;
-                        *reinterpret_cast<unsigned*>(patch + px * ROWB + (r >> 1) * 4) = pack_bf16(c_lo, c_hi);
+                        *reinterpret_cast<unsigned*>(patch + px * ROWB + (r >> 1) * 4) = E::pack(c_lo, c_hi);
                     }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -745,6 +746,7 @@ __device__ __forceinline__ void roles_epilogue(const liso_conv_desc& d, const Fw
 // MFMA), 8-row tiles with 64-channel panels are balanced.
 template <int MODE, int MI, int NJ, bool OUT_F32, int NTAPS, bool PRO>
 __global__ __launch_bounds__(512, 1) void conv_roles_kernel(const liso_conv_desc d, const FwdArgs a) {
+    using E = typename liso_e16::Elem<MODE>::T;
     constexpr bool X3 = MODE == LISO_CONV_F32X3;
     constexpr int PLANES = X3 ? 2 : 1;
     constexpr int CS = X3 ? 16 : 32;
@@ -919,13 +921,13 @@ __global__ __launch_bounds__(512, 1) void conv_roles_kernel(const liso_conv_desc
                     unsigned w[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
-                        float f0 = fmaf(bf16_lo(w[e]), R.sc[2 * e], R.sh[2 * e]);
-                        float f1 = fmaf(bf16_hi(w[e]), R.sc[2 * e + 1], R.sh[2 * e + 1]);
+                        float f0 = fmaf(E::lo(w[e]), R.sc[2 * e], R.sh[2 * e]);
+                        float f1 = fmaf(E::hi(w[e]), R.sc[2 * e + 1], R.sh[2 * e + 1]);
                         if (d.in_relu) {
                             f0 = fmaxf(f0, 0.0f);
                             f1 = fmaxf(f1, 0.0f);
                         }
-                        w[e] = pack_bf16(f0, f1);
+                        w[e] = E::pack(f0, f1);
                     }
                     o = make_uint4(w[0], w[1], w[2], w[3]);
                 }
@@ -1063,7 +1065,7 @@ __global__ __launch_bounds__(512, 1) void conv_roles_kernel(const liso_conv_desc
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(F.al[kk][i]), as_bf8(F.bh[kk][j]), acc[i][j], 0, 0, 0);
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(F.ah[kk][i]), as_bf8(F.bl[kk][j]), acc[i][j], 0, 0, 0);
                         }
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(F.ah[kk][i]), as_bf8(F.bh[kk][j]), acc[i][j], 0, 0, 0);
+                        acc[i][j] = E::mfma(F.ah[kk][i], F.bh[kk][j], acc[i][j]);
                     }
         };
 #ifdef LISO_ROLES_STAMPS
@@ -1118,13 +1120,13 @@ __global__ __launch_bounds__(512, 1) void conv_roles_kernel(const liso_conv_desc
 #ifdef LISO_ROLES_STAMPS
             FwdArgs a2 = a;
             a2.stats = nullptr;
-            conv_epilogue<MI, NJ, OUT_F32, true>(d, a2, acc, 0, T.b, T.tx, T.ty, wave, r, h, true, T.n0, T.row, tid_all, smem);
+            conv_epilogue<E, MI, NJ, OUT_F32, true>(d, a2, acc, 0, T.b, T.tx, T.ty, wave, r, h, true, T.n0, T.row, tid_all, smem);
             STAMP_END(st_epi)
 #else
             if (a.wide_out)
-                roles_epilogue<MI, NJ, OUT_F32>(d, a, acc, T.b, T.tx, T.ty, wave, lane, T.n0, smem, base + 2 * BUF + wave * 2048);
+                roles_epilogue<E, MI, NJ, OUT_F32>(d, a, acc, T.b, T.tx, T.ty, wave, lane, T.n0, smem, base + 2 * BUF + wave * 2048);
             else
-                conv_epilogue<MI, NJ, OUT_F32, true>(d, a, acc, 0, T.b, T.tx, T.ty, wave, r, h, true, T.n0, T.row, tid_all, smem);
+                conv_epilogue<E, MI, NJ, OUT_F32, true>(d, a, acc, 0, T.b, T.tx, T.ty, wave, r, h, true, T.n0, T.row, tid_all, smem);
 #endif
         }
 #ifndef LISO_ROLES_STAMPS
@@ -1158,6 +1160,7 @@ __global__ __launch_bounds__(512, 1) void conv_roles_kernel(const liso_conv_desc
 // MODE: F32X3 (fp32 tensors, bf16 hi / lo split in registers) or BF16 (bf16 tensors: the lane's 8 channels are one 16-byte load).
 template <int MODE, int MI, int NJ, bool OUT_F32, bool PRO>
 __global__ __launch_bounds__(kThreads, 2) void conv_1x1_kernel(const liso_conv_desc d, const FwdArgs a) {
+    using E = typename liso_e16::Elem<MODE>::T;
     constexpr bool X3 = MODE == LISO_CONV_F32X3;
     constexpr int BNT = 32 * NJ;
     constexpr int TH = 4 * MI;
@@ -1277,8 +1280,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_1x1_kernel(const liso_conv_d
                 const unsigned w[4] = {q0.x, q0.y, q0.z, q0.w};
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    f[2 * e] = bf16_lo(w[e]);
-                    f[2 * e + 1] = bf16_hi(w[e]);
+                    f[2 * e] = E::lo(w[e]);
+                    f[2 * e + 1] = E::hi(w[e]);
                 }
             }
             if constexpr (PRO) {
@@ -1295,7 +1298,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_1x1_kernel(const liso_conv_d
                 if (!(in && (e < 4 ? v0 : v1))) f[e] = 0.0f;
             unsigned hi[4];
 #pragma unroll
-            for (int e = 0; e < 4; e++) hi[e] = pack_bf16(f[2 * e], f[2 * e + 1]);
+            for (int e = 0; e < 4; e++) hi[e] = E::pack(f[2 * e], f[2 * e + 1]);
             ah[i] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
             if constexpr (X3) {
                 unsigned lo[4];
@@ -1315,7 +1318,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_1x1_kernel(const liso_conv_d
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(al[i]), as_bf8(bh), acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(ah[i]), as_bf8(bl), acc[i][j], 0, 0, 0);
                 }
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(ah[i]), as_bf8(bh), acc[i][j], 0, 0, 0);
+                acc[i][j] = E::mfma(ah[i], bh, acc[i][j]);
             }
         }
     };
@@ -1333,7 +1336,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_1x1_kernel(const liso_conv_d
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    conv_epilogue<MI, NJ, OUT_F32>(d, a, acc, cls, b, tx, ty, wave, r, h, true, n0, stats_row, tid_all, smem);
+    conv_epilogue<E, MI, NJ, OUT_F32>(d, a, acc, cls, b, tx, ty, wave, r, h, true, n0, stats_row, tid_all, smem);
 }
 
 // ---- windows on 2-8 input channels, F32X3: two taps per MFMA step, fragments straight from global memory ---------------------------
@@ -1466,24 +1469,28 @@ __global__ __launch_bounds__(kThreads, 2) void conv_taps_kernel(const liso_conv_
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    conv_epilogue<1, NJ, true>(d, a, acc, 0, b, tx, ty, wave, r, h, true, n0, stats_row, tid_all, smem);
+    conv_epilogue<liso_e16::Bf16, 1, NJ, true>(d, a, acc, 0, b, tx, ty, wave, r, h, true, n0, stats_row, tid_all, smem);
 }
 
 // ---- weight packing ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void pack_chunk(const float* __restrict__ src, int d1, int taps, int swap_ab, int K, int N, int Kp, int Np,
-                                           int f32, unsigned short* __restrict__ dst, long q);
+                                           int fmt, unsigned short* __restrict__ dst, long q);
 
-// 16-B chunks of the packed weights: bf16 planes x taps x Kp/8 x Np; exact fp32 (one plane of 4-float groups): taps x Kp/4 x Np
-__host__ __device__ inline long pack_chunks(int planes, int taps, int Kp, int Np, int f32) {
-    return f32 ? (long)taps * (Kp / 4) * Np : (long)planes * taps * (Kp / 8) * Np;
+// panel formats: 16-bit planes of bf16 (BF16, F32X3 hi / lo), exact fp32, one fp16 plane
+constexpr int kPackBf16 = 0, kPackF32 = 1, kPackF16 = 2;
+__host__ __device__ inline int pack_format(int mode) { return mode == LISO_CONV_F32 ? kPackF32 : mode == LISO_CONV_F16 ? kPackF16 : kPackBf16; }
+
+// 16-B chunks of the packed weights: 16-bit planes x taps x Kp/8 x Np; exact fp32 (one plane of 4-float groups): taps x Kp/4 x Np
+__host__ __device__ inline long pack_chunks(int planes, int taps, int Kp, int Np, int fmt) {
+    return fmt == kPackF32 ? (long)taps * (Kp / 4) * Np : (long)planes * taps * (Kp / 8) * Np;
 }
 
 __global__ void pack_weights_kernel(const float* __restrict__ src, int d0, int d1, int taps, int swap_ab, int K, int N, int Kp,
-                                    int Np, int planes, int f32, unsigned short* __restrict__ dst) {
-    const long total = pack_chunks(planes, taps, Kp, Np, f32);  // one thread per 16-B chunk
+                                    int Np, int planes, int fmt, unsigned short* __restrict__ dst) {
+    const long total = pack_chunks(planes, taps, Kp, Np, fmt);  // one thread per 16-B chunk
     const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= total) return;
-    pack_chunk(src, d1, taps, swap_ab, K, N, Kp, Np, f32, dst, q);
+    pack_chunk(src, d1, taps, swap_ab, K, N, Kp, Np, fmt, dst, q);
 }
 
 // several weight tensors in one launch (a training step packs every layer twice: forward and data-gradient panels)
@@ -1491,7 +1498,7 @@ constexpr int kPackJobs = 48;
 struct PackJob {
     const float* src;
     unsigned short* dst;
-    int d1, taps, swap_ab, K, N, Kp, Np, f32;
+    int d1, taps, swap_ab, K, N, Kp, Np, fmt;
 };
 struct PackTable {
     PackJob job[kPackJobs];
@@ -1505,14 +1512,14 @@ __global__ void pack_weights_batched_kernel(const PackTable t) {
     int j = 0;
     while (q >= t.end[j]) j++;
     const PackJob& b = t.job[j];
-    pack_chunk(b.src, b.d1, b.taps, b.swap_ab, b.K, b.N, b.Kp, b.Np, b.f32, b.dst, q - (j ? t.end[j - 1] : 0));
+    pack_chunk(b.src, b.d1, b.taps, b.swap_ab, b.K, b.N, b.Kp, b.Np, b.fmt, b.dst, q - (j ? t.end[j - 1] : 0));
 }
 
 __device__ __forceinline__ void pack_chunk(const float* __restrict__ src, int d1, int taps, int swap_ab, int K, int N, int Kp, int Np,
-                                           int f32, unsigned short* __restrict__ dst, long q) {
+                                           int fmt, unsigned short* __restrict__ dst, long q) {
     const int n = (int)(q % Np);
     long t = q / Np;
-    if (f32) {  // [tap][Kp / 4][Np][4] fp32, unrounded
+    if (fmt == kPackF32) {  // [tap][Kp / 4][Np][4] fp32, unrounded
         const int k4 = (int)(t % (Kp / 4));
         const int tap = (int)(t / (Kp / 4));
         float f[4];
@@ -1544,10 +1551,14 @@ __device__ __forceinline__ void pack_chunk(const float* __restrict__ src, int d1
                 const int ia = swap_ab ? k : n, ib = swap_ab ? n : k;  // src[ia][ib][tap]
                 v = src[((long)ia * d1 + ib) * taps + tap];
             }
-            const float hi = round_bf16(v);
-            f[z] = plane == 0 ? hi : (v - hi);
+            if (fmt == kPackF16) {
+                f[z] = v;
+            } else {
+                const float hi = round_bf16(v);
+                f[z] = plane == 0 ? hi : (v - hi);
+            }
         }
-        w[e] = pack_bf16(f[0], f[1]);
+        w[e] = fmt == kPackF16 ? liso_e16::F16::pack(f[0], f[1]) : pack_bf16(f[0], f[1]);
     }
     *reinterpret_cast<uint4*>(dst + q * 8) = make_uint4(w[0], w[1], w[2], w[3]);
 }
@@ -1720,20 +1731,22 @@ extern "C" {
 
 size_t liso_conv_packed_bytes(int k_channels, int n_channels, int taps, int mode) {
     if (k_channels <= 0 || n_channels <= 0 || taps <= 0) return 0;
-    const size_t planes = mode == LISO_CONV_BF16 ? 1 : 2;  // (exact fp32: 4 B per element = the bytes of two bf16 planes)
+    if (mode != LISO_CONV_BF16 && mode != LISO_CONV_F32X3 && mode != LISO_CONV_F32 && mode != LISO_CONV_F16) return 0;
+    const size_t planes = (mode == LISO_CONV_BF16 || mode == LISO_CONV_F16) ? 1 : 2;  // (exact fp32: 4 B per element = the bytes of two bf16 planes)
     return planes * (size_t)taps * round_up(k_channels, 16) * round_up(n_channels, 64) * 2;
 }
 
 int liso_conv_pack_weights(const float* src, int d0, int d1, int kh, int kw, int transposed, int for_dgrad, int mode, void* dst,
                            void* stream) {
     if (!src || !dst || d0 <= 0 || d1 <= 0 || kh <= 0 || kw <= 0) return LISO_EINVAL;
+    if (mode != LISO_CONV_BF16 && mode != LISO_CONV_F32X3 && mode != LISO_CONV_F32 && mode != LISO_CONV_F16) return LISO_EINVAL;
     const bool same = (transposed != 0) == (for_dgrad != 0);
     const int K = same ? d1 : d0, N = same ? d0 : d1;
     const int Kp = round_up(K, 16), Np = round_up(N, 64), taps = kh * kw, planes = mode == LISO_CONV_F32X3 ? 2 : 1;
-    const int f32 = mode == LISO_CONV_F32;
-    const long total = pack_chunks(planes, taps, Kp, Np, f32);
+    const int fmt = pack_format(mode);
+    const long total = pack_chunks(planes, taps, Kp, Np, fmt);
     pack_weights_kernel<<<(int)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, d0, d1, taps, same ? 0 : 1, K, N, Kp, Np,
-                                                                                      planes, f32, (unsigned short*)dst);
+                                                                                      planes, fmt, (unsigned short*)dst);
     return check_launch();
 }
 
@@ -1747,12 +1760,13 @@ int liso_conv_pack_weights_batched(const liso_conv_pack_job* jobs, int n_jobs, v
         for (int i = 0; i < t.n; i++) {
             const liso_conv_pack_job& j = jobs[base + i];
             if (!j.src || !j.dst || j.d0 <= 0 || j.d1 <= 0 || j.kh <= 0 || j.kw <= 0) return LISO_EINVAL;
+            if (j.mode != LISO_CONV_BF16 && j.mode != LISO_CONV_F32X3 && j.mode != LISO_CONV_F32 && j.mode != LISO_CONV_F16) return LISO_EINVAL;
             const bool same = (j.transposed != 0) == (j.for_dgrad != 0);
             const int K = same ? j.d1 : j.d0, N = same ? j.d0 : j.d1;
             const int Kp = round_up(K, 16), Np = round_up(N, 64), taps = j.kh * j.kw, planes = j.mode == LISO_CONV_F32X3 ? 2 : 1;
-            const int f32 = j.mode == LISO_CONV_F32;
-            t.job[i] = PackJob{j.src, (unsigned short*)j.dst, j.d1, taps, same ? 0 : 1, K, N, Kp, Np, f32};
-            run += pack_chunks(planes, taps, Kp, Np, f32);
+            const int fmt = pack_format(j.mode);
+            t.job[i] = PackJob{j.src, (unsigned short*)j.dst, j.d1, taps, same ? 0 : 1, K, N, Kp, Np, fmt};
+            run += pack_chunks(planes, taps, Kp, Np, fmt);
             t.end[i] = run;
         }
         pack_weights_batched_kernel<<<(unsigned)((run + 255) / 256), 256, 0, (hipStream_t)stream>>>(t);
@@ -1813,6 +1827,7 @@ int liso_conv_forward_sparse(const liso_conv_desc* d, const void* x, const void*
     const bool x3 = d->mode == LISO_CONV_F32X3;
     const bool of32 = x3 || d->out_f32;
     const bool f32 = d->mode == LISO_CONV_F32;
+    const bool h16 = d->mode == LISO_CONV_F16;  // (plans as BF16: make_plan treats the two 16-bit modes alike)
 #define LISO_GO(MODE, MI, NJ, OF, CSA, CSB) return p.cs == CSA ? launch<MODE, MI, NJ, OF, CSA>(*d, p, st) : launch<MODE, MI, NJ, OF, CSB>(*d, p, st)
 #define LISO_SEL(MODE, OF, CSA, CSB)                  \
     do {                                    \
@@ -1833,6 +1848,9 @@ int liso_conv_forward_sparse(const liso_conv_desc* d, const void* x, const void*
         if (x3) {
             if (p.mi == 1 && p.nj == 3) return launch_roles<LISO_CONV_F32X3, 1, 3, true, 9>(*d, p, st);
             LISO_ROLES(LISO_CONV_F32X3, true);
+        } else if (h16) {
+            if (of32) LISO_ROLES(LISO_CONV_F16, true);
+            else LISO_ROLES(LISO_CONV_F16, false);
         } else if (of32) {
             LISO_ROLES(LISO_CONV_BF16, true);
         } else {
@@ -1853,6 +1871,8 @@ int liso_conv_forward_sparse(const liso_conv_desc* d, const void* x, const void*
         if (p.mi == 2 && p.nj == 3) return launch_1x1<MODE, 2, 3, OF>(*d, p, st);          \
     } while (0)
         if (x3) LISO_D1(LISO_CONV_F32X3, true);
+        else if (h16 && of32) LISO_D1(LISO_CONV_F16, true);
+        else if (h16) LISO_D1(LISO_CONV_F16, false);
         else if (of32) LISO_D1(LISO_CONV_BF16, true);
         else LISO_D1(LISO_CONV_BF16, false);
 #undef LISO_D1
@@ -1872,6 +1892,8 @@ int liso_conv_forward_sparse(const liso_conv_desc* d, const void* x, const void*
         LISO_GO(LISO_CONV_F32X3, 1, 3, true, 32, 16);
     }
     if (x3) LISO_SEL(LISO_CONV_F32X3, true, 32, 16);
+    if (h16 && of32) LISO_SEL(LISO_CONV_F16, true, 64, 32);
+    if (h16) LISO_SEL(LISO_CONV_F16, false, 64, 32);
     if (of32) LISO_SEL(LISO_CONV_BF16, true, 64, 32);
     LISO_SEL(LISO_CONV_BF16, false, 64, 32);
 #undef LISO_SEL

@@ -225,6 +225,11 @@ void plan_taps(const liso_conv_desc& d, Plan* p) {
 }
 
 bool make_plan(const liso_conv_desc& d, Plan* p) {
+    if (d.mode == LISO_CONV_F16) {  // fp16 tensors: the bytes, tiles and MFMA rate of BF16, so the same plan
+        liso_conv_desc e = d;
+        e.mode = LISO_CONV_BF16;
+        return make_plan(e, p);
+    }
     if (d.batch <= 0 || d.ci <= 0 || d.co <= 0 || d.n_classes < 1 || d.n_classes > LISO_CONV_MAX_CLASSES) return false;
     if (d.n_taps < 1 || d.n_taps > LISO_CONV_MAX_TAPS || d.class_tap_begin[0] != 0 || d.class_tap_begin[d.n_classes] != d.n_taps)
         return false;

@@ -18,6 +18,7 @@
 
 #include "../../include/liso_conv.h"
 #include "../../include/liso_iou3d.h"
+#include "elem16.h"
 #include "per_device.h"
 
 namespace {
@@ -81,6 +82,7 @@ __device__ __forceinline__ bf8 tr_pair(const unsigned char* p0, const unsigned c
 
 template <int MODE, int TG>
 __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_kernel(const liso_conv_desc d, const WgArgs a) {
+    using E = typename liso_e16::Elem<MODE>::T;  // the 16-bit element (bf16 | fp16; F32X3: the bf16 of its hi / lo planes)
     constexpr bool X3 = MODE == LISO_CONV_F32X3;
     constexpr bool F32 = MODE == LISO_CONV_F32;  // exact fp32 on v_mfma_f32_32x32x2_f32: fp32 tiles, plain 4-B LDS reads
     constexpr bool FIN = X3 || F32;
@@ -197,13 +199,13 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_kernel(const liso_conv
                 unsigned w[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    float f0 = fmaf(bf16_lo(w[e]), sc[2 * e], sh[2 * e]);
-                    float f1 = fmaf(bf16_hi(w[e]), sc[2 * e + 1], sh[2 * e + 1]);
+                    float f0 = fmaf(E::lo(w[e]), sc[2 * e], sh[2 * e]);
+                    float f1 = fmaf(E::hi(w[e]), sc[2 * e + 1], sh[2 * e + 1]);
                     if (d.in_relu) {
                         f0 = fmaxf(f0, 0.0f);
                         f1 = fmaxf(f1, 0.0f);
                     }
-                    w[e] = pack_bf16(f0, f1);
+                    w[e] = E::pack(f0, f1);
                 }
                 o = make_uint4(w[0], w[1], w[2], w[3]);
             }
@@ -243,8 +245,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_kernel(const liso_conv
                     const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
-                        bsum[2 * e] += bf16_lo(w[e]);
-                        bsum[2 * e + 1] += bf16_hi(w[e]);
+                        bsum[2 * e] += E::lo(w[e]);
+                        bsum[2 * e + 1] += E::hi(w[e]);
                     }
                 }
             }
@@ -296,7 +298,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_kernel(const liso_conv
                         acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i], 0, 0, 0);
                         acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i], 0, 0, 0);
                     }
-                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i], 0, 0, 0);
+                    acc[i] = E::mfma(ah, bh, acc[i]);
                 }
                 // keep at most 3 taps' fragments in flight: with 9 accumulator tiles live the scheduler otherwise hoists all
                 // 18 transposing reads of a k-step above the first MFMA and spills
@@ -517,6 +519,7 @@ constexpr int RPS = 128;  // LDS bytes per pixel and plane (64 bf16 channels)
 // memory time than its inputs: profiles/r06_wgrad_stamps.txt.
 template <int MODE, int TH, int S, int CIW>
 __global__ __launch_bounds__(kRsThreads, 1) void conv_wgrad_rs3_kernel(const liso_conv_desc d, const WgArgs a) {
+    using E = typename liso_e16::Elem<MODE>::T;
     constexpr bool X3 = MODE == LISO_CONV_F32X3;
     constexpr int PLANES = X3 ? 2 : 1;
     constexpr int IW = (TW - 1) * S + 3, IH = (TH - 1) * S + 3;  // halo tile (padding 1)
@@ -647,13 +650,13 @@ __global__ __launch_bounds__(kRsThreads, 1) void conv_wgrad_rs3_kernel(const lis
                         unsigned w[4] = {o.x, o.y, o.z, o.w};
 #pragma unroll
                         for (int e = 0; e < 4; e++) {
-                            float f0 = fmaf(bf16_lo(w[e]), sc[2 * e], sh[2 * e]);
-                            float f1 = fmaf(bf16_hi(w[e]), sc[2 * e + 1], sh[2 * e + 1]);
+                            float f0 = fmaf(E::lo(w[e]), sc[2 * e], sh[2 * e]);
+                            float f1 = fmaf(E::hi(w[e]), sc[2 * e + 1], sh[2 * e + 1]);
                             if (d.in_relu) {
                                 f0 = fmaxf(f0, 0.0f);
                                 f1 = fmaxf(f1, 0.0f);
                             }
-                            w[e] = pack_bf16(f0, f1);
+                            w[e] = E::pack(f0, f1);
                         }
                         o = make_uint4(w[0], w[1], w[2], w[3]);
                     }
@@ -688,8 +691,8 @@ __global__ __launch_bounds__(kRsThreads, 1) void conv_wgrad_rs3_kernel(const lis
                         const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                         for (int e = 0; e < 4; e++) {
-                            bsum[2 * e] += bf16_lo(w[e]);
-                            bsum[2 * e + 1] += bf16_hi(w[e]);
+                            bsum[2 * e] += E::lo(w[e]);
+                            bsum[2 * e + 1] += E::hi(w[e]);
                         }
                     }
                 }
@@ -777,7 +780,7 @@ __global__ __launch_bounds__(kRsThreads, 1) void conv_wgrad_rs3_kernel(const lis
             acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i], 0, 0, 0);
             acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i], 0, 0, 0);
         }
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i], 0, 0, 0);
+        acc[i] = E::mfma(ah, bh, acc[i]);
     };
 
 #ifdef LISO_WGRAD_STAMPS
@@ -972,6 +975,11 @@ struct WgPlan {
 };
 
 bool make_plan_impl(const liso_conv_desc& d, WgPlan* p, bool compact) {
+    if (d.mode == LISO_CONV_F16) {  // fp16 tensors: the bytes and MFMA rate of BF16, so the same plan
+        liso_conv_desc e = d;
+        e.mode = LISO_CONV_BF16;
+        return make_plan_impl(e, p, compact);
+    }
     if (d.batch <= 0 || d.ci <= 0 || d.co <= 0 || d.n_classes < 1 || d.n_classes > LISO_CONV_MAX_CLASSES) return false;
     if (d.n_taps < 1 || d.n_taps > LISO_CONV_MAX_TAPS || d.class_tap_begin[0] != 0 || d.class_tap_begin[d.n_classes] != d.n_taps)
         return false;
@@ -1362,6 +1370,11 @@ struct Rs3Plan {
 bool make_rs3_plan(const liso_conv_desc& d, Rs3Plan* p) {
     if (const char* e = getenv("LISO_WGRAD_RS3"))  // experiments / A-B runs: 0 = the generic kernel everywhere
         if (atoi(e) == 0) return false;
+    if (d.mode == LISO_CONV_F16) {
+        liso_conv_desc e = d;
+        e.mode = LISO_CONV_BF16;
+        return make_rs3_plan(e, p);
+    }
     if ((d.mode != LISO_CONV_BF16 && d.mode != LISO_CONV_F32X3) || d.n_classes != 1 || d.n_taps != 9 || d.w_taps != 9) return false;
     const bool x3 = d.mode == LISO_CONV_F32X3;
     const int vec = x3 ? 4 : 8;
@@ -1620,7 +1633,8 @@ int liso_conv_wgrad(const liso_conv_desc* d, const void* x, const float* in_scal
                     void* stream) {
     if (!d || !x || !dy || !dw || !workspace) return LISO_EINVAL;
     if ((in_scale == nullptr) != (in_shift == nullptr)) return LISO_EINVAL;
-    const int vec = d->mode == LISO_CONV_BF16 ? 8 : 4;
+    const bool h16 = d->mode == LISO_CONV_F16;
+    const int vec = (d->mode == LISO_CONV_BF16 || h16) ? 8 : 4;
     if (dy_pix_stride % vec || dy_pix_stride < d->co || (((uintptr_t)x | (uintptr_t)dy) & 15)) return LISO_EINVAL;
     if (d->wgrad_co < 0 || d->wgrad_co > d->co) return LISO_EINVAL;
     Rs3Plan r3;
@@ -1635,7 +1649,13 @@ int liso_conv_wgrad(const liso_conv_desc* d, const void* x, const float* in_scal
         r3.a.bias_slab = dbias ? (float*)((char*)workspace + r3.slab_bytes) : nullptr;
         hipStream_t st3 = (hipStream_t)stream;
         int rc3;
-        if (r3.a.ci_w == 32)
+        if (h16 && r3.a.ci_w == 32)
+            rc3 = r3.th == 8 ? launch_rs3<LISO_CONV_F16, 8, 1, 32>(*d, r3, st3) : launch_rs3<LISO_CONV_F16, 4, 1, 32>(*d, r3, st3);
+        else if (h16)
+            rc3 = r3.stride == 2 ? launch_rs3<LISO_CONV_F16, 3, 2>(*d, r3, st3)
+                  : r3.th == 8   ? launch_rs3<LISO_CONV_F16, 8, 1>(*d, r3, st3)
+                                 : launch_rs3<LISO_CONV_F16, 4, 1>(*d, r3, st3);
+        else if (r3.a.ci_w == 32)
             rc3 = d->mode == LISO_CONV_F32X3 ? launch_rs3<LISO_CONV_F32X3, 3, 1, 32>(*d, r3, st3)
                   : r3.th == 8           ? launch_rs3<LISO_CONV_BF16, 8, 1, 32>(*d, r3, st3)
                                          : launch_rs3<LISO_CONV_BF16, 4, 1, 32>(*d, r3, st3);
@@ -1667,6 +1687,11 @@ int liso_conv_wgrad(const liso_conv_desc* d, const void* x, const float* in_scal
         rc = p.tg == 7   ? launch<LISO_CONV_F32X3, 7>(*d, p, st)
              : p.tg == 3 ? launch<LISO_CONV_F32X3, 3>(*d, p, st)
                          : launch<LISO_CONV_F32X3, 1>(*d, p, st);
+    else if (h16)
+        rc = p.tg == 9   ? launch<LISO_CONV_F16, 9>(*d, p, st)
+             : p.tg == 7 ? launch<LISO_CONV_F16, 7>(*d, p, st)
+             : p.tg == 3 ? launch<LISO_CONV_F16, 3>(*d, p, st)
+                         : launch<LISO_CONV_F16, 1>(*d, p, st);
     else
         rc = p.tg == 9   ? launch<LISO_CONV_BF16, 9>(*d, p, st)
              : p.tg == 7 ? launch<LISO_CONV_BF16, 7>(*d, p, st)

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/liso_iou3d.h"  // error codes
+#include "../../include/liso_conv.h"  // element codes (LISO_ELEM_*)
 #include "../../include/liso_pillars.h"
 
 namespace {
@@ -593,6 +594,8 @@ template <> __device__ __forceinline__ void store_out<__hip_bfloat16>(__hip_bflo
 template <typename T> __device__ __forceinline__ float load_in(const T* p);
 template <> __device__ __forceinline__ float load_in<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float load_in<__hip_bfloat16>(const __hip_bfloat16* p) { return __bfloat162float(*p); }
+template <> __device__ __forceinline__ void store_out<_Float16>(_Float16* p, float v) { *p = (_Float16)v; }  // (round to nearest even)
+template <> __device__ __forceinline__ float load_in<_Float16>(const _Float16* p) { return (float)*p; }
 
 // stage the rows of pillars [v0, v0 + kGroup) of one wave step: returns the group's first row offset, fills off[] (lane
 // g holds pt_off[v0+g] for g <= kGroup) and copies the rows into `frow` with 16-B loads
@@ -970,6 +973,7 @@ int liso_pfn_forward_scatter(const float* feat, const int* pt_off, const int* vo
                              float* occupancy, void* stream) {
     if (!cfg_ok(cfg, batch) || !feat || !pt_off || !voxel_cell || !cell_to_voxel || !weight || !bn_out || !canvas || !occupancy)
         return LISO_EINVAL;
+    if (out_bf16 != LISO_ELEM_F32 && out_bf16 != LISO_ELEM_BF16 && out_bf16 != LISO_ELEM_F16) return LISO_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const long cells = (long)batch * cfg->gx * cfg->gy;
     const int rows = batch * cfg->max_voxels;
@@ -979,13 +983,16 @@ int liso_pfn_forward_scatter(const float* feat, const int* pt_off, const int* vo
     if (pfn_blocks > 4096) pfn_blocks = 4096;
     const unsigned grid = (unsigned)(zero_blocks + pfn_blocks);
 #define LISO_FWD(CC, T) pfn_forward_kernel<CC, T><<<grid, kPfnThreads, 0, st>>>(feat, pt_off, voxel_cell, rows, cfg->max_points, cells, zero_blocks, cell_to_voxel, weight, bn_out, (T*)canvas, occupancy)
-    switch (cfg->n_channels * 2 + (out_bf16 ? 1 : 0)) {
-        case 6: LISO_FWD(3, float); break;
-        case 7: LISO_FWD(3, __hip_bfloat16); break;
-        case 8: LISO_FWD(4, float); break;
-        case 9: LISO_FWD(4, __hip_bfloat16); break;
-        case 10: LISO_FWD(5, float); break;
-        default: LISO_FWD(5, __hip_bfloat16); break;
+    switch (cfg->n_channels * 3 + out_bf16) {  // (n_channels 3..5, element code 0..2)
+        case 9: LISO_FWD(3, float); break;
+        case 10: LISO_FWD(3, __hip_bfloat16); break;
+        case 11: LISO_FWD(3, _Float16); break;
+        case 12: LISO_FWD(4, float); break;
+        case 13: LISO_FWD(4, __hip_bfloat16); break;
+        case 14: LISO_FWD(4, _Float16); break;
+        case 15: LISO_FWD(5, float); break;
+        case 16: LISO_FWD(5, __hip_bfloat16); break;
+        default: LISO_FWD(5, _Float16); break;
     }
 #undef LISO_FWD
     return check_launch();
@@ -998,6 +1005,7 @@ int liso_pfn_backward(const float* feat, const int* pt_off, const int* voxel_cel
     if (!cfg_ok(cfg, batch) || !feat || !pt_off || !voxel_cell || !num_voxels || !weight || !gamma || !bn_out || !grad_canvas ||
         !grad_weight || !grad_gamma || !grad_beta || !partials || (training && !moments))
         return LISO_EINVAL;
+    if (grad_bf16 != LISO_ELEM_F32 && grad_bf16 != LISO_ELEM_BF16 && grad_bf16 != LISO_ELEM_F16) return LISO_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int rows = batch * cfg->max_voxels;
     const int grid = pfn_grid((rows + kGroup - 1) / kGroup);
@@ -1013,13 +1021,16 @@ int liso_pfn_backward(const float* feat, const int* pt_off, const int* voxel_cel
                                                            bn_out, moments, training, grad_weight, grad_gamma,       \
                                                            grad_beta);                                               \
     } while (0)
-    switch (cfg->n_channels * 2 + (grad_bf16 ? 1 : 0)) {
-        case 6: LISO_BWD(3, float); break;
-        case 7: LISO_BWD(3, __hip_bfloat16); break;
-        case 8: LISO_BWD(4, float); break;
-        case 9: LISO_BWD(4, __hip_bfloat16); break;
-        case 10: LISO_BWD(5, float); break;
-        default: LISO_BWD(5, __hip_bfloat16); break;
+    switch (cfg->n_channels * 3 + grad_bf16) {  // (n_channels 3..5, element code 0..2)
+        case 9: LISO_BWD(3, float); break;
+        case 10: LISO_BWD(3, __hip_bfloat16); break;
+        case 11: LISO_BWD(3, _Float16); break;
+        case 12: LISO_BWD(4, float); break;
+        case 13: LISO_BWD(4, __hip_bfloat16); break;
+        case 14: LISO_BWD(4, _Float16); break;
+        case 15: LISO_BWD(5, float); break;
+        case 16: LISO_BWD(5, __hip_bfloat16); break;
+        default: LISO_BWD(5, _Float16); break;
     }
 #undef LISO_BWD
     return check_launch();

@@ -21,6 +21,7 @@
 
 #include "../../include/liso_conv.h"
 #include "../../include/liso_iou3d.h"
+#include "elem16.h"
 
 namespace {
 
@@ -177,11 +178,14 @@ __device__ __forceinline__ int class_of_block(const int* __restrict__ seg, int p
     return cls;
 }
 
-// BF16: bf16 tensors, one MFMA per product; otherwise fp32 tensors in F32X3 arithmetic (hi * hi + hi * lo + lo * hi, small terms first)
-template <int K, int CO, bool BF16>
+// EL (LISO_ELEM_*) = BF16 / F16: 16-bit tensors, one MFMA per product; F32: fp32 tensors in F32X3 arithmetic (hi * hi + hi * lo + lo * hi,
+// small terms first)
+template <int K, int CO, int EL>
 __global__ __launch_bounds__(256) void stem_taps_kernel(const void* __restrict__ xv, long xps, const int* __restrict__ cells,
                                                         const int* __restrict__ seg, const uint4* __restrict__ wp,
                                                         float* __restrict__ prod) {
+    constexpr bool H16 = EL != LISO_ELEM_F32;  // 16-bit tensors
+    using E = typename liso_e16::Elem<EL == LISO_ELEM_F16 ? LISO_CONV_F16 : LISO_CONV_BF16>::T;
     using G = Geo<K>;
     constexpr int ROWF = G::SLOTS * CO, NT = CO / 32, KP8 = CI / 8;
     // 32 cells per block; the taps of the cells' class are dealt to the four waves (a block of 128 cells with every wave walking all
@@ -199,7 +203,7 @@ __global__ __launch_bounds__(256) void stem_taps_kernel(const void* __restrict__
         const size_t cell = (size_t)cells[p < end ? p : row0];
 #pragma unroll
         for (int ks = 0; ks < 4; ks++) {
-            if constexpr (BF16) {
+            if constexpr (H16) {
                 ah[ks] = *reinterpret_cast<const uint4*>((const unsigned short*)xv + cell * xps + ks * 16 + h * 8);
                 al[ks] = ah[ks];
             } else {
@@ -220,18 +224,18 @@ __global__ __launch_bounds__(256) void stem_taps_kernel(const void* __restrict__
 #pragma unroll
                 for (int ks = 0; ks < 4; ks++) {  // B fragment: output channel nt * 32 + r, input channels ks * 16 + h * 8 .. + 7
                     bh[ks] = wp[((size_t)(0 * G::TAPS + tap) * KP8 + ks * 2 + h) * NP + nt * 32 + r];
-                    if constexpr (!BF16) bl[ks] = wp[((size_t)(1 * G::TAPS + tap) * KP8 + ks * 2 + h) * NP + nt * 32 + r];
+                    if constexpr (!H16) bl[ks] = wp[((size_t)(1 * G::TAPS + tap) * KP8 + ks * 2 + h) * NP + nt * 32 + r];
                 }
                 f16v acc;
 #pragma unroll
                 for (int i = 0; i < 16; i++) acc[i] = 0.0f;
 #pragma unroll
                 for (int ks = 0; ks < 4; ks++) {
-                    if constexpr (!BF16) {
+                    if constexpr (!H16) {
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(al[ks]), as_bf8(bh[ks]), acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(ah[ks]), as_bf8(bl[ks]), acc, 0, 0, 0);
                     }
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(ah[ks]), as_bf8(bh[ks]), acc, 0, 0, 0);
+                    acc = E::mfma(ah[ks], bh[ks], acc);
                 }
                 float* dst = prod + (size_t)row0 * ROWF + slot * CO + nt * 32 + r;  // acc[i]: cell row 8 * (i / 4) + 4 * h + i % 4
 #pragma unroll
@@ -245,11 +249,13 @@ __global__ __launch_bounds__(256) void stem_taps_kernel(const void* __restrict__
 }
 
 // ---- 3. every output pixel gathers the tap products of its window ------------------------------------------------------------------
-template <int K, int CO, bool BF16>
+template <int K, int CO, int EL>
 __global__ __launch_bounds__(256) void stem_gather_kernel(const unsigned* __restrict__ bitmap, int words, const int* __restrict__ cell_pos,
                                                           const float* __restrict__ prod, const float* __restrict__ bias, int hi, int wi,
                                                           int ho, int wo, int relu, int groups, void* __restrict__ outv,
                                                           float* __restrict__ stats_partial, const float* __restrict__ stats_shift) {
+    constexpr bool H16 = EL != LISO_ELEM_F32;  // 16-bit tensors
+    using E = typename liso_e16::Elem<EL == LISO_ELEM_F16 ? LISO_CONV_F16 : LISO_CONV_BF16>::T;
     using G = Geo<K>;
     // 16 channels per lane (the window bookkeeping is per pixel: with 4 channels per lane 16 lanes repeated it and the kernel was
     // bound by exactly that, 42 us for 262k pixels), LPP lanes per pixel, PPB pixels per pass
@@ -309,12 +315,12 @@ __global__ __launch_bounds__(256) void stem_gather_kernel(const unsigned* __rest
 #pragma unroll
         for (int e = 0; e < CPL; e++) {
             if (relu) acc[e] = fmaxf(acc[e], 0.f);
-            if constexpr (BF16) acc[e] = round_bf16(acc[e]);  // (statistics of the stored, rounded values, like the dense epilogue)
+            if constexpr (H16) acc[e] = E::round(acc[e]);  // (statistics of the stored, rounded values, like the dense epilogue)
         }
-        if constexpr (BF16) {
+        if constexpr (H16) {
             uint4* dst = reinterpret_cast<uint4*>((unsigned short*)outv + pix * CO + CPL * q);
-            dst[0] = make_uint4(pack_bf16(acc[0], acc[1]), pack_bf16(acc[2], acc[3]), pack_bf16(acc[4], acc[5]), pack_bf16(acc[6], acc[7]));
-            dst[1] = make_uint4(pack_bf16(acc[8], acc[9]), pack_bf16(acc[10], acc[11]), pack_bf16(acc[12], acc[13]), pack_bf16(acc[14], acc[15]));
+            dst[0] = make_uint4(E::pack(acc[0], acc[1]), E::pack(acc[2], acc[3]), E::pack(acc[4], acc[5]), E::pack(acc[6], acc[7]));
+            dst[1] = make_uint4(E::pack(acc[8], acc[9]), E::pack(acc[10], acc[11]), E::pack(acc[12], acc[13]), E::pack(acc[14], acc[15]));
         } else {
             float4* dst = reinterpret_cast<float4*>((float*)outv + pix * CO + CPL * q);
 #pragma unroll
@@ -352,10 +358,12 @@ __global__ __launch_bounds__(256) void stem_gather_kernel(const unsigned* __rest
 // dx[cell][ci] = sum over the taps of the cell's class of dy[(iy + P - ky) / 2][(ix + P - kx) / 2][:] . W[tap][:, ci]: the pillar encoder's
 // backward reads the canvas gradient at occupied cells only (the rest of dx is the caller's zero fill).  A = the gathered dy rows of 32
 // cells (K dimension = output channels), B = the data-gradient panels of the tap; all taps of the class add into one accumulator.
-template <int K, int CO, bool BF16>
+template <int K, int CO, int EL>
 __global__ __launch_bounds__(256) void stem_dgrad_kernel(const void* __restrict__ dyv, long gps, const int* __restrict__ cells,
                                                          const int* __restrict__ seg, const uint4* __restrict__ wp, int hi, int wi,
                                                          int ho, int wo, void* __restrict__ dxv, long dxps) {
+    constexpr bool H16 = EL != LISO_ELEM_F32;  // 16-bit tensors
+    using E = typename liso_e16::Elem<EL == LISO_ELEM_F16 ? LISO_CONV_F16 : LISO_CONV_BF16>::T;
     using G = Geo<K>;
     constexpr int KSTEPS = CO / 16, KP8 = CO / 8, NT = CI / 32;
     const int pos0 = blockIdx.x * 128;
@@ -385,7 +393,7 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(const void* __restrict_
 #pragma unroll
             for (int ks = 0; ks < KSTEPS; ks++) {
                 uint4 ah, al;
-                if constexpr (BF16) {
+                if constexpr (H16) {
                     ah = ok ? *reinterpret_cast<const uint4*>((const unsigned short*)dyv + orow + ks * 16 + h * 8) : make_uint4(0, 0, 0, 0);
                     al = ah;
                 } else {
@@ -395,12 +403,12 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(const void* __restrict_
 #pragma unroll
                 for (int nt = 0; nt < NT; nt++) {
                     const uint4 bh = wp[((size_t)(0 * G::TAPS + tap) * KP8 + ks * 2 + h) * NP + nt * 32 + r];
-                    if constexpr (!BF16) {
+                    if constexpr (!H16) {
                         const uint4 bl = wp[((size_t)(1 * G::TAPS + tap) * KP8 + ks * 2 + h) * NP + nt * 32 + r];
                         acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(al), as_bf8(bh), acc[nt], 0, 0, 0);
                         acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(ah), as_bf8(bl), acc[nt], 0, 0, 0);
                     }
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(ah), as_bf8(bh), acc[nt], 0, 0, 0);
+                    acc[nt] = E::mfma(ah, bh, acc[nt]);
                 }
             }
         }
@@ -412,9 +420,8 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(const void* __restrict_
         if (row0 + rr < end) {
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) {
-                if constexpr (BF16) {
-                    const __bf16 v = (__bf16)acc[nt][i];
-                    ((unsigned short*)dxv)[(size_t)c2 * dxps + nt * 32 + r] = __builtin_bit_cast(unsigned short, v);
+                if constexpr (H16) {
+                    ((unsigned short*)dxv)[(size_t)c2 * dxps + nt * 32 + r] = (unsigned short)(E::pack(acc[nt][i], 0.0f) & 0xffffu);
                 } else {
                     ((float*)dxv)[(size_t)c2 * dxps + nt * 32 + r] = acc[nt][i];
                 }
@@ -488,6 +495,7 @@ int liso_sparse_conv_forward(const void* x, long x_pix_stride, int is_bf16, cons
                              void* stream) {
     Layout l;
     if (!x || !occupancy || !w_packed || !y || !workspace) return LISO_EINVAL;
+    if (is_bf16 != LISO_ELEM_F32 && is_bf16 != LISO_ELEM_BF16 && is_bf16 != LISO_ELEM_F16) return LISO_EINVAL;
     const int vec = is_bf16 ? 8 : 4;
     if (x_pix_stride < CI || (x_pix_stride % vec) || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_packed | (uintptr_t)workspace) & 15))
         return LISO_EINVAL;
@@ -512,9 +520,10 @@ int liso_sparse_conv_forward(const void* x, long x_pix_stride, int is_bf16, cons
         stem_gather_kernel<K, CO, BF><<<gb, 256, 0, st>>>(bitmap, l.words, cell_pos, prod, bias, hi, wi, ho, wo, relu, groups, y, stats_partial, \
                                                          stats_shift);                                                                 \
     } while (0)
-    if (k == 7 && co == 32 && !is_bf16) LISO_SPARSE_FWD(7, 32, false);
-    else if (k == 3 && co == 64 && is_bf16) LISO_SPARSE_FWD(3, 64, true);
-    else if (k == 3 && co == 64 && !is_bf16) LISO_SPARSE_FWD(3, 64, false);
+    if (k == 7 && co == 32 && is_bf16 == LISO_ELEM_F32) LISO_SPARSE_FWD(7, 32, LISO_ELEM_F32);
+    else if (k == 3 && co == 64 && is_bf16 == LISO_ELEM_BF16) LISO_SPARSE_FWD(3, 64, LISO_ELEM_BF16);
+    else if (k == 3 && co == 64 && is_bf16 == LISO_ELEM_F16) LISO_SPARSE_FWD(3, 64, LISO_ELEM_F16);
+    else if (k == 3 && co == 64 && is_bf16 == LISO_ELEM_F32) LISO_SPARSE_FWD(3, 64, LISO_ELEM_F32);
     else return LISO_EINVAL;
 #undef LISO_SPARSE_FWD
     return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH;
@@ -525,6 +534,7 @@ int liso_sparse_conv_dgrad(const void* dy, long dy_pix_stride, int is_bf16, cons
                            void* workspace, size_t workspace_bytes, int reuse_lists, void* stream) {
     Layout l;
     if (!dy || (!occupancy && !reuse_lists) || !w_packed_dgrad || !dx || !workspace) return LISO_EINVAL;
+    if (is_bf16 != LISO_ELEM_F32 && is_bf16 != LISO_ELEM_BF16 && is_bf16 != LISO_ELEM_F16) return LISO_EINVAL;
     const int vec = is_bf16 ? 8 : 4;
     if (dy_pix_stride < co || (dy_pix_stride % vec) || dx_pix_stride < CI || (((uintptr_t)dy | (uintptr_t)w_packed_dgrad | (uintptr_t)workspace) & 15))
         return LISO_EINVAL;
@@ -539,9 +549,10 @@ int liso_sparse_conv_dgrad(const void* dy, long dy_pix_stride, int is_bf16, cons
     const unsigned tb = (unsigned)(l.cap / 128);
 #define LISO_SPARSE_DG(K, CO, BF) \
     stem_dgrad_kernel<K, CO, BF><<<tb, 256, 0, st>>>(dy, dy_pix_stride, cells, seg, (const uint4*)w_packed_dgrad, hi, wi, ho, wo, dx, dx_pix_stride)
-    if (k == 7 && co == 32 && !is_bf16) LISO_SPARSE_DG(7, 32, false);
-    else if (k == 3 && co == 64 && is_bf16) LISO_SPARSE_DG(3, 64, true);
-    else if (k == 3 && co == 64 && !is_bf16) LISO_SPARSE_DG(3, 64, false);
+    if (k == 7 && co == 32 && is_bf16 == LISO_ELEM_F32) LISO_SPARSE_DG(7, 32, LISO_ELEM_F32);
+    else if (k == 3 && co == 64 && is_bf16 == LISO_ELEM_BF16) LISO_SPARSE_DG(3, 64, LISO_ELEM_BF16);
+    else if (k == 3 && co == 64 && is_bf16 == LISO_ELEM_F16) LISO_SPARSE_DG(3, 64, LISO_ELEM_F16);
+    else if (k == 3 && co == 64 && is_bf16 == LISO_ELEM_F32) LISO_SPARSE_DG(3, 64, LISO_ELEM_F32);
     else return LISO_EINVAL;
 #undef LISO_SPARSE_DG
     return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH;

@@ -14,8 +14,10 @@ from liso_amd import _lib as L
 
 
 def _supported(c, dtype):
-    v = 8 if dtype == torch.bfloat16 else 4
-    return dtype in (torch.float32, torch.bfloat16) and c % v == 0 and c <= 256
+    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    v = 8 if L.is_half(dtype) else 4
+    return c % v == 0 and c <= 256
 
 
 class _BnAct(torch.autograd.Function):
@@ -34,7 +36,7 @@ class _BnAct(torch.autograd.Function):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         with torch.cuda.device(x.device):
             L.check(L.TIMER.launch("bn_fwd", lambda: lib.liso_bn_relu_fwd(
-                L.ptr(xc), int(x.dtype == torch.bfloat16), M, C, L.ptr(gamma), L.ptr(beta), L.ptr(running_mean),
+                L.ptr(xc), L.elem_code(x.dtype), M, C, L.ptr(gamma), L.ptr(beta), L.ptr(running_mean),
                 L.ptr(running_var), float(momentum), float(eps), int(training), int(relu), L.ptr(y), L.ptr(stats), L.ptr(ws),
                 nbytes, L.stream_ptr()), units=3 * M * C * xc.element_size()), "bn_relu_fwd")
         ctx.save_for_backward(xc, gamma, stats)
@@ -58,7 +60,7 @@ class _BnAct(torch.autograd.Function):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
         with torch.cuda.device(xc.device):
             L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd(
-                L.ptr(g), L.ptr(xc), int(xc.dtype == torch.bfloat16), M, C, L.ptr(gamma), L.ptr(stats), int(training),
+                L.ptr(g), L.ptr(xc), L.elem_code(xc.dtype), M, C, L.ptr(gamma), L.ptr(stats), int(training),
                 int(relu), L.ptr(dx), L.ptr(gg), L.ptr(gb), L.ptr(ws), nbytes, L.stream_ptr()),
                 units=5 * M * C * xc.element_size()), "bn_relu_bwd")
         return dx.permute(0, 3, 1, 2), gg, gb, None, None, None, None, None, None

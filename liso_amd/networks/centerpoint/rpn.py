@@ -14,6 +14,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from liso_amd import _lib as L
 from liso_amd.networks.centerpoint.fused_bn import bn_act
 from liso_amd.networks.centerpoint.norm import baurst_build_norm_layer as build_norm_layer
 from liso_amd.networks.centerpoint.weight_init import xavier_init
@@ -137,7 +138,7 @@ class RPN(nn.Module):
         specs = [MC.ConvSpec.of(d[0]) for _, _, d in taps]
         sizes = [s_.out_hw(xi.shape[2], xi.shape[3]) for s_, (xi, _, _) in zip(specs, taps)]
         chans = [d[0].out_channels for _, _, d in taps]
-        vec = 8 if x.dtype == torch.bfloat16 else 4
+        vec = 8 if L.is_half(x.dtype) else 4
         ups = []
         if len(set(sizes)) == 1 and all(c % 8 == 0 for c in chans) and sum(chans) % vec == 0:
             (ho, wo), B = sizes[0], x.shape[0]

@@ -101,6 +101,7 @@ class _PillarFeatureScatter(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum, eps,
                 out_dtype, out=None, prep=None):
+        code = L.elem_code(out_dtype)  # (TypeError before anything is allocated or launched: the canvas rows are sized by out_dtype)
         L.require_cuda(points, weight)
         lib = L.lib()
         dev = points.device
@@ -127,7 +128,7 @@ class _PillarFeatureScatter(torch.autograd.Function):
                 occupancy = torch.empty((B, 1, pcfg.gx, pcfg.gy), dtype=torch.float32, device=dev)
             L.check(L.TIMER.launch("pfn_forward_scatter", lambda: lib.liso_pfn_forward_scatter(
                 L.ptr(feat), L.ptr(pt_off), L.ptr(voxel_cell), ctypes.byref(pcfg), B, L.ptr(cell_to_voxel), L.ptr(weight),
-                L.ptr(bn_out), L.ptr(canvas), int(out_dtype == torch.bfloat16), L.ptr(occupancy), st),
+                L.ptr(bn_out), L.ptr(canvas), code, L.ptr(occupancy), st),
                 # algorithmic bytes: points read once + dense canvas (its own element size) + occupancy written once
                 units=points.numel() * 4 + canvas.numel() * canvas.element_size() + occupancy.numel() * 4),
                 "pfn_forward_scatter")
@@ -142,7 +143,7 @@ class _PillarFeatureScatter(torch.autograd.Function):
         lib = L.lib()
         dev = feat.device
         g = grad_canvas.permute(0, 2, 3, 1)
-        if g.dtype not in (torch.float32, torch.bfloat16):
+        if g.dtype not in (torch.float32, torch.bfloat16, torch.float16):
             g = g.float()
         g = g.contiguous()
         F = weight.shape[1]
@@ -153,7 +154,7 @@ class _PillarFeatureScatter(torch.autograd.Function):
         with torch.cuda.device(dev):
             L.check(lib.liso_pfn_backward(L.ptr(feat), L.ptr(pt_off), L.ptr(voxel_cell), ctypes.byref(ctx.pcfg), ctx.B,
                                           L.ptr(num_voxels), L.ptr(weight), L.ptr(gamma), L.ptr(bn_out), L.ptr(moments),
-                                          int(ctx.training), L.ptr(g), int(g.dtype == torch.bfloat16), L.ptr(gw), L.ptr(gg),
+                                          int(ctx.training), L.ptr(g), L.elem_code(g.dtype), L.ptr(gw), L.ptr(gg),
                                           L.ptr(gb), L.ptr(partials), L.stream_ptr()), "pfn_backward")
         return gw, gg, gb, None, None, None, None, None, None, None, None, None, None, None
 
@@ -186,7 +187,7 @@ class PointsPillarFeatureNetWrapper(nn.Module):
             point_cloud_range=pc_range, norm_cfg={"type": "BN1d", "eps": 0.001, "momentum": 0.01})
         self.voxel_size, self.pc_range = voxel_size, pc_range
         self.grid = tuple(int(g) for g in cfg.data.img_grid_size)
-        self.out_dtype = torch.float32  # set to torch.bfloat16 for the bf16 BEV backbone
+        self.out_dtype = torch.float32  # torch.bfloat16 / torch.float16 for the 16-bit BEV backbone
 
     def _pcfg(self, n_channels):
         c = L.PillarCfg()
@@ -236,6 +237,7 @@ class PointsPillarFeatureNetWrapper(nn.Module):
     def extract_pts_feat(self, pts, out=None, prep=None):
         """reference :86-102.  `out` (extension): (canvas rows [B, gx, gy, 64], occupancy [B, 1, gx, gy]) to write into;
         `prep` (extension): the result of `prepare(pts)` for the same clouds"""
+        L.elem_code(self.out_dtype)  # an unsupported canvas dtype raises here, before any launch
         if prep is not None:
             cat, offsets, prep = prep
         else:

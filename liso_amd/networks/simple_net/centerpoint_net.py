@@ -2,6 +2,7 @@
 `pfn`, `rpn`, `center_head`; forward(img_t0, pcls) -> (dict of NHWC maps, aux))."""
 import torch
 
+from liso_amd import _lib as L
 from liso_amd.networks.centerpoint.center_head import CenterHead
 from liso_amd.networks.centerpoint.rpn import RPN
 from liso_amd.networks.pcl_to_feature_grid.pcl_to_feature_grid import PointsPillarFeatureNetWrapper
@@ -46,7 +47,9 @@ class CenterPointStyleNet(torch.nn.Module):
         self.center_head = CenterHead(**head_conf, common_heads=common_heads, norm_cfg=dict(cp.batch_norm.kwargs))
 
     def set_compute_dtype(self, dtype):
-        """fp32 = parity configuration; bf16 = BASELINE config 3 (bf16 BEV tensors, fp32 BN stats / head outputs)."""
+        """fp32 = parity configuration; bf16 = BASELINE config 3 (bf16 BEV tensors, fp32 BN stats / head outputs); fp16 = BASELINE
+        config 5 (fp16 BEV tensors, the same fp32 parts; trained with a loss scale: DetectorTrainer(loss_scale=...))."""
+        L.elem_code(dtype)  # (TypeError: no device kernel takes that dtype)
         self.pfn.out_dtype = dtype
 
     def forward(self, img_t0, pcls, canvas=None):

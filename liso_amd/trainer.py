@@ -117,7 +117,7 @@ def side_stream(device, role, priority=0):
 
 class DetectorTrainer:
     def __init__(self, cfg, device, compute_dtype=torch.float32, total_steps=None, fused_loss=None, use_graph=False, exact=None,
-                 grad_buckets=None):
+                 grad_buckets=None, loss_scale="default"):
         """`grad_buckets` (graph path, several ranks): 2 (default) = the step is captured as TWO graphs, cut behind the backbone's first
         block (mfma_conv.GradCut): the gradients of everything downstream of the cut -- 97 % of the parameters -- are all-reduced
         between the two replays and the collective overlaps block 0's backward pass (the layers at the largest resolution), the
@@ -133,7 +133,11 @@ class DetectorTrainer:
         `use_graph`: forward + loss + backward of one step (no device->host sync on that path) are captured once per input
         shape into a hipGraph and replayed; new clouds / targets are copied into the captured input buffers.  Gradients live
         in one flat buffer: data parallelism is ONE RCCL all-reduce of that buffer after the replay (no DDP wrapper), then
-        the eager AdamW / OneCycleLR step."""
+        the eager AdamW / OneCycleLR step.
+        `loss_scale` (compute_dtype float16 only): "dynamic" (the fp16 default) = a loss scale that backs off on overflow and grows
+        after clean steps, a float = that fixed scale, None = no scaling.  The state stays on the device (liso_amd/utils/loss_scale.py):
+        the backward pass is seeded with it, steps whose gradients overflowed leave parameters and moments untouched.  bf16 / fp32
+        trainers take no loss scale."""
         from liso_amd.losses import fused_centerpoint
 
         self.cfg, self.device = cfg, device
@@ -162,6 +166,23 @@ class DetectorTrainer:
         # on the GPU the parameters, their gradients and the AdamW moments are views into four flat buffers: the update is one
         # launch, the gradient all-reduce one collective, zero_grad one memset
         self.optimizer, self.lr_scheduler = get_optimizer_scheduler(cfg, self.net, total_steps, flat=device.type == "cuda")
+        self.loss_scaler = None
+        if loss_scale == "default":
+            loss_scale = "dynamic" if compute_dtype == torch.float16 else None
+        if loss_scale is not None:
+            if compute_dtype != torch.float16:
+                raise ValueError(f"loss scaling is for fp16 training (compute_dtype {compute_dtype})")
+            if device.type != "cuda":
+                raise ValueError("fp16 training runs on the device kernels only")
+            from liso_amd.utils.loss_scale import DeviceLossScale
+
+            if loss_scale == "dynamic":
+                self.loss_scaler = DeviceLossScale(device)
+            elif isinstance(loss_scale, (int, float)) and not isinstance(loss_scale, bool):
+                self.loss_scaler = DeviceLossScale(device, init_scale=float(loss_scale), dynamic=False)
+            else:
+                raise ValueError(f"loss_scale: 'dynamic', a number or None, got {loss_scale!r}")
+            self.optimizer.loss_scale = self.loss_scaler
         if self.world > 1 and not self.use_graph:
             # ~19 MB of fp32 gradients: one flat bucket, launched as backward reaches the first layer's grads
             self.model = torch.nn.parallel.DistributedDataParallel(
@@ -260,10 +281,21 @@ class DetectorTrainer:
             return self._graph_step(pcls, targets, prep)
         self.optimizer.zero_grad(set_to_none=True)
         total, losses, _ = self.loss(pcls, targets)
-        total.backward()
+        self._backward(total)
         self.optimizer.step()
         self.lr_scheduler.step()
         return total.detach()
+
+    def _backward(self, total):
+        """total.backward(), seeded with the device-resident loss scale when there is one (read at run / replay time: no sync)"""
+        if self.loss_scaler is None:
+            total.backward()
+        else:
+            total.backward(self.loss_scaler.seed)
+
+    def loss_scale_stats(self):
+        """{scale, applied_steps, skipped_steps, growth_tracker} of the fp16 loss scale, None without one (reads the device: a sync)"""
+        return None if self.loss_scaler is None else self.loss_scaler.stats()
 
     def eager_pass(self, pcls, targets):
         """forward + loss + backward with eager launches and NO update: no collective, no optimizer / scheduler step (bench.py
@@ -276,7 +308,7 @@ class DetectorTrainer:
         ctx = self.model.no_sync() if hasattr(self.model, "no_sync") else contextlib.nullcontext()
         with ctx:
             total, _, _ = self.loss(pcls, targets)
-            total.backward()
+            self._backward(total)  # (fp16: seeded with the loss scale like the real step, so the same gradients flow)
         with torch.no_grad():
             for k, v in self.net.state_dict().items():
                 if k in bufs:
@@ -355,7 +387,7 @@ class DetectorTrainer:
                     finally:
                         rpn.grad_cut = None
                     with MC.wgrad_side(self._wgrad_stream):
-                        total.backward()
+                        self._backward(total)
                     self._body_loss = total.detach()
                 if cut is not None and part in (None, 2):
                     with MC.wgrad_side(self._wgrad_stream):

@@ -36,6 +36,9 @@ class FlatAdamW(torch.optim.Optimizer):
         self.flat_exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=dev)
         self._step = 0
         self.grad_scale = 1.0  # factor on the gradients inside the update (data parallelism: 1 / world size behind a SUM all-reduce)
+        # fp16 training: a liso_amd.utils.loss_scale.DeviceLossScale -- the update then divides the scale out, skips steps whose
+        # gradients overflowed and keeps its bias-correction step counter on the device (None: the plain update, unchanged)
+        self.loss_scale = None
         self.offsets = {id(p): o for p, o in zip(params, offs)}  # first element of every parameter inside the flat buffers
         for p, o in zip(params, offs):
             if not _dense(p.data):
@@ -59,6 +62,12 @@ class FlatAdamW(torch.optim.Optimizer):
         assert closure is None
         assert len(self.param_groups) == 1, "one parameter group (the reference's optimizer has one)"
         g = self.param_groups[0]
+        if self.loss_scale is not None:
+            with torch.cuda.device(self.flat_param.device):
+                self.loss_scale.adamw_step(self.flat_param, self.flat_grad, self.flat_exp_avg, self.flat_exp_avg_sq, self.numel, g["lr"],
+                                           g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.grad_scale)
+            torch.autograd.graph.increment_version(g["params"])
+            return
         self._step += 1
         with torch.cuda.device(self.flat_param.device):
             L.check(L.TIMER.launch("adamw_flat", lambda: L.lib().liso_adamw_step_scaled_f32(
@@ -69,11 +78,19 @@ class FlatAdamW(torch.optim.Optimizer):
         torch.autograd.graph.increment_version(g["params"])
 
     def state_dict(self):
+        if self.loss_scale is not None:  # (the applied-step counter lives on the device)
+            self._step = self.loss_scale.stats()["applied_steps"]
         for st in self.state.values():
             st["step"] = torch.tensor(float(self._step))
-        return super().state_dict()
+        sd = super().state_dict()
+        if self.loss_scale is not None:  # fp16: the loss scale's state travels with the moments (GradScaler keeps its own state_dict)
+            sd["loss_scale"] = self.loss_scale.state_dict()
+        return sd
 
     def load_state_dict(self, state_dict):
+        loss_scale = state_dict.get("loss_scale")
+        if loss_scale is not None:
+            state_dict = {k: v for k, v in state_dict.items() if k != "loss_scale"}
         views = {p: (st["exp_avg"], st["exp_avg_sq"]) for p, st in self.state.items()}
         super().load_state_dict(state_dict)
         step = 0
@@ -87,6 +104,11 @@ class FlatAdamW(torch.optim.Optimizer):
             st["exp_avg"], st["exp_avg_sq"] = m, v
             st.setdefault("step", torch.tensor(0.0))
         self._step = step
+        if self.loss_scale is not None:
+            if loss_scale is not None:  # scale, growth tracker and step counters as saved
+                self.loss_scale.load_state_dict(loss_scale)
+            else:  # (a checkpoint without a loss scale, e.g. of a bf16 / fp32 run: the scale starts afresh, the step count carries over)
+                self.loss_scale.state[3].fill_(step)
 
 
 class FlatRMSprop(torch.optim.Optimizer):

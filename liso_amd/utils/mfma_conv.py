@@ -26,8 +26,7 @@ def on_device(x):
     liso_amd/utils/host_ops.py)."""
     if not x.is_cuda:
         return False
-    if x.dtype not in (torch.bfloat16, torch.float32):
-        raise TypeError(f"liso_amd: device convolutions take bfloat16 / float32 tensors, got {x.dtype}")
+    L.elem_code(x.dtype)  # (TypeError for a dtype no kernel takes)
     return True
 
 
@@ -86,6 +85,8 @@ class fp32_arithmetic:
 def _mode(dtype):
     if dtype == torch.bfloat16:
         return L.CONV_BF16
+    if dtype == torch.float16:
+        return L.CONV_F16
     if dtype == torch.float32:
         return L.CONV_F32 if _FP32_MODE == "exact" else L.CONV_F32X3
     raise L.LisoHipError(f"mfma conv: unsupported dtype {dtype}")
@@ -343,14 +344,20 @@ def _pack_weights(weight, spec, for_dgrad, mode):
     return out
 
 
+def _half_mode(mode):
+    """bf16 / fp16 tensors: 2-byte elements, 8 channels per 16-byte group"""
+    return mode in (L.CONV_BF16, L.CONV_F16)
+
+
 def _vec(mode):
-    return 8 if mode == L.CONV_BF16 else 4
+    return 8 if _half_mode(mode) else 4
 
 
 def _timer_name(mode, kind, d=None):
     """timer family of a launch; forward / data-gradient launches of conv_roles_kernel get their own families (bench.py's `roofline`
     is about ONE kernel: rocprofv3 lists conv_roles_kernel and conv_igemm_kernel separately, so does the timer)"""
-    name = ("conv_bf16_" if mode == L.CONV_BF16 else "conv_f32x3_" if mode == L.CONV_F32X3 else "conv_f32_") + kind
+    name = ("conv_bf16_" if mode == L.CONV_BF16 else "conv_f16_" if mode == L.CONV_F16 else "conv_f32x3_" if mode == L.CONV_F32X3
+            else "conv_f32_") + kind
     if d is not None and L.TIMER.enabled:
         kind = L.lib().liso_conv_kernel_kind(ctypes.byref(d))
         name += "_roles" if kind == 1 else "_direct" if kind in (2, 3) else ""
@@ -365,12 +372,12 @@ def _flops(d):
 def _bytes(d, wgrad=False):
     """algorithmic HBM bytes of one launch: the tensor that is read + the tensor that is written once each + the weights
     (forward / data gradient: packed bf16 panels, 2 B x planes; weight gradient: x and dy read once, fp32 dW written)"""
-    es = 2 if d.mode == L.CONV_BF16 else 4
+    es = 2 if _half_mode(d.mode) else 4
     w = d.w_taps * d.ci * d.co
     if wgrad:
         return d.batch * (d.hi * d.wi * d.ci + d.ho * d.wo * d.co) * es + 4 * w
-    out_es = 4 if (d.out_f32 or d.mode != L.CONV_BF16) else 2
-    return d.batch * (d.hi * d.wi * d.ci * es + d.ho * d.wo * d.co * out_es) + w * (2 if d.mode == L.CONV_BF16 else 4)
+    out_es = 4 if (d.out_f32 or not _half_mode(d.mode)) else 2
+    return d.batch * (d.hi * d.wi * d.ci * es + d.ho * d.wo * d.co * out_es) + w * (2 if _half_mode(d.mode) else 4)
 
 
 def conv_forward(x, weight, bias, spec, in_scale=None, in_shift=None, in_relu=False, out_relu=False, out_dtype=None,
@@ -386,8 +393,10 @@ def conv_forward(x, weight, bias, spec, in_scale=None, in_shift=None, in_relu=Fa
     co = weight.shape[1] if spec.transposed else weight.shape[0]
     ho, wo = spec.out_hw(hi, wi)
     out_dtype = out_dtype or x.dtype
-    if mode != L.CONV_BF16:
+    if not _half_mode(mode):
         assert out_dtype == torch.float32
+    else:
+        assert out_dtype in (x.dtype, torch.float32), "16-bit convolutions write their own dtype or fp32"
     out_f32 = out_dtype == torch.float32
     if out is not None:
         # `out` = (channels-last buffer [B, ho, wo, C_total], first channel): the result becomes channels [first, first + co) of that
@@ -579,9 +588,9 @@ def conv_wgrad_sparse(x, occupancy, dy, weight_shape, spec, want_bias=True):
 
 def supported(x, weight, spec):
     """can the own kernels run this convolution (forward, data and weight gradient)?"""
-    if not x.is_cuda or x.dtype not in (torch.bfloat16, torch.float32):
+    if not x.is_cuda or x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
         return False
-    vec = 8 if x.dtype == torch.bfloat16 else 4
+    vec = 8 if L.is_half(x.dtype) else 4
     ci = x.shape[1]
     co = weight.shape[1] if spec.transposed else weight.shape[0]
     if ci % vec or spec.kh * spec.kw > L.CONV_MAX_TAPS:
@@ -731,7 +740,7 @@ def _bn_backward_group(g, x_raw, grp, relu, training, out=None):
     Channel slices of wider channels-last tensors are read in place (liso_bn_relu_bwd_strided); `out`: a logical-NCHW tensor (e.g. the
     group's channel slice of the concatenated input gradient) to write dx_raw into."""
     C = grp["gamma"].shape[0]
-    vec = 8 if x_raw.dtype == torch.bfloat16 else 4
+    vec = 8 if L.is_half(x_raw.dtype) else 4
     xv, xs = _rows_view(x_raw, vec)
     if xv is None:
         xv, xs = x_raw.permute(0, 2, 3, 1).contiguous(), C
@@ -751,7 +760,7 @@ def _bn_backward_group(g, x_raw, grp, relu, training, out=None):
     gb = tb if direct else torch.empty(C, dtype=torch.float32, device=xv.device)
     nbytes = lib.liso_bn_workspace_bytes(C)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=xv.device)
-    bf = int(xv.dtype == torch.bfloat16)
+    bf = L.elem_code(xv.dtype)
     units = 5 * M * C * xv.element_size()
     with torch.cuda.device(xv.device):
         if (xs, gs, ds) != (C, C, C):
@@ -1031,15 +1040,20 @@ def _dev_index(dev):
     return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
+def _sparse_mode(el):
+    """panel mode of the sparse-canvas kernels for an element code: bf16 / fp16 panels, F32X3 hi / lo panels for fp32 tensors"""
+    return {L.ELEM_BF16: L.CONV_BF16, L.ELEM_F16: L.CONV_F16}.get(int(el), L.CONV_F32X3)
+
+
 def _sparse_geometry(x_raw, weight, spec):
-    """(is_bf16, k, co) if the sparse-canvas kernels cover this convolution, else None: 7x7 / 2 / 3 with 32 filters on fp32 tensors (the
-    SLIM stem) or 3x3 / 2 / 1 with 64 filters on bf16 / fp32 tensors (the detector's first layer), 64 input channels, an even canvas
+    """(element code, k, co) if the sparse-canvas kernels cover this convolution, else None: 7x7 / 2 / 3 with 32 filters on fp32 tensors
+    (the SLIM stem) or 3x3 / 2 / 1 with 64 filters on bf16 / fp16 / fp32 tensors (the detector's first layer), 64 input channels, an even canvas
     height and a width that is a multiple of 64; fp32 tensors only in F32X3 arithmetic (the exact-fp32 mode keeps the dense kernels)"""
     if os.environ.get("LISO_SPARSE_STEM", "1") == "0" or spec.transposed or x_raw.dim() != 4:
         return None
     B, C, H, W = x_raw.shape
     geo = (spec.kh, spec.kw, spec.stride, spec.padding, weight.shape[0])
-    bf = x_raw.dtype == torch.bfloat16
+    bf = L.elem_code(x_raw.dtype) if x_raw.dtype in (torch.bfloat16, torch.float16) else 0  # (16-bit tensors: non-zero)
     if C != 64 or tuple(weight.shape[1:]) != (64, spec.kh, spec.kw) or H % 2 or W % 64:
         return None
     if geo == (7, 7, 2, 3, 32) and x_raw.dtype == torch.float32 and fp32_mode() == "x3":
@@ -1085,7 +1099,7 @@ def _sparse_stem(x_raw, occupancy, weight, bias, spec, kind, relu, stats_shift=N
     nbytes = lib.liso_sparse_conv_workspace_bytes(B, H, W, k, co, cap, 0)
     if nbytes == 0:
         return None
-    mode = L.CONV_BF16 if bf else L.CONV_F32X3
+    mode = _sparse_mode(bf)
     packed = pack_weights(weight, spec, False, mode)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     ho, wo = H // 2, W // 2
@@ -1127,7 +1141,7 @@ def _sparse_dgrad(dy, occupancy, weight, spec, x_shape, x_dtype, lists=None):
     nbytes = lib.liso_sparse_conv_workspace_bytes(B, H, W, k, co, cap, 1)
     if nbytes == 0:
         return None
-    packed = pack_weights(weight, spec, True, L.CONV_BF16 if bf else L.CONV_F32X3)
+    packed = pack_weights(weight, spec, True, _sparse_mode(bf))
     reuse = lists is not None and lists.numel() >= nbytes  # (the forward call's workspace on this canvas: its cell lists are reused)
     ws = lists if reuse else torch.empty(nbytes, dtype=torch.uint8, device=dev)
     dx = torch.zeros((B, H, W, C), dtype=x_dtype, device=dev)
@@ -1269,7 +1283,7 @@ def conv2d(layer, x, relu=False, occupancy=None, out=None):
     if x.is_cuda and not spec.transposed:
         # 1-3 (7) input channels -- the motion encoder's conv_flow1: 7x7 on the 2-channel flow, liso/slim/model/update.py:53-60 --
         # the kernels read channels in 16-B groups: zero channels (and zero filter slices) up to one group, then the own kernel
-        vec = 8 if x.dtype == torch.bfloat16 else 4
+        vec = 8 if L.is_half(x.dtype) else 4
         pad = (-x.shape[1]) % vec
         xp = torch.nn.functional.pad(x.permute(0, 2, 3, 1), (0, pad)).permute(0, 3, 1, 2)  # one launch: dense NHWC rows of one 16-B group
         if torch.is_grad_enabled() and layer.weight.requires_grad:
