@@ -286,6 +286,12 @@ SIGNATURES = {
     "liso_bike_rollout_fwd_f32": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp]),
     "liso_bike_rollout_bwd_f32": (_i, [_i, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liso_smooth_tracks_jerk_f32": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
+    # include/liso_flow_metrics.h
+    "liso_flow_metrics_state_bytes": (_sz, []),
+    "liso_flow_metrics_result_bytes": (_sz, []),
+    "liso_flow_metrics_reset": (_i, [_vp, _vp]),
+    "liso_flow_metrics_update": (_i, [_vp, _lg, _vp, _lg, _vp, _lg, _i, _vp, _lg, _vp, _lg, _vp, _lg, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "liso_flow_metrics_read": (_i, [_vp, _vp, _vp]),
     # include/liso_augment.h
     "liso_bev_free_mask_workspace_bytes": (_sz, [_i, _i]),
     "liso_bev_free_mask": (_i, [_vp, ctypes.c_long, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -161,6 +161,65 @@ def slim_pair(seed, device, n_points=120000, grid=512, bev_range_m=100.0):
     return sample(clouds[0], with_ground[0], T01), sample(clouds[1], with_ground[1], torch.linalg.inv(T01))
 
 
+def slim_val_batch(seed, device, batch=1, n_points=20000, grid=256, bev_range_m=50.0):
+    """A SLIM validation batch in the reference's sample layout (experiment.py:606-631): `sample_t0` like slim_pair's, batched,
+    plus `gt.flow_ta_tb` [B,N,3] (the true per-point flow, computed as in cluster_sample), `gt.moving_mask` [B,N] (the point lies
+    on an object with non-zero speed) and `gt.point_has_valid_flow_label` [B,N] (false on ~3 % of the points).  The last rows of
+    every t0 sample are padding (`pcl_is_valid` false, zero coordinates and flow; a different count per sample); the network
+    input `pcl_full_no_ground_ta` holds the real points only.  Returns (sample_t0, sample_t1); sample_t1 (fully valid) is the
+    time-reversed view like slim_pair's."""
+    gen = torch.Generator(device="cpu").manual_seed(seed + 277)
+    half = bev_range_m / 2
+    fields0 = {k: [] for k in ("pcl", "valid", "coors", "flow", "moving", "label", "odom", "net", "full")}
+    fields1 = {k: [] for k in ("pcl", "valid", "coors", "odom", "net", "full")}
+
+    def keep_rows(cloud, n):
+        keep = (cloud[:, 2] > -1.45) & (cloud[:, :2].abs().amax(dim=1) < half - 1e-3)
+        rows = torch.nonzero(keep).flatten().cpu()
+        idx = rows[torch.randperm(rows.numel(), generator=gen)[:n]] if rows.numel() >= n else \
+            torch.cat([rows, rows[torch.randint(0, rows.numel(), (n - rows.numel(),), generator=gen)]])
+        return idx.to(cloud.device)
+
+    for b in range(batch):
+        boxes0, speed, ego = make_scene(seed * 100 + b, device, n_boxes=30)
+        boxes1 = move_scene(boxes0, speed, ego)
+        cloud0, obj = render(boxes0, device, seed * 100 + b, n_points=120000)
+        cloud1, _ = render(boxes1, device, seed * 100 + b + 50, n_points=120000)
+        T01 = _se2(float(ego[0]), float(ego[1]), float(ego[2]), device)
+        on = obj >= 0
+        k = obj.clamp(min=0)
+        disp = torch.zeros(cloud0.shape[0], 3, device=device)
+        disp[:, 0] = torch.where(on, speed[k] * torch.cos(boxes0[k, 6]), torch.zeros_like(disp[:, 0]))
+        disp[:, 1] = torch.where(on, speed[k] * torch.sin(boxes0[k, 6]), torch.zeros_like(disp[:, 1]))
+        moved = torch.cat([cloud0[:, :3] + disp, torch.ones_like(cloud0[:, :1])], dim=-1).double()
+        flow = ((torch.linalg.inv(T01) @ moved.T).T[:, :3] - cloud0[:, :3].double()).float()
+        moving = on & (speed[k] > 0)
+        n_pad = n_points // 50 + 13 * b
+        idx = keep_rows(cloud0, n_points - n_pad)
+        pad = lambda t: torch.cat([t, torch.zeros((n_pad,) + tuple(t.shape[1:]), dtype=t.dtype, device=device)])  # noqa: E731
+        pcl = pad(cloud0[idx])
+        label = torch.rand(n_points, generator=gen).to(device) >= 0.03
+        fields0["pcl"].append(pcl), fields0["flow"].append(pad(flow[idx])), fields0["moving"].append(pad(moving[idx]))
+        fields0["label"].append(label & pad(torch.ones(n_points - n_pad, dtype=torch.bool, device=device)))
+        fields0["valid"].append(torch.arange(n_points, device=device) < n_points - n_pad)
+        fields0["coors"].append(voxelize_sample(pcl, (bev_range_m, bev_range_m), (grid, grid))[0])
+        fields0["odom"].append(T01), fields0["net"].append(cloud0[idx].contiguous()), fields0["full"].append(cloud0)
+        c1 = cloud1[keep_rows(cloud1, n_points)].contiguous()
+        fields1["pcl"].append(c1), fields1["valid"].append(torch.ones(n_points, dtype=torch.bool, device=device))
+        fields1["coors"].append(voxelize_sample(c1, (bev_range_m, bev_range_m), (grid, grid))[0])
+        fields1["odom"].append(torch.linalg.inv(T01)), fields1["net"].append(c1), fields1["full"].append(cloud1)
+
+    def sample(f, gt_extra):
+        return {"pcl_full_no_ground_ta": f["net"], "pcl_full_w_ground_ta": torch.stack(f["full"]),
+                "pcl_ta": {"pcl": torch.stack(f["pcl"]), "pcl_is_valid": torch.stack(f["valid"]), "pillar_coors": torch.stack(f["coors"])},
+                "gt": {"odom_ta_tb": torch.stack(f["odom"]), **gt_extra},
+                "src_trgt_time_delta_s": torch.full((batch,), 0.1, device=device)}
+
+    s0 = sample(fields0, {"flow_ta_tb": torch.stack(fields0["flow"]), "moving_mask": torch.stack(fields0["moving"]),
+                          "point_has_valid_flow_label": torch.stack(fields0["label"])})
+    return s0, sample(fields1, {})
+
+
 def cluster_sample(seed, device, batch=1, n_points=120000, grid=512, bev_range_m=100.0, time_delta_s=0.1):
     """A batch for FlowClusterDetector.forward in the reference's sample layout (flow_cluster_detector.py:94-103):
     `pcl_ta` = {pcl [B,N,4] without ground, pcl_is_valid, pillar_coors}, `pcl_full_w_ground_ta` [B,M,4],

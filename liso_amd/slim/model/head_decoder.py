@@ -202,13 +202,15 @@ class HeadDecoder(nn.Module):
     def forward(self, network_output, dynamicness_threshold, *, pc, pointwise_voxel_coordinates, pointwise_valid_mask,
                 filled_pillar_mask, odom, inv_odom, summaries, gt_flow_bev=None, per_point_cluster_idxs_gt=None,
                 ohe_gt_stat_dyn_ground_label_bev_map=None, dynamic_flow_is_non_rigid_flow=False, gather_plan=None,
-                pointwise_only=False, aggregated_flow_only=False):
+                pointwise_only=False, aggregated_flow_only=False, eval_flows_only=False):
         """reference :410-496.  `gather_plan` (extension): a BevGatherPlan of (pointwise_voxel_coordinates // final_scale,
         pointwise_valid_mask) to reuse across the RAFT iterations of one cloud; built here when absent.
         `pointwise_only` (extension, training): return the per-point predictions, `static_aggr_trafo`, `not_enough_points`
         and `dynamicness_threshold` only -- everything the losses read -- without `dense_maps` / `modified_network_output`.
         `aggregated_flow_only` (extension, inference; with `pointwise_only`): the caller reads nothing but `aggregated_flow`; when that
-        does not depend on the static aggregation (model.use_static_aggr_flow_for_aggr_flow False) the Kabsch fit is skipped."""
+        does not depend on the static aggregation (model.use_static_aggr_flow_for_aggr_flow False) the Kabsch fit is skipped.
+        `eval_flows_only` (extension, inference; with `pointwise_only`): the caller reads `static_flow`, `aggregated_flow` and
+        `static_aggr_flow` only (the flows SLIM's validation evaluates): one decode of those three after the Kabsch fit."""
         coors_fs = torch.div(pointwise_voxel_coordinates, self.cfg.model.u_net.final_scale, rounding_mode="trunc")
         if gather_plan is None:
             gather_plan = BevGatherPlan(coors_fs, pointwise_valid_mask, network_output.shape[1:3])
@@ -217,7 +219,8 @@ class HeadDecoder(nn.Module):
             return self._forward_pointwise(network_output, dynamicness_threshold, pc=pc, coors_fs=coors_fs,
                                            pointwise_valid_mask=pointwise_valid_mask, filled_pillar_mask=filled_pillar_mask,
                                            inv_odom=inv_odom, dynamic_flow_is_non_rigid_flow=dynamic_flow_is_non_rigid_flow,
-                                           gather_plan=gather_plan, aggregated_flow_only=aggregated_flow_only)
+                                           gather_plan=gather_plan, aggregated_flow_only=aggregated_flow_only,
+                                           eval_flows_only=eval_flows_only)
         (modified, nod, gt_flow_bev, _, _, _, _, _, static_aggr_trafo, not_enough_points) = self.apply_output_modification(
             network_output, dynamicness_threshold, pc=pc, pointwise_voxel_coordinates_fs=coors_fs,
             pointwise_valid_mask=pointwise_valid_mask, filled_pillar_mask=filled_pillar_mask, inv_odom=inv_odom,
@@ -235,7 +238,7 @@ class HeadDecoder(nn.Module):
 
 
     def _forward_pointwise(self, network_output, dynamicness_threshold, *, pc, coors_fs, pointwise_valid_mask, filled_pillar_mask,
-                           inv_odom, dynamic_flow_is_non_rigid_flow, gather_plan, aggregated_flow_only=False):
+                           inv_odom, dynamic_flow_is_non_rigid_flow, gather_plan, aggregated_flow_only=False, eval_flows_only=False):
         """Gather first, decode second.  Every step of apply_output_modification (:67-298) is pointwise in the BEV cell --
         defaults at unfilled pillars, softmax, thresholds, flow selection -- except (a) the BEV-wide extrema of the
         True / False logit modes and (b) the static aggregation, which itself only reads the maps at the points' pillars and
@@ -265,6 +268,11 @@ class HeadDecoder(nn.Module):
             static_aggr_trafo, not_enough_points = batched_weighted_pc_alignment(
                 x, y, w, pointwise_valid_mask,
                 use_epsilon_on_weights=self.cfg.losses.unsupervised.use_epsilon_for_weighted_pc_alignment)
+            if eval_flows_only and not torch.is_grad_enabled():
+                o = FD.decode_points(raw, static_aggr_trafo, meta, want=("stat_flow", "agg_flow", "saf_flow"))
+                return Munch(static_flow=o["stat_flow"], aggregated_flow=o["agg_flow"], static_aggr_flow=o["saf_flow"],
+                             static_aggr_trafo=static_aggr_trafo, dynamicness_threshold=dynamicness_threshold,
+                             not_enough_points=not_enough_points)
             o = FD.decode_points(raw, static_aggr_trafo, meta)
             fl = o["flags"]
             return Munch(disappearing_logit=o["dis_logit"], disappearing=o["dis"], class_logits=o["logits"], class_probs=o["probs"],

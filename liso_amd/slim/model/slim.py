@@ -73,6 +73,25 @@ class SLIM(nn.Module):
         return pred.aggregated_flow
 
     @torch.no_grad()
+    def infer_eval_flows(self, sample_data_t0, sample_data_t1):
+        """The three per-point flows SLIM's validation evaluates (liso/slim/experiment.py:633-639: `static_flow` = raw,
+        `aggregated_flow` = agg, `static_aggr_flow` = rig of preds_fw[-1]), each [B,N,3].  Like infer_point_flow_t0_t1: forward
+        direction and last RAFT iteration only, then the static-aggregation Kabsch fit and ONE pointwise decode of the three
+        flows (the training forward runs both directions and decodes 12 outputs per iteration)."""
+        dev = next(self.raft_network.parameters()).device
+        net_out, aux = self.raft_network.infer_forward_direction(get_network_input_pcls(self.cfg, sample_data_t0, "ta", to_device=dev),
+                                                                 get_network_input_pcls(self.cfg, sample_data_t1, "ta", to_device=dev))
+        pa = sample_data_t0["pcl_ta"]
+        pred = self.head_decoder_fw(
+            net_out, self.moving_dynamicness_threshold.value(), pc=pa["pcl"].to(dev),
+            pointwise_voxel_coordinates=pa["pillar_coors"].to(dev), pointwise_valid_mask=pa["pcl_is_valid"].to(dev),
+            filled_pillar_mask=torch.squeeze(aux["t0"]["bev_net_input_dbg"] > 0.5, dim=1),
+            odom=sample_data_t0["gt"]["odom_ta_tb"].to(dev), inv_odom=sample_data_t1["gt"]["odom_ta_tb"].to(dev), summaries=None,
+            dynamic_flow_is_non_rigid_flow=self.slim_cfg.model.dynamic_flow_is_non_rigid_flow, pointwise_only=True,
+            eval_flows_only=True)
+        return type(pred)(static_flow=pred.static_flow, aggregated_flow=pred.aggregated_flow, static_aggr_flow=pred.static_aggr_flow)
+
+    @torch.no_grad()
     def infer_export_predictions(self, sample_data_t0, sample_data_t1):
         """What the flow export consumes (liso/slim/experiment.py:363-471: `bev_raw_flow_t0_t1`, `bev_raw_flow_t1_t0`,
         `bev_dynamicness_*` of the LAST RAFT iteration): both flow directions in one batched network pass, one dense decode per

@@ -613,6 +613,19 @@ class SlimTrainer:
         self._reduce_and_update()
         return total.detach()
 
+    def eval_model(self, val_batches, max_iterations=None):
+        """liso/slim/experiment.py:560-578 without its TensorBoard writers: the validation pass over `val_batches` ((sample_t0,
+        sample_t1) pairs with flow labels) in eval mode, then the previous mode again.  -> (eval_metrics, flow_metrics) of
+        liso_amd.slim.validation.run_eval_on_this_dataset.  No parameter, buffer or threshold state changes."""
+        from liso_amd.slim.validation import run_eval_on_this_dataset
+
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            return run_eval_on_this_dataset(self.net, val_batches, max_iterations=max_iterations)
+        finally:
+            self.net.train(was_training)
+
     def _reduce_and_update(self):
         if self.use_graph and self.world > 1:
             dist.all_reduce(self._flat_grad)
