@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.fp16_checks import assert_fp16_rounded, require_fp16
+
 pytestmark = pytest.mark.gpu
 
 # (B, Ci, Co, H, W, k, stride, pad, transposed)
@@ -46,6 +48,9 @@ def _mk(geom, dtype, seed=0):
     if dtype == torch.bfloat16:  # the kernel sees bf16 activations and bf16-rounded weights
         x = x.bfloat16().float()
         w = w.bfloat16().float()
+    elif dtype == torch.float16:  # ... fp16 activations and fp16-rounded weights
+        x = x.half().float()
+        w = w.half().float()
     return x, w, b
 
 
@@ -56,6 +61,7 @@ def _rel(a, b):
 
 ARITH = [pytest.param((torch.bfloat16, "x3"), id="bf16"), pytest.param((torch.float32, "x3"), id="f32x3"),
          pytest.param((torch.float32, "exact"), id="f32exact")]
+F16 = pytest.param((torch.float16, "x3"), id="f16")
 
 
 @pytest.fixture(autouse=True)
@@ -109,13 +115,15 @@ def test_forward_dgrad_wgrad(geom, arith, monkeypatch):
     assert _rel(db, gb) <= 2 * tol, _rel(db, gb)
 
 
-@pytest.mark.parametrize("arith", ARITH)
+@pytest.mark.parametrize("arith", ARITH + [F16])
 def test_prologue_epilogue_statistics_and_channel_slices(arith):
     """x' = relu(x * scale + shift) fused into the staging (padding stays exactly zero), ReLU + bias epilogue, the partial
     sums -> BatchNorm statistics (vs torch on the stored tensor), input given as a channel slice of a wider tensor"""
+    dtype, fmode = arith
+    if dtype == torch.float16:
+        require_fp16()
     from liso_amd.utils import mfma_conv as MC
 
-    dtype, fmode = arith
     MC.set_fp32_mode(fmode)
     exact = dtype == torch.float32 and fmode == "exact"
     geom = (2, 64, 128, 40, 40, 3, 1, 1, False)
@@ -131,6 +139,8 @@ def test_prologue_epilogue_statistics_and_channel_slices(arith):
     xin = torch.relu(x.double() * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1))
     if dtype == torch.bfloat16:
         xin = torch.relu((x * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))).bfloat16().double()  # rounded like the staging does
+    elif dtype == torch.float16:  # the staging's fmaf in fp32 (exact in fp64, then one rounding), then the fp16 store
+        xin = torch.relu(x.double() * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)).float().half().double()
     ref = torch.relu(F.conv2d(xin, w.double(), b.double(), stride=s, padding=p))
     bn = torch.nn.BatchNorm2d(Co).cuda().train()
     with torch.no_grad():
@@ -138,8 +148,12 @@ def test_prologue_epilogue_statistics_and_channel_slices(arith):
     shift_stat = bn.running_mean.clone()
     y, part = MC.conv_forward(xs, w.cuda(), b.cuda(), spec, scale.cuda(), shift.cuda(), in_relu=True, out_relu=True,
                               want_stats=True, stats_shift=shift_stat)
-    tol = 8e-3 if dtype == torch.bfloat16 else 3e-6 if exact else 6e-5
+    # fp16: the output's rounding (2^-11) plus fp32 accumulation; each element within half an fp16 ulp of the exact value, plus
+    # the fp32 summation error (relative to the largest output)
+    tol = 8e-3 if dtype == torch.bfloat16 else 6e-4 if dtype == torch.float16 else 3e-6 if exact else 6e-5
     assert _rel(y, ref) <= tol, _rel(y, ref)
+    if dtype == torch.float16:
+        assert_fp16_rounded(y, ref, 1e-5)
     fold = MC.finalize_bn(part, B * y.shape[2] * y.shape[3], bn, shift_stat)
     yf = y.float()
     mean, var = yf.mean(dim=(0, 2, 3)), yf.var(dim=(0, 2, 3), unbiased=False)
@@ -154,11 +168,13 @@ def test_prologue_epilogue_statistics_and_channel_slices(arith):
     dy = torch.randn(ref.shape, generator=g)
     if dtype == torch.bfloat16:
         dy = dy.bfloat16().float()
+    elif dtype == torch.float16:
+        dy = dy.half().float()
     w64 = w.double().requires_grad_(True)
     gw, = torch.autograd.grad(F.conv2d(xin, w64, None, stride=s, padding=p), [w64], dy.double())
     dw, _ = MC.conv_wgrad(xs, dy.to(dtype).cuda().contiguous(memory_format=torch.channels_last), tuple(w.shape), spec,
                           scale.cuda(), shift.cuda(), in_relu=True)
-    assert _rel(dw, gw) <= (2e-4 if dtype == torch.bfloat16 else 6e-6 if exact else 1e-4), _rel(dw, gw)
+    assert _rel(dw, gw) <= (2e-4 if dtype == torch.bfloat16 else 5e-5 if dtype == torch.float16 else 6e-6 if exact else 1e-4), _rel(dw, gw)
 
 
 def _stat(a, b):
@@ -220,13 +236,15 @@ def test_fused_conv_autograd_chain_matches_torch_modules(beta_lo, beta_hi, fmode
         assert int(bns[i].num_batches_tracked) == 1
 
 
-@pytest.mark.parametrize("arith", ARITH[:2])
+@pytest.mark.parametrize("arith", ARITH[:2] + [F16])
 def test_sparse_input_tile_skipping_is_bit_identical(arith):
     """liso_conv_forward_sparse: with the occupancy map of a sparse canvas (3 % of the cells occupied, clustered) the blocks whose
     input window holds no occupied cell skip their work; output and BatchNorm partial sums must equal the dense call bit for bit"""
+    dtype, fmode = arith
+    if dtype == torch.float16:
+        require_fp16()
     from liso_amd.utils import mfma_conv as MC
 
-    dtype, fmode = arith
     MC.set_fp32_mode(fmode)
     g = torch.Generator().manual_seed(3)
     B, C, H, W = 2, 64, 256, 256
@@ -433,11 +451,13 @@ def test_sparse_first_rpn_layer_equals_the_dense_kernels(B, H, W, density, dtype
     assert _rel(ws, wd) <= 1e-2 if dtype == torch.bfloat16 else _rel(ws, wd) <= 1e-4
 
 
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32, torch.float16])
 def test_convolutions_writing_channel_ranges_of_one_buffer_and_slice_cat(dtype):
     """fused_conv(..., out=(buffer, first_channel)): three convolutions (3x3, 1x1, transposed 2x2 -- the deblock geometries of
     rpn.py:52-63) write one concatenated map without a concatenation pass; `slice_cat` connects it to autograd: same values as
     torch.cat of the stand-alone outputs, same input / weight gradients"""
+    if dtype == torch.float16:
+        require_fp16()
     from liso_amd.utils import mfma_conv as MC
 
     torch.manual_seed(9)

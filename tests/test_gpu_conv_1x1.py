@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.fp16_checks import assert_fp16_rounded, require_fp16
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -178,10 +180,43 @@ def test_small_channel_windows(shape):
     assert torch.equal(y, y4)
 
 
+# relative tolerances of the 16-bit outputs: bf16 rounds to 2^-9, fp16 to 2^-11 (+ fp32 accumulation)
+ARITH16 = [pytest.param(torch.float32, id="f32x3"), pytest.param(torch.bfloat16, id="bf16"), pytest.param(torch.float16, id="f16")]
+TOL = {torch.float32: 2e-5, torch.bfloat16: 2e-2, torch.float16: 1e-3}
+
+
+def _round16(dtype, *ts):
+    """operands as the kernel sees them: rounded to the tensor's 16-bit type"""
+    if dtype == torch.bfloat16:
+        return tuple(t.bfloat16().float() for t in ts)
+    if dtype == torch.float16:
+        return tuple(t.half().float() for t in ts)
+    return ts
+
+
+def _staged(x, sc, sh, dtype):
+    """relu(x * sc + sh) as the staging stores it: fmaf in fp32, then rounded to the 16-bit element type"""
+    xin = F.relu(x.double() * sc.double()[None, :, None, None] + sh.double()[None, :, None, None])
+    if dtype == torch.bfloat16:
+        xin = xin.float().bfloat16().double()
+    elif dtype == torch.float16:
+        xin = xin.float().half().double()
+    return xin
+
+
+def _check16(dtype, y, ref):
+    assert _rel(y.float(), ref) <= TOL[dtype], _rel(y.float(), ref)
+    if dtype == torch.float16:
+        assert y.dtype == torch.float16
+        assert_fp16_rounded(y, ref, 1e-5)
+
+
 # ---- the same kernel on bf16 tensors and on tap classes (transposed convolutions with kernel = stride: rpn.py:70-104 deblocks) --------------
-@pytest.mark.parametrize("dtype", [pytest.param(torch.float32, id="f32x3"), pytest.param(torch.bfloat16, id="bf16")])
+@pytest.mark.parametrize("dtype", ARITH16)
 @pytest.mark.parametrize("shape", [(2, 128, 128, 32, 32, 2), (2, 256, 128, 64, 64, 2), (1, 64, 96, 9, 37, 2), (3, 40, 72, 20, 33, 1), (2, 128, 128, 128, 128, 1)])
 def test_transposed_kernel_equals_stride_and_bf16_1x1(shape, dtype):
+    if dtype == torch.float16:
+        require_fp16()
     from liso_amd import _lib as L
     from liso_amd.utils import mfma_conv as MC
 
@@ -191,8 +226,7 @@ def test_transposed_kernel_equals_stride_and_bf16_1x1(shape, dtype):
     transposed = k > 1
     w = (torch.randn(Ci, Co, k, k, generator=g) if transposed else torch.randn(Co, Ci, 1, 1, generator=g)) / Ci ** 0.5
     b = torch.randn(Co, generator=g) * 0.3
-    if dtype == torch.bfloat16:
-        x, w = x.bfloat16().float(), w.bfloat16().float()
+    x, w = _round16(dtype, x, w)
     spec = MC.ConvSpec(k, k, k, 0, transposed)
     xd = x.to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
     mode = MC._mode(dtype)
@@ -201,17 +235,15 @@ def test_transposed_kernel_equals_stride_and_bf16_1x1(shape, dtype):
     build = MC.scatter_desc if transposed else MC.gather_desc
     d = build(spec, B, H, W, Ci, xps, ho, wo, Co, Co, 0, mode, dtype == torch.float32, False, False)
     assert L.lib().liso_conv_kernel_kind(ctypes.byref(d)) == 2, "descriptor does not take conv_1x1_kernel"
-    tol = 2e-2 if dtype == torch.bfloat16 else 2e-5
     ref_fn = (lambda xx, bb: F.conv_transpose2d(xx, w.double(), bb, stride=k)) if transposed else (lambda xx, bb: F.conv2d(xx, w.double(), bb))
     y, _ = MC.conv_forward(xd, w.to(DEV), b.to(DEV), spec, out_relu=True)
     ref = F.relu(ref_fn(x.double(), b.double()))
-    assert y.shape == ref.shape and _rel(y.float(), ref) <= tol
+    assert y.shape == ref.shape
+    _check16(dtype, y, ref)
     sc, sh = torch.rand(Ci, generator=g) + 0.5, torch.randn(Ci, generator=g) * 0.2
     y2, part = MC.conv_forward(xd, w.to(DEV), None, spec, sc.to(DEV), sh.to(DEV), in_relu=True, want_stats=True)
-    xin = F.relu(x.double() * sc.double()[None, :, None, None] + sh.double()[None, :, None, None])
-    if dtype == torch.bfloat16:
-        xin = xin.float().bfloat16().double()
-    assert _rel(y2.float(), ref_fn(xin, None)) <= tol
+    xin = _staged(x, sc, sh, dtype)
+    _check16(dtype, y2, ref_fn(xin, None))
     stored = y2.float().double()
     s1, s2 = part[:, 0, :Co].double().sum(0).cpu(), part[:, 1, :Co].double().sum(0).cpu()
     assert torch.allclose(s1, stored.sum((0, 2, 3)).cpu(), rtol=1e-4, atol=1e-3 * float(stored.abs().max()))
@@ -219,10 +251,12 @@ def test_transposed_kernel_equals_stride_and_bf16_1x1(shape, dtype):
     assert torch.isfinite(part).all()
 
 
-@pytest.mark.parametrize("dtype", [pytest.param(torch.float32, id="f32x3"), pytest.param(torch.bfloat16, id="bf16")])
+@pytest.mark.parametrize("dtype", ARITH16)
 @pytest.mark.parametrize("shape", [(2, 64, 128, 256, 256, 2), (1, 32, 40, 18, 70, 2), (2, 16, 32, 27, 27, 3)])
 def test_kernel_equals_stride_convolutions(shape, dtype):
     """k x k / stride k (the k = 2 deblock): non-overlapping windows -- one 1x1 problem on k * k * Ci channels, no pixel read twice"""
+    if dtype == torch.float16:
+        require_fp16()
     from liso_amd import _lib as L
     from liso_amd.utils import mfma_conv as MC
 
@@ -231,8 +265,7 @@ def test_kernel_equals_stride_convolutions(shape, dtype):
     x = torch.randn(B, Ci, H, W, generator=g)
     w = torch.randn(Co, Ci, k, k, generator=g) / (Ci * k * k) ** 0.5
     b = torch.randn(Co, generator=g) * 0.3
-    if dtype == torch.bfloat16:
-        x, w = x.bfloat16().float(), w.bfloat16().float()
+    x, w = _round16(dtype, x, w)
     spec = MC.ConvSpec(k, k, k, 0, False)
     xd = x.to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
     mode = MC._mode(dtype)
@@ -240,25 +273,25 @@ def test_kernel_equals_stride_convolutions(shape, dtype):
     ho, wo = spec.out_hw(H, W)
     d = MC.gather_desc(spec, B, H, W, Ci, xps, ho, wo, Co, Co, 0, mode, dtype == torch.float32, False, False)
     assert L.lib().liso_conv_kernel_kind(ctypes.byref(d)) == 2, "descriptor does not take conv_1x1_kernel"
-    tol = 2e-2 if dtype == torch.bfloat16 else 2e-5
     y, _ = MC.conv_forward(xd, w.to(DEV), b.to(DEV), spec, out_relu=True)
     ref = F.relu(F.conv2d(x.double(), w.double(), b.double(), stride=k))
-    assert y.shape == ref.shape and _rel(y.float(), ref) <= tol
+    assert y.shape == ref.shape
+    _check16(dtype, y, ref)
     sc, sh = torch.rand(Ci, generator=g) + 0.5, torch.randn(Ci, generator=g) * 0.2
     y2, part = MC.conv_forward(xd, w.to(DEV), None, spec, sc.to(DEV), sh.to(DEV), in_relu=True, want_stats=True)
-    xin = F.relu(x.double() * sc.double()[None, :, None, None] + sh.double()[None, :, None, None])
-    if dtype == torch.bfloat16:
-        xin = xin.float().bfloat16().double()
-    assert _rel(y2.float(), F.conv2d(xin, w.double(), None, stride=k)) <= tol
+    xin = _staged(x, sc, sh, dtype)
+    _check16(dtype, y2, F.conv2d(xin, w.double(), None, stride=k))
     stored = y2.float().double()
     assert torch.allclose(part[:, 0, :Co].double().sum(0).cpu(), stored.sum((0, 2, 3)).cpu(), rtol=1e-4, atol=1e-3 * float(stored.abs().max()))
 
 
-@pytest.mark.parametrize("dtype", [pytest.param(torch.float32, id="f32x3"), pytest.param(torch.bfloat16, id="bf16")])
+@pytest.mark.parametrize("dtype", ARITH16)
 @pytest.mark.parametrize("shape", [(8, 32, 64, 256, 256), (4, 64, 96, 128, 128), (2, 64, 128, 37, 45), (1, 16, 24, 9, 70)])
 def test_3x3_stride_2_layers_on_small_pixels(shape, dtype):
     """3x3 / stride 2 / padding 1 on pixels of <= 256 bytes (the encoders' downsampling layers, extractor.py:211-297; the detector's block
     entries, rpn.py:113-131): the direct kernel re-reads each pixel 2.25 times through L1 instead of staging tiles"""
+    if dtype == torch.float16:
+        require_fp16()
     from liso_amd import _lib as L
     from liso_amd.utils import mfma_conv as MC
 
@@ -267,8 +300,7 @@ def test_3x3_stride_2_layers_on_small_pixels(shape, dtype):
     x = torch.randn(B, Ci, H, W, generator=g)
     w = torch.randn(Co, Ci, 3, 3, generator=g) / (Ci * 9) ** 0.5
     b = torch.randn(Co, generator=g) * 0.3
-    if dtype == torch.bfloat16:
-        x, w = x.bfloat16().float(), w.bfloat16().float()
+    x, w = _round16(dtype, x, w)
     spec = MC.ConvSpec(3, 3, 2, 1, False)
     xd = x.to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
     mode = MC._mode(dtype)
@@ -276,16 +308,14 @@ def test_3x3_stride_2_layers_on_small_pixels(shape, dtype):
     ho, wo = spec.out_hw(H, W)
     d = MC.gather_desc(spec, B, H, W, Ci, xps, ho, wo, Co, Co, 0, mode, dtype == torch.float32, False, False)
     assert L.lib().liso_conv_kernel_kind(ctypes.byref(d)) == 2, "descriptor does not take conv_1x1_kernel"
-    tol = 2e-2 if dtype == torch.bfloat16 else 2e-5
     y, _ = MC.conv_forward(xd, w.to(DEV), b.to(DEV), spec, out_relu=True)
     ref = F.relu(F.conv2d(x.double(), w.double(), b.double(), stride=2, padding=1))
-    assert y.shape == ref.shape and _rel(y.float(), ref) <= tol
+    assert y.shape == ref.shape
+    _check16(dtype, y, ref)
     sc, sh = torch.rand(Ci, generator=g) + 0.5, torch.randn(Ci, generator=g) * 0.2
     y2, part = MC.conv_forward(xd, w.to(DEV), None, spec, sc.to(DEV), sh.to(DEV), in_relu=True, want_stats=True)
-    xin = F.relu(x.double() * sc.double()[None, :, None, None] + sh.double()[None, :, None, None])
-    if dtype == torch.bfloat16:
-        xin = xin.float().bfloat16().double()
-    assert _rel(y2.float(), F.conv2d(xin, w.double(), None, stride=2, padding=1)) <= tol
+    xin = _staged(x, sc, sh, dtype)
+    _check16(dtype, y2, F.conv2d(xin, w.double(), None, stride=2, padding=1))
     stored = y2.float().double()
     assert torch.allclose(part[:, 0, :Co].double().sum(0).cpu(), stored.sum((0, 2, 3)).cpu(), rtol=1e-4, atol=1e-3 * float(stored.abs().max()))
     assert torch.allclose(part[:, 1, :Co].double().sum(0).cpu(), stored.square().sum((0, 2, 3)).cpu(), rtol=1e-4, atol=1e-6)

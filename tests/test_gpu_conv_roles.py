@@ -12,6 +12,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.fp16_checks import assert_fp16_rounded, require_fp16
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -26,7 +28,9 @@ SHAPES = [
     (7, 32, 96, 31, 33),      # odd tile counts
     (1, 304, 96, 16, 16),     # deep reduction, few tiles (gridDim < 8)
 ]
-ARITH = [pytest.param(torch.float32, id="f32x3"), pytest.param(torch.bfloat16, id="bf16")]
+ARITH = [pytest.param(torch.float32, id="f32x3"), pytest.param(torch.bfloat16, id="bf16"), pytest.param(torch.float16, id="f16")]
+# relative tolerances of the 16-bit outputs: bf16 rounds to 2^-9, fp16 to 2^-11 (+ fp32 accumulation)
+TOL16 = {torch.bfloat16: 2e-2, torch.float16: 1e-3}
 
 
 def _mk(shape, dtype, seed=0):
@@ -37,7 +41,20 @@ def _mk(shape, dtype, seed=0):
     b = torch.randn(Co, generator=g) * 0.3
     if dtype == torch.bfloat16:
         x, w = x.bfloat16().float(), w.bfloat16().float()
+    elif dtype == torch.float16:
+        x, w = x.half().float(), w.half().float()
     return x, w, b
+
+
+def _staged(x, sc, sh, dtype):
+    """the input the kernel multiplies: relu(x * sc + sh), for 16-bit tensors rounded as the staging stores it (fmaf in fp32, then the
+    element type)"""
+    xin = F.relu(x.double() * sc.double()[None, :, None, None] + sh.double()[None, :, None, None])
+    if dtype == torch.bfloat16:
+        xin = xin.float().bfloat16().double()
+    elif dtype == torch.float16:
+        xin = xin.float().half().double()
+    return xin
 
 
 def _kind(x, w, spec):
@@ -59,30 +76,34 @@ def _rel(a, b):
 @pytest.mark.parametrize("dtype", ARITH)
 @pytest.mark.parametrize("shape", SHAPES)
 def test_forward_prologue_statistics_and_slices(shape, dtype):
+    if dtype == torch.float16:
+        require_fp16()
     from liso_amd.utils import mfma_conv as MC
 
     B, Ci, Co, H, W = shape
-    if dtype == torch.bfloat16 and (Ci % 32 or Ci < 64 or Co % 2):
-        pytest.skip("bf16 layers take this kernel only with whole 32-channel slabs, at least two of them")
+    if dtype != torch.float32 and (Ci % 32 or Ci < 64 or Co % 2):
+        pytest.skip("16-bit layers take this kernel only with whole 32-channel slabs, at least two of them")
     x, w, b = _mk(shape, dtype)
     spec = MC.ConvSpec(3, 3, 1, 1, False)
     xd = x.to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
     wd, bd = w.to(DEV), b.to(DEV)
     assert _kind(xd, wd, spec) == 1, "descriptor does not take conv_roles_kernel"
-    tol = 2e-2 if dtype == torch.bfloat16 else 2e-5  # bf16: the OUTPUT is rounded to bf16 (2^-9), fp32: 2^-16 per product
+    tol = TOL16.get(dtype, 2e-5)  # 16-bit: the OUTPUT is rounded (bf16 2^-9, fp16 2^-11), fp32: 2^-16 per product
     # plain, with bias + ReLU
     y, _ = MC.conv_forward(xd, wd, bd, spec, out_relu=True)
     ref = F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=1))
     assert _rel(y.float(), ref) <= tol
+    if dtype == torch.float16:
+        assert_fp16_rounded(y, ref, 1e-5)
     # prologue (per-channel affine + ReLU of the producer) and the statistics epilogue
     g = torch.Generator().manual_seed(1)
     sc, sh = torch.rand(Ci, generator=g) + 0.5, torch.randn(Ci, generator=g) * 0.2
     y2, part = MC.conv_forward(xd, wd, None, spec, sc.to(DEV), sh.to(DEV), in_relu=True, want_stats=True)
-    xin = F.relu(x.double() * sc.double()[None, :, None, None] + sh.double()[None, :, None, None])
-    if dtype == torch.bfloat16:
-        xin = xin.float().bfloat16().double()
+    xin = _staged(x, sc, sh, dtype)
     ref2 = F.conv2d(xin, w.double(), None, padding=1)
     assert _rel(y2.float(), ref2) <= tol
+    if dtype == torch.float16:
+        assert_fp16_rounded(y2, ref2, 1e-5)
     stored = y2.float().double()  # the sums are taken over the STORED (rounded) values
     s1 = part[:, 0, :Co].double().sum(0).cpu()
     s2 = part[:, 1, :Co].double().sum(0).cpu()
@@ -93,13 +114,18 @@ def test_forward_prologue_statistics_and_slices(shape, dtype):
     if Co % 8 == 0:
         buf = torch.full((B, H, W, Co + 24), 7.0, dtype=dtype, device=DEV)
         y3, _ = MC.conv_forward(xd, wd, bd, spec, out=(buf, 8))
-        assert _rel(y3.float(), F.conv2d(x.double(), w.double(), b.double(), padding=1)) <= tol
+        ref3 = F.conv2d(x.double(), w.double(), b.double(), padding=1)
+        assert _rel(y3.float(), ref3) <= tol
+        if dtype == torch.float16:
+            assert_fp16_rounded(y3, ref3, 1e-5)
         assert bool((buf[..., :8] == 7.0).all()) and bool((buf[..., 8 + Co:] == 7.0).all())
 
 
 @pytest.mark.parametrize("dtype", ARITH)
 @pytest.mark.parametrize("shape", [(2, 64, 96, 40, 72), (1, 32, 64, 9, 33), (3, 128, 32, 64, 64)])
 def test_data_gradient(shape, dtype):
+    if dtype == torch.float16:
+        require_fp16()
     from liso_amd.utils import mfma_conv as MC
 
     B, Ci, Co, H, W = shape
@@ -108,34 +134,50 @@ def test_data_gradient(shape, dtype):
     dy = torch.randn(B, Co, H, W, generator=g)
     if dtype == torch.bfloat16:
         dy = dy.bfloat16().float()
+    elif dtype == torch.float16:
+        dy = dy.half().float()
     spec = MC.ConvSpec(3, 3, 1, 1, False)
     dyd = dy.to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
     gx = MC.conv_dgrad(dyd, w.to(DEV), spec, (B, Ci, H, W))
     x64 = x.double().requires_grad_(True)
     (ref,) = torch.autograd.grad(F.conv2d(x64, w.double(), padding=1), [x64], dy.double())
-    assert _rel(gx.float(), ref) <= (2e-2 if dtype == torch.bfloat16 else 2e-5)
+    assert _rel(gx.float(), ref) <= TOL16.get(dtype, 2e-5)
+    if dtype == torch.float16:
+        assert gx.dtype == torch.float16
+        assert_fp16_rounded(gx, ref, 1e-5)
 
 
 def test_forced_tile_shapes_agree_bitwise_on_statistics_and_closely_on_values(tmp_path):
     """LISO_ROLES_MI / LISO_ROLES_NJ force the tile shape (a plan-time switch: one child process per shape).  Values must agree to
     fp32 rounding of the summation order (identical here: the order over (slab, tap) does not depend on the tile), and the statistics
     rows -- fixed 4 x 32-pixel sets, fixed tree -- bit for bit."""
+    _forced_tile_shapes(tmp_path, "float32", 48, ((1, 1), (1, 2), (2, 1), (2, 2), (1, 3)))
+
+
+def test_forced_tile_shapes_agree_bitwise_with_fp16_tensors(tmp_path):
+    """the same with fp16 tensors (64 input channels: two whole 32-channel slabs) and an fp16 output, over the tile shapes the 16-bit
+    plan offers (no 1 x 3: that one is F32X3's)"""
+    require_fp16()
+    _forced_tile_shapes(tmp_path, "float16", 64, ((1, 1), (1, 2), (2, 1), (2, 2)))
+
+
+def _forced_tile_shapes(tmp_path, dtype, ci, shapes):
     code = r"""
 import sys, torch
 sys.path.insert(0, %r)
 from liso_amd.utils import mfma_conv as MC
 torch.manual_seed(0)
-x = torch.randn(3, 48, 40, 72, device="cuda").contiguous(memory_format=torch.channels_last)
-w = torch.randn(64, 48, 3, 3, device="cuda") * 0.05
+x = torch.randn(3, %d, 40, 72, device="cuda").to(torch.%s).contiguous(memory_format=torch.channels_last)
+w = torch.randn(64, %d, 3, 3, device="cuda") * 0.05
 y, part = MC.conv_forward(x, w, None, MC.ConvSpec(3, 3, 1, 1, False), want_stats=True)
 torch.save({"y": y.cpu(), "s": part[:, :, :64].cpu(), "rows": part.shape[0]}, sys.argv[1])
 """
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
-    for mi, nj in ((1, 1), (1, 2), (2, 1), (2, 2), (1, 3)):
+    for mi, nj in shapes:
         path = str(tmp_path / f"roles_forced_{mi}{nj}.pt")
         env = dict(os.environ, LISO_ROLES_MI=str(mi), LISO_ROLES_NJ=str(nj))
-        r = subprocess.run([sys.executable, "-c", code % root, path], env=env, capture_output=True, text=True, timeout=300)
+        r = subprocess.run([sys.executable, "-c", code % (root, ci, dtype, ci), path], env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(torch.load(path))
     for k, o in enumerate(outs[1:]):
