@@ -292,6 +292,11 @@ SIGNATURES = {
     "liso_flow_metrics_reset": (_i, [_vp, _vp]),
     "liso_flow_metrics_update": (_i, [_vp, _lg, _vp, _lg, _vp, _lg, _i, _vp, _lg, _vp, _lg, _vp, _lg, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "liso_flow_metrics_read": (_i, [_vp, _vp, _vp]),
+    # include/liso_det_nms.h
+    "liso_det_nms_workspace_bytes": (_sz, [_i, _i]),
+    "liso_det_nms_order": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
+    "liso_det_nms_select": (_i, [_i, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
+    "liso_det_nms_gather": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     # include/liso_augment.h
     "liso_bev_free_mask_workspace_bytes": (_sz, [_i, _i]),
     "liso_bev_free_mask": (_i, [_vp, ctypes.c_long, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -391,6 +396,11 @@ class MineFilterCfg(ctypes.Structure):
     """mirror of liso_mine_filter_cfg (include/liso_box_mining.h)"""
     _fields_ = [("batch", _i), ("k", _i), ("min_points", _i), ("aspect_ratio_max", ctypes.c_double), ("max_box_len_m", ctypes.c_double),
                 ("min_box_area_m2", ctypes.c_double), ("min_box_volume_m3", ctypes.c_double), ("park_invalid", _i)]
+
+
+class DetGatherField(ctypes.Structure):
+    """mirror of liso_det_gather_field (include/liso_det_nms.h)"""
+    _fields_ = [("src", _vp), ("dst", _vp), ("row_elems", _i), ("elem_bytes", _i), ("pad_bits", ctypes.c_uint64)]
 
 
 class TargetsCfg(ctypes.Structure):

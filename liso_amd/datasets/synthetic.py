@@ -254,3 +254,42 @@ def cluster_sample(seed, device, batch=1, n_points=120000, grid=512, bev_range_m
               "gt": {"flow_ta_tb": torch.stack(flows), "odom_ta_tb": torch.stack(odoms)},
               "src_trgt_time_delta_s": torch.full((batch,), time_delta_s, device=device)}
     return sample, scenes
+
+
+def detector_map_trained_like(seed, batch, side, device, n_objects=30, bev_range_m=100.0):
+    """Dense detector output [B, side*side] shaped like a trained CenterPoint head's decoded maps: one box per BEV cell at the
+    cell centre with background logits ~ N(-6, 1), plus `n_objects` objects, each a score peak (logit up to ~4) over the cells
+    within 2.5 m of its centre whose boxes jitter around the object's box (0.15 m, 5 % size, 0.05 rad).  Returns a Shape
+    (pos [B,M,3], dims [B,M,3], rot [B,M,1], probs = logits [B,M,1], all fp32, every slot valid)."""
+    from liso_amd.kabsch.shape_utils import Shape
+
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    cell = bev_range_m / side
+    c = (torch.arange(side, dtype=torch.float32) + 0.5) * cell - bev_range_m / 2
+    cx, cy = torch.meshgrid(c, c, indexing="ij")
+    cx, cy = cx.reshape(-1), cy.reshape(-1)
+    M = side * side
+    P, D, R, L = [], [], [], []
+    for _ in range(batch):
+        pos = torch.stack([cx, cy, torch.full((M,), -1.0)], dim=-1) + torch.randn(M, 3, generator=g) * torch.tensor([0.1, 0.1, 0.05])
+        dims = torch.stack([torch.rand(M, generator=g) * 1.5 + 1.0, torch.rand(M, generator=g) * 0.8 + 0.8,
+                            torch.rand(M, generator=g) * 0.4 + 1.3], dim=-1)
+        rot = (torch.rand(M, 1, generator=g) * 2 - 1) * math.pi
+        logit = torch.randn(M, 1, generator=g) - 6.0
+        obj = (torch.rand(n_objects, 2, generator=g) * 2 - 1) * (bev_range_m / 2 - 5.0)
+        odims = torch.stack([torch.rand(n_objects, generator=g) * 1.5 + 3.5, torch.rand(n_objects, generator=g) * 0.5 + 1.6,
+                             torch.rand(n_objects, generator=g) * 0.4 + 1.4], dim=-1)
+        oyaw = (torch.rand(n_objects, generator=g) * 2 - 1) * math.pi
+        for k in range(n_objects):
+            d2 = (cx - obj[k, 0]) ** 2 + (cy - obj[k, 1]) ** 2
+            near = d2 < 2.5 ** 2
+            m = int(near.sum())
+            if m == 0:
+                continue
+            pos[near, :2] = obj[k] + torch.randn(m, 2, generator=g) * 0.15
+            dims[near] = odims[k] * (1 + torch.randn(m, 3, generator=g) * 0.05)
+            rot[near, 0] = oyaw[k] + torch.randn(m, generator=g) * 0.05
+            logit[near, 0] = torch.maximum(logit[near, 0], 4.0 - 1.2 * d2[near] + torch.randn(m, generator=g) * 0.3)
+        P.append(pos), D.append(dims), R.append(rot), L.append(logit)
+    st = lambda xs: torch.stack(xs).to(device)  # noqa: E731
+    return Shape(pos=st(P), dims=st(D), rot=st(R), probs=st(L))

@@ -50,6 +50,29 @@ class BoxLearner(torch.nn.Module):
         flat = maybe_flatten_anchors_except_for({k: v.clone() for k, v in decoded.items()}, ())
         return Shape(**flat), decoded, activated, aux_outputs
 
+    @torch.no_grad()
+    def predict_boxes(self, img_t0, pcls_t0, *, overlap_threshold=None, pre_nms_max_boxes=None, post_nms_max_boxes=500,
+                      logit_threshold=-1e32, sigmoid_probs=False, canvas=None):
+        """Decoding forward (`train=False`) + batched rotated NMS on the device (liso_amd.utils.nms_iou.iou_based_nms_batched):
+        (Shape [B,P], keep_idx int64 [B,P], counts int32 [B]), P = post_nms_max_boxes, no host sync.  The module's mode is the
+        caller's.
+        The defaults are run_val's post-processing (liso/eval/eval_ours.py:361-386): slots with a logit below `logit_threshold`
+        take no part, the boxes are ranked by sigmoid(probs) when `activations.probs == "none"` (by the probs otherwise), no
+        pre-NMS cut, 500 boxes kept, raw probs returned.  `pre_nms_max_boxes=1000, post_nms_max_boxes=100, sigmoid_probs=True`
+        is the tracker's (liso/tracker/tracking.py:710-740): the kept boxes carry the sigmoid probs (the tracker applies no
+        logit threshold; the default -1e32 drops only slots whose logit is -inf or below -1e32).
+        `overlap_threshold=None` reads cfg.nms_iou_threshold.  Ties in the ranking keep ascending slot index."""
+        from liso_amd.utils.nms_iou import iou_based_nms_batched
+
+        boxes, _, _, _ = self.forward(img_t0, pcls_t0, train=False, canvas=canvas)
+        thr = self.cfg.nms_iou_threshold if overlap_threshold is None else overlap_threshold
+        logits = boxes.probs[..., 0]
+        key = torch.sigmoid(logits) if self.cfg.box_prediction.activations.probs == "none" else logits
+        if sigmoid_probs and self.cfg.box_prediction.activations.probs == "none":
+            boxes.probs = torch.sigmoid(boxes.probs)
+        return iou_based_nms_batched(boxes, thr, pre_nms_max_boxes, post_nms_max_boxes, scores=key, logit_threshold=logit_threshold,
+                                     threshold_values=logits)
+
     def apply_all_output_modifications(self, *, raw_box_vars, gt_boxes=None, centermaps_gt=None):
         """reference :111-151"""
         activated = {k: self.activations[k](v) for k, v in raw_box_vars.items()}

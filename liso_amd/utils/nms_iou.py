@@ -52,6 +52,38 @@ def iou_based_nms(objects: Shape, overlap_threshold: float, pre_nms_max_boxes: i
                             pre_maxsize=pre_nms_max_boxes, post_max_size=post_nms_max_boxes)
 
 
+@torch.no_grad()
+def iou_based_nms_batched(boxes: Shape, overlap_threshold: float, pre_nms_max_boxes: int = None, post_nms_max_boxes: int = 500,
+                          scores=None, *, logit_threshold: float = None, threshold_values=None):
+    """`iou_based_nms` for a padded batch, on the device, with no host sync (include/liso_det_nms.h; graph-capturable).
+
+    boxes: Shape [B,N] with padding slots (valid False); scores fp32 [B,N], default probs[..., 0].
+    Returns (Shape [B,P], keep_idx int64 [B,P], counts int32 [B]) with P = post_nms_max_boxes (<= 1024): per sample b,
+    keep_idx[b, :counts[b]] are the slot indices of
+        iou_based_nms(boxes[b].drop_padding_boxes(), overlap_threshold, pre_nms_max_boxes, post_nms_max_boxes)
+    mapped back from the compacted rows to slots, and -1 after them; the Shape holds those rows in that order, the other rows
+    carry the padding values of `Shape.set_padding_val_to(0.0)`.
+    Ordering is STABLE: equal scores keep ascending slot index (the reference's torch.sort is not stable, so its order among
+    ties is unspecified).  NaN scores come first, as torch.sort(stable=True, descending=True) puts them.
+    `logit_threshold`: slots with threshold_values (default: scores) < logit_threshold take no part, as run_val's
+    `probs < logit_threshold` filter (None: no filter)."""
+    from liso_amd import det_nms as D
+    from liso_amd.kabsch.shape_utils import INVALID_CLASS_ID
+
+    B, N = boxes.valid.shape
+    if scores is None:
+        scores = boxes.probs[..., 0]
+    dense = convert_shapes_to_dense_3d(boxes).float().contiguous()
+    keys, order = D.order(scores.float().contiguous(), None if threshold_values is None else threshold_values.float().contiguous(),
+                          boxes.valid.contiguous(), logit_threshold)
+    keep, counts = D.select(dense, keys, order, overlap_threshold, pre_nms_max_boxes, post_nms_max_boxes)
+    names = ("pos", "dims", "rot", "probs", "velo", "valid", "class_id", "difficulty")
+    pads = {"valid": False, "class_id": INVALID_CLASS_ID, "difficulty": INVALID_CLASS_ID}
+    srcs = [getattr(boxes, k).contiguous() for k in names]
+    outs = D.gather(keep, counts, srcs, [pads.get(k, 0.0) for k in names])
+    return Shape(**dict(zip(names, outs))), keep, counts
+
+
 def boxes_iou_bev(boxes_a, boxes_b):
     """reference :102-121 -- (N,7),(M,7) -> (N,M)"""
     assert boxes_a.shape[1] == boxes_b.shape[1] == 7
