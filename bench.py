@@ -8,10 +8,16 @@ Default workload (`--workload loop`, BASELINE.json configs[3] at N GPUs, the wor
 defines the metric on): a "step" = one fused LISO iteration per GPU -- SLIM forward (no_grad) on a pair of 120k-point
 sweeps -> per-point flow -> FlowClusterDetector (BEV dynamicness, DBSCAN, region moments, z fit, Kabsch heading) ->
 rotated NMS -> CenterPoint target maps -> CenterPoint-pillar detector train step (fwd + bwd + [RCCL gradient all-reduce]
-+ AdamW + OneCycleLR), inputs resident in HBM; a step consumes 2 frames.  The same JSON line carries `iou3d_nms`
-(boxes/s of the NMS entry point incl. the device greedy sweep, pairs/s of the IoU matrix; the second half of
-BASELINE.json's metric), `roofline` (the hand-written kernel family with the largest share of the step's GPU time,
-HIP events on the launch stream) and `cpu_baseline` (the oracle port of the same iteration on the host cores).
++ AdamW + OneCycleLR), inputs resident in HBM; a step consumes 2 frames.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write `--dump-outputs` if given, print the
+line (`value`, `ms_per_step`, `step_times`, `final_loss`, `config`).  `--full` adds everything else to the same line, after the
+timed steps: `iou3d_nms` (boxes/s of the NMS entry point incl. the device greedy sweep, pairs/s of the IoU matrix, at three sizes;
+the second half of BASELINE.json's metric), `roofline` / `step_roofline` / `roofline_pillars` (the hand-written kernel family with
+the largest share of the step's GPU time, HIP events on the launch stream, eager passes of their own behind a graph-replayed
+region), `cpu_baseline` (the oracle port of the same iteration on the host cores), the legs below and, with several ranks,
+`dist_cost` and the replicas' parameter checksums.  `--no-cpu-baseline`, `--no-iou3d`, `--no-fp32-leg` and `--no-legs` trim a
+`--full` line.
 `--workload slim` (configs[1]): one SLIM self-supervised TRAIN step on one pair, B=1 per GPU as in the reference's
 `slim_RAFT batch_size_one`.  `--workload detector` (configs[2]): one detector train step, B=4 clouds per GPU, bf16.
 `--workload iou3d`: only the iou3d_nms section.  `--workload stress` (configs[4] on one GPU): the detector train step on
@@ -20,9 +26,9 @@ the pillar path; the line carries `roofline_pillars` (decorate + forward launche
 dominant kernel's `roofline`.
 `--dtype`: bf16 (default: detector in bf16 as BASELINE configs[2] says, SLIM in fp32 tensors on F32X3 MFMAs) | f32x3 (fp32 tensors
 everywhere, three bf16 MFMAs per product: the cheapest arithmetic that meets north_star's 1e-3 on logits and flow,
-tests/test_gpu_parity_full_size.py) | fp32 (native fp32 MFMA everywhere).  The default line also carries bounded legs of the same
-iteration in the two parity-conformant arithmetics (`parity_leg`, `fp32_exact_leg`) and of configs[1] / [2] / [4]
-(`slim_leg`, `detector_leg`, `stress_leg`: `python bench.py --workload ...` run as child processes, their own lines trimmed).
+tests/test_gpu_parity_full_size.py) | fp32 (native fp32 MFMA everywhere).  The default workload's `--full` line also carries bounded
+legs of the same iteration in the two parity-conformant arithmetics (`parity_leg`, `fp32_exact_leg`) and of configs[1] / [2] / [4]
+(`slim_leg`, `detector_leg`, `stress_leg`: `python bench.py --full --workload ...` run as child processes, their own lines trimmed).
 Weak scaling: per-GPU work fixed, samples sharded across ranks by seed, the only collective is the gradient
 all-reduce.  Rank 0 prints ONE JSON line.  `python bench.py --gpus N` without a launcher starts the N ranks itself.
 """
@@ -73,12 +79,17 @@ def parse():
     ap.add_argument("--batch", type=int, default=None,
                     help="clouds (detector workload, default 4) / sweep pairs (loop workload, default 2 = the reference's batch_size, "
                          "liso_config.yml:121) per GPU and step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-iou3d", action="store_true", help="skip the iou3d_nms section of the line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what the headline does not need: per-kernel rooflines (eager event "
+                         "passes), iou3d_nms at three sizes, the CPU baselines, the parity / configs[1] / [2] / [4] / loader legs, the flow "
+                         "export cost and, with several ranks, the collective's cost and the replicas' checksums (default: headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline section of the line")
+    ap.add_argument("--no-iou3d", action="store_true", help="--full: skip the iou3d_nms section of the line")
     ap.add_argument("--no-fp32-leg", action="store_true",
-                    help="loop workload, default dtype: skip the short parity legs (`parity_leg` = f32x3, `fp32_exact_leg` of the line)")
+                    help="--full, loop workload, default dtype: skip the short parity legs (`parity_leg` = f32x3, `fp32_exact_leg` of the line)")
     ap.add_argument("--no-legs", action="store_true",
-                    help="loop workload: skip the bounded configs[1] / [2] / [4] legs (`slim_leg`, `detector_leg`, `stress_leg`: child processes)")
+                    help="--full, loop workload: skip the bounded configs[1] / [2] / [4] legs (`slim_leg`, `detector_leg`, `stress_leg`: "
+                         "child processes)")
     ap.add_argument("--uniform-clouds", action="store_true",
                     help="loop workload: every sweep with exactly 120000 loss-cloud points (default: 16 pairs of 116k-124k points, mean 120k, "
                          "so that the bucket padding and the per-signature graph caches are exercised as on real sweeps)")
@@ -281,20 +292,21 @@ def cpu_baseline_loop(cfg, trainer, s0, s1, torch):
             "stage_seconds": {k: round(v, 4) for k, v in stages.items()}}
 
 
-def bench_iou3d(dev, torch, with_cpu=True, reps=None, warmup=3, outputs=None):
+def bench_iou3d(dev, torch, with_cpu=True, reps=None, warmup=3, outputs=None, full=True):
     """BASELINE.json metric, second half (SURVEY.md 8d ii): boxes/s of one nms_gpu-equivalent call INCLUDING the device
     greedy sweep, pairs/s of the rotated IoU matrix, at N in {256, 1000, 4096}; random car-like boxes (the oracle's
     generator, xy in +-50 m), sorted by score; HIP events on the launch stream, inputs resident in HBM.  VALU fraction at
     SURVEY's fixed 600 flop per pair vs the 157.3 TFLOP/s fp32 vector peak; the C oracle (single thread, like the
     reference's serial boxes_iou_bev_cpu + greedy loop) timed beside it.  `reps` timed calls per size (default 50, 20 at
-    N = 4096) behind `warmup` untimed ones; `outputs` (a dict) receives the IoU matrix and keep list of N = 1000."""
+    N = 4096) behind `warmup` untimed ones; `outputs` (a dict) receives the IoU matrix and keep list of N = 1000.
+    `full=False`: N = 1000 alone (the headline of `--workload iou3d`), without the host API's time and the oracles."""
     import numpy as np
 
     from liso_amd import iou3d_nms_cuda as M
     from oracle import iou3d as O
 
     out = {"flop_per_pair": 600, "valu_peak_tflops": VALU_PEAK_F32_TF, "thresh": 0.1, "sizes": {}}
-    for n in (256, 1000, 4096):
+    for n in (256, 1000, 4096) if full else (1000,):
         b, s = O.random_boxes(n, 1, 50.0)
         b = b[np.argsort(-s, kind="stable")]
         tb = torch.from_numpy(b).to(dev)
@@ -319,16 +331,17 @@ def bench_iou3d(dev, torch, with_cpu=True, reps=None, warmup=3, outputs=None):
         if outputs is not None and n == 1000:
             keep_dev, num_dev = M.nms_gpu_device(tb, 0.1)
             outputs.update({"nms_keep": keep_dev[:int(num_dev.item())], "iou_bev": iou})
-        keep = torch.zeros(n, dtype=torch.int64)
-        t0 = time.perf_counter()
-        for _ in range(5):
-            M.nms_gpu(tb, keep, 0.1)
-        t_api = (time.perf_counter() - t0) / 5
-        row = {"nms_boxes_per_s": n / t_nms, "nms_ms": 1e3 * t_nms, "nms_host_api_ms": 1e3 * t_api,
+        row = {"nms_boxes_per_s": n / t_nms, "nms_ms": 1e3 * t_nms,
                "nms_pairs_per_s": n * (n - 1) / 2 / t_nms,
                "iou_matrix_pairs_per_s": n * n / t_iou, "iou_matrix_ms": 1e3 * t_iou,
                "iou_matrix_valu_frac": 600.0 * n * n / t_iou / (VALU_PEAK_F32_TF * 1e12)}
-        if with_cpu:
+        keep = torch.zeros(n, dtype=torch.int64)
+        if full:
+            t0 = time.perf_counter()
+            for _ in range(5):
+                M.nms_gpu(tb, keep, 0.1)
+            row["nms_host_api_ms"] = 1e3 * (time.perf_counter() - t0) / 5
+        if full and with_cpu:
             t0 = time.perf_counter()
             ref_keep = O.nms(b, 0.1)
             t_cpu_nms = time.perf_counter() - t0
@@ -388,9 +401,10 @@ def dump_outputs(out_dir, arrays, torch):
 
 def child_leg(extra, steps=10, warmup=3, timeout_s=420):
     """one bounded run of another workload of this script as a CHILD process (started, never exec'ed, from this GPU process; the
-    parent idles meanwhile) -> its JSON line trimmed to the numbers a reader of the default line needs"""
+    parent idles meanwhile) -> its JSON line trimmed to the numbers a reader of the `--full` line needs (the leg's own roofline
+    included: the child runs with `--full`, without its own baseline, iou3d section and legs)"""
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
-           "--no-cpu-baseline", "--no-iou3d", "--no-legs"] + list(extra)
+           "--full", "--no-cpu-baseline", "--no-iou3d", "--no-legs"] + list(extra)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "DEBUG_CLR_GRAPH_PACKET_CAPTURE")}
     t0 = time.perf_counter()
     try:
@@ -409,6 +423,103 @@ def child_leg(extra, steps=10, warmup=3, timeout_s=420):
            "wall_s": round(time.perf_counter() - t0, 1), "command": "python bench.py " + " ".join(cmd[2:])}
     if "roofline_pillars" in j:
         out["roofline_pillars"] = {k: j["roofline_pillars"].get(k) for k in ("achieved", "peak", "unit", "frac", "avg_pair_ms", "batch")}
+    return out
+
+
+def kernel_rooflines(args, L, trainer, batch, event_steps, timed_in, ms_per_step, dev, torch):
+    """`--full`: the hand-written kernel family with the largest share of the step against its roofline (`roofline`), the step's
+    convolutions against the matrix cores (`step_roofline`) and the pillar path against HBM (`roofline_pillars`), from the HIP events
+    of `_lib.TIMER` (the timed steps of an eager run; the event passes behind a graph-replayed region)"""
+    durs = {k: L.TIMER.durations_ms(k) for k in list(L.TIMER.events) if L.TIMER.events[k]}
+    totals = {k: sum(v) for k, v in durs.items()}
+    per_unit = {k: L.TIMER.weighted_total_ms(k) for k in durs}  # launches that serve a batch of iterations count 1 / batch
+    static_bytes = static_algorithmic_bytes(args.workload, 1 if args.workload == "loop" else batch, 2 if args.dtype == "bf16" else 4)
+    key = max(per_unit, key=per_unit.get)  # the hand-written kernel family with the largest share of the step
+    if args.workload in ("detector", "stress") and key.startswith("pfn"):
+        key = "pfn_forward_scatter"
+    kname, bound, unit = KERNELS.get(key, (key, "hbm", "bytes"))
+    n_launch = max(len(durs[key]), 1)
+    units = L.TIMER.units.get(key, [])
+    if key == "knn_query" and units:  # queries per launch as counted at the call site
+        nq = sum(units) / len(units)
+        alg_total = n_launch * ((nq + N_POINTS) * 12 + nq * 8)
+    elif units and len(units) == len(durs[key]):
+        alg_total = float(sum(units))
+    else:
+        alg_total = float(static_bytes.get(key, 0)) * n_launch
+    t_total = totals[key] * 1e-3
+    if key == "pfn_forward_scatter" and "pfn_decorate" in totals:  # the pillar pass is two launches: one unit
+        t_total += totals["pfn_decorate"] * 1e-3
+    if bound == "mfma":
+        achieved = alg_total / t_total / 1e12 if t_total > 0 else 0.0
+        peak = MFMA_PEAK_BF16_TF / 3.0 if "f32x3" in key else VALU_PEAK_F32_TF if key.startswith("conv_f32_") else MFMA_PEAK_BF16_TF
+        runit = "TFLOP/s"
+    else:
+        achieved = alg_total / t_total / 1e9 if t_total > 0 else 0.0
+        peak, runit = HBM_PEAK_GBS, "GB/s"
+    # the pipelined loop caps the persistent 3x3 convolutions of the captured SLIM inference at `infer_cus` compute units (default: half
+    # the chip, liso_amd/trainer.py) and the event passes time them under the same cap: their roofline is the peak of the CUs they may
+    # use.  (Only where the family holds nothing but those launches: the bf16 headline's F32X3 forward family; in --dtype f32x3 the
+    # detector's uncapped launches share the family and the whole chip's peak stays.)
+    cu_cap = None
+    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+    if (args.workload == "loop" and args.dtype == "bf16" and key == "conv_f32x3_fwd_roles" and getattr(trainer, "infer_cus", 0)
+            and bound == "mfma"):
+        cu_cap = {"cus": trainer.infer_cus, "of": n_cu, "whole_chip_peak": peak, "whole_chip_frac": achieved / peak}
+        peak = peak * trainer.infer_cus / n_cu
+    traffic, traffic_src = pmc_traffic(args.workload, PMC_PATTERNS[key]) if key in PMC_PATTERNS else (None, None)
+    roofline = {"kernel": kname, "bound": bound, "achieved": achieved, "peak": peak, "unit": runit,
+                "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
+                "avg_launch_ms": 1e3 * t_total / n_launch,
+                "launches_per_step": sum(L.TIMER.weights.get(key, [1.0] * n_launch)) / max(event_steps, 1),
+                ("algorithmic_flop_per_launch" if bound == "mfma" else "algorithmic_bytes_per_launch"): alg_total / n_launch,
+                **({"algorithmic_bytes_per_launch": sum(L.TIMER.bytes[key]) / len(L.TIMER.bytes[key])}
+                   if bound == "mfma" and L.TIMER.bytes.get(key) else {}),
+                # share of the SUMMED event-timed kernel time (the kernels are timed alone on one stream; the pipelined
+                # step overlaps three streams, so a quotient by the step time would not be a share)
+                "share_of_timed_kernels": per_unit[key] / max(sum(per_unit.values()), 1e-12),
+                "timed_in": timed_in,
+                "timed_kernels_ms_per_step": {k: round(v / max(event_steps, 1), 4) for k, v in
+                                              sorted(per_unit.items(), key=lambda kv: -kv[1])}}
+    out = {"roofline": roofline}
+    # the WHOLE step against the matrix-core roofline: algorithmic flops of every convolution launch of a step (counted at the call
+    # sites, 2 * M * N * K of the implicit GEMM; launches that serve several steps weighted by their share) / the time those flops
+    # take at the peak of the arithmetic they run in, over the measured step time.  The HBM-bound stages add nothing to the
+    # numerator: this is "how much of the step's time is accounted for by matrix math at peak".
+    def _peak_tf(k):
+        return MFMA_PEAK_BF16_TF / 3.0 if "f32x3" in k else VALU_PEAK_F32_TF if k.startswith("conv_f32_") else MFMA_PEAK_BF16_TF
+    conv_keys = [k for k in durs if KERNELS.get(k, ("", "", ""))[1] == "mfma" and len(L.TIMER.units.get(k, [])) == len(durs[k])]
+    flops_by = {k: sum(u * w for u, w in zip(L.TIMER.units[k], L.TIMER.weights.get(k, [1.0] * len(durs[k])))) / max(event_steps, 1)
+                for k in conv_keys}
+    at_peak_ms = sum(1e3 * f / (_peak_tf(k) * 1e12) for k, f in flops_by.items())
+    out["step_roofline"] = {"bound": "mfma", "algorithmic_flop_per_step": sum(flops_by.values()),
+                            "time_at_peak_ms": at_peak_ms, "ms_per_step": ms_per_step,
+                            "frac": at_peak_ms / ms_per_step,
+                            "peaks_tflops": {"bf16": MFMA_PEAK_BF16_TF, "f32 via bf16x3": MFMA_PEAK_BF16_TF / 3.0, "f32 exact": VALU_PEAK_F32_TF},
+                            "flop_by_family": {k: v for k, v in sorted(flops_by.items(), key=lambda kv: -kv[1])},
+                            "note": "sum over the step's convolution launches of flops / peak(arithmetic) divided by the measured step time"}
+    if "pfn_forward_scatter" in totals:
+        # the pillar path as its own HBM roofline: decorate (+ scans) and forward launches timed together over the event passes;
+        # algorithmic bytes = points read once + dense canvas + occupancy written once (SURVEY.md 8d)
+        n_p = max(len(durs["pfn_forward_scatter"]), 1)
+        t_p = (totals["pfn_forward_scatter"] + totals.get("pfn_decorate", 0.0)) * 1e-3
+        # bytes as counted at every launch (pcl_to_feature_grid.py): points read once + the dense canvas at ITS element size (fp32 for
+        # the SLIM encoders' canvases, bf16 for the detector's in the default loop) + the occupancy map written once
+        pu = L.TIMER.units.get("pfn_forward_scatter", [])
+        bytes_total = float(sum(pu)) if len(pu) == len(durs["pfn_forward_scatter"]) else 0.0
+        tr_p, src_p = pmc_traffic(args.workload, ["pfn_forward_kernel", "pfn_decorate_kernel"])
+        out["roofline_pillars"] = {"kernel": "pfn_decorate_kernel (+3 scan kernels) + pfn_forward_kernel", "bound": "hbm",
+                                   "achieved": bytes_total / t_p / 1e9 if t_p > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                   "frac": (bytes_total / t_p / 1e9 / HBM_PEAK_GBS) if t_p > 0 else 0.0,
+                                   "algorithmic_bytes_per_launch_pair": bytes_total / n_p, "avg_pair_ms": 1e3 * t_p / n_p,
+                                   "launch_pairs": n_p, "traffic": tr_p, "traffic_source": src_p}
+    if cu_cap is not None:
+        roofline["compute_units"] = cu_cap
+    if bound == "mfma" and "f32x3" in key:
+        roofline["peak_note"] = ("fp32 tensors computed as 3 bf16 MFMAs per product (hi*hi + hi*lo + lo*hi): peak = dense "
+                                 "bf16 MFMA / 3 in algorithmic fp32 flops (native f32 MFMA peak: 157.3 TFLOP/s)" +
+                                 (f"; these launches are capped at {cu_cap['cus']} of {cu_cap['of']} compute units (the pipeline's partition, "
+                                  "`compute_units`): peak scaled by that share" if cu_cap is not None else ""))
     return out
 
 
@@ -566,7 +677,8 @@ def main():
     if args.workload == "iou3d":
         if rank == 0:
             outputs = {} if args.dump_outputs else None
-            r = bench_iou3d(dev, torch, with_cpu=not args.no_cpu_baseline, reps=args.steps, warmup=args.warmup, outputs=outputs)
+            r = bench_iou3d(dev, torch, with_cpu=not args.no_cpu_baseline, reps=args.steps, warmup=args.warmup, outputs=outputs,
+                            full=args.full)
             if outputs is not None:
                 dump_outputs(args.dump_outputs, outputs, torch)
             n = "1000"
@@ -698,7 +810,7 @@ def main():
         captures_after_warmup = (len(trainer._infer_graphs), trainer.mine_captures)
 
     graphed = (args.workload == "slim" and args.graph) or (args.workload in ("loop", "detector", "stress") and not args.eager)
-    if not graphed:  # per-launch HIP events on the launch stream, inside the timed region
+    if not graphed:  # per-launch HIP events on the launch stream, inside the timed region (with or without --full: same timed steps)
         L.TIMER.enable_all()
     L.TIMER.reset()
     if world > 1:
@@ -725,9 +837,9 @@ def main():
                   "timing": f"{args.steps} hipEvent pairs on the caller's stream, one per step (ms_per_step = wall clock over the same steps between "
                             "two synchronisations)"} if step_ms else None
     # data parallelism: what the gradient all-reduce COSTS a step, measured: the same steps once more with the collective skipped (the
-    # replicas diverge from here on: the parameter checksums below were taken first), and the collective alone on an idle GPU
+    # replicas diverge from here on: the parameter checksums below were taken first), and the collective alone on an idle GPU (--full)
     dist_cost = None
-    if world > 1:
+    if world > 1 and args.full:
         det = getattr(trainer, "detector", trainer)
         cs_early = torch.stack([p.detach().double().sum() for p in det.net.parameters()]).sum().reshape(1)
         if hasattr(det, "_reduce_gradients") and det.use_graph:
@@ -756,7 +868,7 @@ def main():
                          "note": "exposed all-reduce time per step = ms_per_step - ms_per_step_without_collective (same steps, collective skipped, "
                                  "MAX over ranks); allreduce_alone_ms = the flat gradient buffer all-reduced 10 times on an otherwise idle GPU"}
     timed_in, event_steps = "the timed steps", args.steps
-    if graphed:
+    if graphed and args.full:
         # the timed steps replay a hipGraph, inside which per-kernel events cannot be recorded: the same kernels are timed
         # over two eager forward+backward passes right after the timed region.  EVERY rank runs them and they issue no
         # collective and no optimizer update (update=False), so the ranks stay in lock step for the MAX reduction below.
@@ -776,7 +888,7 @@ def main():
         timed_in = f"{event_steps} eager fwd+bwd passes after the timed region, one untimed pass first (the timed steps replay a hipGraph)"
     L.TIMER.disable_all()
     legs = {}
-    if args.workload == "loop" and args.dtype == "bf16" and world == 1 and rank == 0 and not args.no_fp32_leg:
+    if args.full and args.workload == "loop" and args.dtype == "bf16" and world == 1 and rank == 0 and not args.no_fp32_leg:
         # the same iteration in the two parity-conformant arithmetics (north_star: logits / flow within 1e-3 of the reference's fp32
         # path; certified at this size by tests/test_gpu_parity_full_size.py), bounded legs, each this script in a CHILD process:
         #   parity_leg      fp32 tensors everywhere, three bf16 MFMAs per product (F32X3), SLIM and detector  (--dtype f32x3)
@@ -802,7 +914,7 @@ def main():
                                        f"[{'exact' if exact else 'x3'}]"]
                 leg["note"] = "same launch structure and inputs as the headline line, in a child process"
             legs[name] = leg
-    if args.workload == "loop" and args.dtype == "bf16" and world == 1 and rank == 0 and not args.no_legs:
+    if args.full and args.workload == "loop" and args.dtype == "bf16" and world == 1 and rank == 0 and not args.no_legs:
         # BASELINE configs[1] / [2] / [4] as bounded legs: this script with --workload slim | detector | stress in a child process
         # (the SLIM training graph needs another runtime mode, see _graph_env), its JSON line trimmed to the numbers
         for name, extra in (("slim_leg", ["--workload", "slim", "--graph"]), ("slim_exact_leg", ["--workload", "slim", "--graph", "--dtype", "fp32"]),
@@ -815,7 +927,7 @@ def main():
                                           "the pipeline, one collated pinned buffer and one H2D copy per pair into a ring of device staging slots (bench.py "
                                           "PinnedLoader); `value` of the line itself has every pair resident in HBM")
     export_cost = None
-    if args.workload == "loop" and world == 1 and rank == 0 and not args.no_legs:
+    if args.full and args.workload == "loop" and world == 1 and rank == 0 and not args.no_legs:
         # what a flow EXPORT costs next to the loop's inference (the miner reads flow t0 -> t1 only; liso/slim/experiment.py:363-471
         # writes both directions): eager calls on one sweep pair incl. the pillar encoders, wall time per pair
         def wall(fn, reps=8):
@@ -837,6 +949,7 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if world > 1 and args.full:
         # data parallelism keeps the replicas identical: every rank's parameter checksum travels to rank 0 and into the line
         cs = cs_early  # (taken right behind the timed steps, before the collective-free steps of `dist_cost`)
         got = [torch.zeros_like(cs) for _ in range(world)]
@@ -844,44 +957,6 @@ def main():
         checksums = [float(g.item()) for g in got]
 
     if rank == 0:
-        durs = {k: L.TIMER.durations_ms(k) for k in list(L.TIMER.events) if L.TIMER.events[k]}
-        totals = {k: sum(v) for k, v in durs.items()}
-        per_unit = {k: L.TIMER.weighted_total_ms(k) for k in durs}  # launches that serve a batch of iterations count 1 / batch
-        static_bytes = static_algorithmic_bytes(args.workload, 1 if args.workload == "loop" else batch, 2 if args.dtype == "bf16" else 4)
-        key = max(per_unit, key=per_unit.get)  # the hand-written kernel family with the largest share of the step
-        if args.workload in ("detector", "stress") and key.startswith("pfn"):
-            key = "pfn_forward_scatter"
-        kname, bound, unit = KERNELS.get(key, (key, "hbm", "bytes"))
-        n_launch = max(len(durs[key]), 1)
-        units = L.TIMER.units.get(key, [])
-        if key == "knn_query" and units:  # queries per launch as counted at the call site
-            nq = sum(units) / len(units)
-            alg_total = n_launch * ((nq + N_POINTS) * 12 + nq * 8)
-        elif units and len(units) == len(durs[key]):
-            alg_total = float(sum(units))
-        else:
-            alg_total = float(static_bytes.get(key, 0)) * n_launch
-        t_total = totals[key] * 1e-3
-        if key == "pfn_forward_scatter" and "pfn_decorate" in totals:  # the pillar pass is two launches: one unit
-            t_total += totals["pfn_decorate"] * 1e-3
-        if bound == "mfma":
-            achieved = alg_total / t_total / 1e12 if t_total > 0 else 0.0
-            peak = MFMA_PEAK_BF16_TF / 3.0 if "f32x3" in key else VALU_PEAK_F32_TF if key.startswith("conv_f32_") else MFMA_PEAK_BF16_TF
-            runit = "TFLOP/s"
-        else:
-            achieved = alg_total / t_total / 1e9 if t_total > 0 else 0.0
-            peak, runit = HBM_PEAK_GBS, "GB/s"
-        # the pipelined loop caps the persistent 3x3 convolutions of the captured SLIM inference at `infer_cus` compute units (default: half
-        # the chip, liso_amd/trainer.py) and the event passes time them under the same cap: their roofline is the peak of the CUs they may
-        # use.  (Only where the family holds nothing but those launches: the bf16 headline's F32X3 forward family; in --dtype f32x3 the
-        # detector's uncapped launches share the family and the whole chip's peak stays.)
-        cu_cap = None
-        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
-        if (args.workload == "loop" and args.dtype == "bf16" and key == "conv_f32x3_fwd_roles" and getattr(trainer, "infer_cus", 0)
-                and bound == "mfma"):
-            cu_cap = {"cus": trainer.infer_cus, "of": n_cu, "whole_chip_peak": peak, "whole_chip_frac": achieved / peak}
-            peak = peak * trainer.infer_cus / n_cu
-        traffic, traffic_src = pmc_traffic(args.workload, PMC_PATTERNS[key]) if key in PMC_PATTERNS else (None, None)
         workload = {
             "loop": ("fused LISO iteration (BASELINE configs[3]): SLIM fwd (no_grad; forward flow direction t0->t1 only, only the last "
                      "of the 6 RAFT iterations decoded -- what the box miner consumes) -> FlowClusterDetector (DBSCAN) -> NMS "
@@ -943,36 +1018,9 @@ def main():
                                                       "cell_capacity_exceeded": _sparse_overflow(dev)}},
             "final_loss": float(loss),
             "step_times": step_times,
-            "roofline": {"kernel": kname, "bound": bound, "achieved": achieved, "peak": peak, "unit": runit,
-                         "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
-                         "avg_launch_ms": 1e3 * t_total / n_launch,
-                         "launches_per_step": sum(L.TIMER.weights.get(key, [1.0] * n_launch)) / max(event_steps, 1),
-                         ("algorithmic_flop_per_launch" if bound == "mfma" else "algorithmic_bytes_per_launch"): alg_total / n_launch,
-                         **({"algorithmic_bytes_per_launch": sum(L.TIMER.bytes[key]) / len(L.TIMER.bytes[key])}
-                            if bound == "mfma" and L.TIMER.bytes.get(key) else {}),
-                         # share of the SUMMED event-timed kernel time (the kernels are timed alone on one stream; the pipelined
-                         # step overlaps three streams, so a quotient by the step time would not be a share)
-                         "share_of_timed_kernels": per_unit[key] / max(sum(per_unit.values()), 1e-12),
-                         "timed_in": timed_in,
-                         "timed_kernels_ms_per_step": {k: round(v / max(event_steps, 1), 4) for k, v in
-                                                       sorted(per_unit.items(), key=lambda kv: -kv[1])}},
         }
-        # the WHOLE step against the matrix-core roofline: algorithmic flops of every convolution launch of a step (counted at the call
-        # sites, 2 * M * N * K of the implicit GEMM; launches that serve several steps weighted by their share) / the time those flops
-        # take at the peak of the arithmetic they run in, over the measured step time.  The HBM-bound stages add nothing to the
-        # numerator: this is "how much of the step's time is accounted for by matrix math at peak".
-        def _peak_tf(k):
-            return MFMA_PEAK_BF16_TF / 3.0 if "f32x3" in k else VALU_PEAK_F32_TF if k.startswith("conv_f32_") else MFMA_PEAK_BF16_TF
-        conv_keys = [k for k in durs if KERNELS.get(k, ("", "", ""))[1] == "mfma" and len(L.TIMER.units.get(k, [])) == len(durs[k])]
-        flops_by = {k: sum(u * w for u, w in zip(L.TIMER.units[k], L.TIMER.weights.get(k, [1.0] * len(durs[k])))) / max(event_steps, 1)
-                    for k in conv_keys}
-        at_peak_ms = sum(1e3 * f / (_peak_tf(k) * 1e12) for k, f in flops_by.items())
-        line["step_roofline"] = {"bound": "mfma", "algorithmic_flop_per_step": sum(flops_by.values()),
-                                 "time_at_peak_ms": at_peak_ms, "ms_per_step": 1e3 * elapsed / args.steps,
-                                 "frac": at_peak_ms / (1e3 * elapsed / args.steps),
-                                 "peaks_tflops": {"bf16": MFMA_PEAK_BF16_TF, "f32 via bf16x3": MFMA_PEAK_BF16_TF / 3.0, "f32 exact": VALU_PEAK_F32_TF},
-                                 "flop_by_family": {k: v for k, v in sorted(flops_by.items(), key=lambda kv: -kv[1])},
-                                 "note": "sum over the step's convolution launches of flops / peak(arithmetic) divided by the measured step time"}
+        if args.full:
+            line.update(kernel_rooflines(args, L, trainer, batch, event_steps, timed_in, line["ms_per_step"], dev, torch))
         if loader is not None:
             line["loader"] = {"pinned_host_pairs": len(loader.host), "uploads": loader.uploads, "h2d_bytes_total": loader.uploaded_bytes,
                               "h2d_bytes_per_step": loader.uploaded_bytes / max(loader.uploads, 1) * batch,
@@ -981,31 +1029,9 @@ def main():
         if dist_cost is not None:
             dist_cost["exposed_allreduce_ms_per_step"] = line["ms_per_step"] - dist_cost["ms_per_step_without_collective"]
             line["dist_cost"] = dist_cost
-        if "pfn_forward_scatter" in totals:
-            # the pillar path as its own HBM roofline: decorate (+ scans) and forward launches timed together over the event passes;
-            # algorithmic bytes = points read once + dense canvas + occupancy written once
-            n_p = max(len(durs["pfn_forward_scatter"]), 1)
-            t_p = (totals["pfn_forward_scatter"] + totals.get("pfn_decorate", 0.0)) * 1e-3
-            # bytes as counted at every launch (pcl_to_feature_grid.py): points read once + the dense canvas at ITS element size (fp32 for
-            # the SLIM encoders' canvases, bf16 for the detector's in the default loop) + the occupancy map written once
-            pu = L.TIMER.units.get("pfn_forward_scatter", [])
-            bytes_total = float(sum(pu)) if len(pu) == len(durs["pfn_forward_scatter"]) else 0.0
-            tr_p, src_p = pmc_traffic(args.workload, ["pfn_forward_kernel", "pfn_decorate_kernel"])
-            line["roofline_pillars"] = {"kernel": "pfn_decorate_kernel (+3 scan kernels) + pfn_forward_kernel", "bound": "hbm",
-                                        "achieved": bytes_total / t_p / 1e9 if t_p > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                        "frac": (bytes_total / t_p / 1e9 / HBM_PEAK_GBS) if t_p > 0 else 0.0,
-                                        "algorithmic_bytes_per_launch_pair": bytes_total / n_p, "avg_pair_ms": 1e3 * t_p / n_p,
-                                        "launch_pairs": n_p, "traffic": tr_p, "traffic_source": src_p}
-        if cu_cap is not None:
-            line["roofline"]["compute_units"] = cu_cap
-        if bound == "mfma" and "f32x3" in key:
-            line["roofline"]["peak_note"] = ("fp32 tensors computed as 3 bf16 MFMAs per product (hi*hi + hi*lo + lo*hi): peak = dense "
-                                             "bf16 MFMA / 3 in algorithmic fp32 flops (native f32 MFMA peak: 157.3 TFLOP/s)" +
-                                             (f"; these launches are capped at {cu_cap['cus']} of {cu_cap['of']} compute units (the pipeline's partition, "
-                                              "`compute_units`): peak scaled by that share" if cu_cap is not None else ""))
-        if world == 1 and not args.no_iou3d:
+        if args.full and world == 1 and not args.no_iou3d:
             line["iou3d_nms"] = bench_iou3d(dev, torch, with_cpu=not args.no_cpu_baseline)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.workload == "slim":
                 line["cpu_baseline"] = cpu_baseline_slim(cfg, trainer, s0, s1, torch)
             elif args.workload == "detector":

@@ -32,7 +32,7 @@ if "--workload" not in sys.argv:
 assert sys.argv[sys.argv.index("--workload") + 1] == "detector", "the library-backed comparison covers the detector workload"
 if "--eager" not in sys.argv:
     sys.argv.append("--eager")
-for flag in ("--no-fp32-leg", "--no-legs"):
+for flag in ("--full", "--no-fp32-leg", "--no-legs"):
     if flag not in sys.argv:
         sys.argv.append(flag)
 bench.main()

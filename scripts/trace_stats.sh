@@ -6,7 +6,7 @@ TAG=$1; RE=$2; shift; shift
 OUT=$R/gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT; mkdir -p $OUT
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $R/bench.py --no-cpu-baseline --no-iou3d --no-legs --steps ${TRACE_STEPS:-50} --warmup 5 "$@" > $OUT/line.json 2> $OUT/err.txt
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $R/bench.py --full --no-cpu-baseline --no-iou3d --no-legs --steps ${TRACE_STEPS:-50} --warmup 5 "$@" > $OUT/line.json 2> $OUT/err.txt
 F=$(find $OUT -name "*_kernel_stats.csv" | head -1)
 cp $F $R/gpurun_out/${TAG}_stats.csv
 find $OUT -name "*_kernel_trace.csv" -delete; find $OUT -name "*.db" -delete

@@ -140,7 +140,8 @@ def test_bench_ranks_on_one_gpu_reports_world_and_identical_replicas(workload, w
     """`python bench.py --gpus 2 | 4` through its own rank spawner, all ranks on cuda:0, gloo carrying the collectives
     (LISO_DIST_BACKEND=gloo: RCCL refuses two ranks on one device; the default backend "nccl" = RCCL is what the driver's
     multi-GPU runs use).  Exercises the world > 1 code of bench.py: barrier-bracketed timing, MAX over ranks, the flat-buffer
-    gradient all-reduce after every replay, rank-0-only line.  The line must report n_gpus 2 and replicas that agree."""
+    gradient all-reduce after every replay, rank-0-only line.  The line must report n_gpus 2 and replicas that agree (`--full`: the
+    replicas' checksums, the collective's cost and the step's roofline are not part of a plain run's line)."""
     import json
     import subprocess
     import sys
@@ -150,7 +151,7 @@ def test_bench_ranks_on_one_gpu_reports_world_and_identical_replicas(workload, w
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "2", "--workload", workload,
-                        "--no-cpu-baseline", "--no-iou3d"], env=env, capture_output=True, text=True, timeout=850)
+                        "--full", "--no-cpu-baseline", "--no-iou3d"], env=env, capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]  # rank 0 only
