@@ -21,6 +21,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "liso_conv.h" /* liso_wgrad_reduce_job */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -53,6 +55,16 @@ int liso_bn_relu_bwd_strided(const void* dy, long dy_stride, const void* x, long
 int liso_bn_relu_bwd_ticket(const void* dy, const void* x, int is_bf16, long m, int c, const float* gamma, const float* stats,
                             int training, int relu, void* dx, float* grad_gamma, float* grad_beta, void* workspace,
                             size_t workspace_bytes, unsigned* ticket, void* stream);
+
+/* liso_bn_relu_bwd / liso_bn_relu_bwd_strided (dy_stride = x_stride = dx_stride = 0: dense rows) whose finalize launch also carries the
+ * blocks of a deferred weight-gradient slab reduction (include/liso_conv.h: liso_conv_wgrad_deferred): grid = the finalize's blocks
+ * first, then the reduction's.  The two roles share the launch and nothing else -- no flag, fence or atomic between them; every block
+ * runs the instructions of the separate launches on the same data, so all results are the same bits.  The finalize (latency-bound, a
+ * few blocks) runs in the shadow of the reduction (bandwidth-bound), one launch less on the backward pass's dependent chain per layer.
+ * job == NULL: exactly liso_bn_relu_bwd(_strided). */
+int liso_bn_relu_bwd_chained(const void* dy, long dy_stride, const void* x, long x_stride, int is_bf16, long m, int c, const float* gamma,
+                             const float* stats, int training, int relu, void* dx, long dx_stride, float* grad_gamma, float* grad_beta,
+                             void* workspace, size_t workspace_bytes, const liso_wgrad_reduce_job* job, void* stream);
 
 /* ---- InstanceNorm2d(+ReLU), training: the same passes with one set of statistics per sample ---------------------------------
  * Replaces `nn.InstanceNorm2d(affine=True)` + `ReLU` of the SLIM encoders in training (liso/slim/model/extractor.py:24-38,

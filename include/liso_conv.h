@@ -165,6 +165,26 @@ int liso_conv_wgrad(const liso_conv_desc* d, const void* x, const float* in_scal
                     int dy_pix_stride, int transposed, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* The same weight gradient with the slab reduction handed to the caller.  Nothing reads dw / dbias before the optimizer, but the
+ * reduction is a launch of its own on the stream that carries the backward pass's dependent chain; a caller that is about to issue
+ * another tiny launch on that stream (the BatchNorm-backward finalize, include/liso_bn.h: liso_bn_relu_bwd_chained) lets the
+ * reduction's blocks ride in it.  liso_conv_wgrad_deferred launches the slab kernel only and fills `job` (a plain value: the library
+ * keeps no state); liso_conv_wgrad_reduce launches the reduction of a job as liso_conv_wgrad does.  dw / dbias are undefined until the
+ * job has been reduced, exactly once, behind the slab kernel in stream order; the workspace must stay untouched until then.  Either
+ * route writes the same bits. */
+typedef struct liso_wgrad_reduce_job {
+    const float* slab;       /* [splits][taps][cip][cop] partial weight gradients (inside the workspace) */
+    const float* bias_slab;  /* [bias_rows][cop] partial bias gradients, NULL without dbias */
+    float* dw;
+    float* dbias;            /* may be NULL */
+    long cip, cop;           /* padded input / output channels of a slab */
+    int splits, bias_rows, taps, ci, co, transposed;
+} liso_wgrad_reduce_job;
+int liso_conv_wgrad_deferred(const liso_conv_desc* d, const void* x, const float* in_scale, const float* in_shift, const void* dy,
+                             int dy_pix_stride, int transposed, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
+                             liso_wgrad_reduce_job* job, void* stream);
+int liso_conv_wgrad_reduce(const liso_wgrad_reduce_job* job, void* stream);
+
 /* BatchNorm statistics from the partial sums of a forward launch (fixed order, fp64 merge):
  *   mean = shift + S1 / n, var = S2 / n - (S1 / n)^2 (biased), n = batch * ho * wo
  *   stats[4 * c] = scale | shift | mean | invstd with scale = gamma * invstd, shift = beta - mean * scale

@@ -250,6 +250,7 @@ SIGNATURES = {
     "liso_in_relu_bwd_sum": (_i, [_vp, _vp, _i, _i, ctypes.c_long, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_bn_relu_bwd": (_i, [_vp, _vp, _i, ctypes.c_long, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_bn_relu_bwd_strided": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _vp, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp, _vp, _sz, _vp]),
+    "liso_bn_relu_bwd_chained": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _vp, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp, _vp, _sz, _vp, _vp]),
     "liso_bn_relu_bwd_ticket": (_i, [_vp, _vp, _i, ctypes.c_long, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "liso_knn_workspace_bytes": (_sz, [_vp, _i]),
     "liso_knn_build_f32": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
@@ -266,6 +267,8 @@ SIGNATURES = {
     "liso_conv_plan_info": (_i, [_vp, _vp]),
     "liso_conv_wgrad_workspace_bytes": (_sz, [_vp]),
     "liso_conv_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "liso_conv_wgrad_deferred": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "liso_conv_wgrad_reduce": (_i, [_vp, _vp]),
     "liso_conv_wgrad_sparse_workspace_bytes": (_sz, [_vp]),
     "liso_conv_wgrad_sparse_f32": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "liso_conv_wgrad_smallci_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
@@ -341,6 +344,12 @@ class ConvPackJob(ctypes.Structure):
     """mirror of liso_conv_pack_job (include/liso_conv.h)"""
     _fields_ = [("src", _vp), ("dst", _vp), ("d0", _i), ("d1", _i), ("kh", _i), ("kw", _i), ("transposed", _i), ("for_dgrad", _i),
                 ("mode", _i)]
+
+
+class WgradReduceJob(ctypes.Structure):
+    """mirror of liso_wgrad_reduce_job (include/liso_conv.h)"""
+    _fields_ = [("slab", _vp), ("bias_slab", _vp), ("dw", _vp), ("dbias", _vp), ("cip", ctypes.c_long), ("cop", ctypes.c_long),
+                ("splits", _i), ("bias_rows", _i), ("taps", _i), ("ci", _i), ("co", _i), ("transposed", _i)]
 
 
 class KnnGrid(ctypes.Structure):

@@ -13,6 +13,7 @@
 
 #include "../../include/liso_bn.h"
 #include "../../include/liso_iou3d.h"
+#include "chain_bodies.h"
 #include "elem16.h"
 
 namespace {
@@ -372,61 +373,30 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
                           fin.coef + (size_t)blockIdx.y * 3 * c, sh_a, sh_b, kThreads);
 }
 
-// sums -> grad_beta, grad_gamma and the three dx coefficients per channel: dx = A * (dz - B - xhat * Cc)
-// blockIdx.x = group (InstanceNorm sample), blockIdx.y = channel segment of `cw` channels (cw = c: one block per group).  With 32-channel
-// segments every thread merges nblk / 32 partial sums -- one round of loads instead of four to eight dependent ones at 128 / 256 channels
-// (the launch sits between the reduction and the dx pass of EVERY layer: 6.1 us each before, 23 per detector step).
-__global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __restrict__ partial, int nblk, long m, int c, int cw,
-                                                               const float* __restrict__ gamma,
-                                                               const float* __restrict__ stats, int training,
-                                                               float* __restrict__ grad_gamma, float* __restrict__ grad_beta,
-                                                               float* __restrict__ coef) {
+// sums -> grad_beta, grad_gamma and the three dx coefficients per channel (chain_bodies.h: bn_bwd_finalize_segment)
+// blockIdx.x = group (InstanceNorm sample), blockIdx.y = channel segment of `cw` channels (cw = c: one block per group)
+__global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(liso_chain::BnBwdFinalizeArgs f) {
     __shared__ double sh_a[1024], sh_b[1024];
-    partial += (size_t)blockIdx.x * nblk * 2 * c;
-    stats += (size_t)blockIdx.x * 4 * c; coef += (size_t)blockIdx.x * 3 * c;
-    grad_gamma += (size_t)blockIdx.x * c; grad_beta += (size_t)blockIdx.x * c;
-    const int tid = threadIdx.x;
-    const int chunks = 1024 / cw > 0 ? 1024 / cw : 1;
-    const int lc = tid % cw, chunk = tid / cw;
-    const int ch = blockIdx.y * cw + lc;
-    double a = 0.0, b = 0.0;
-    if (chunk < chunks) {
-        const int per = (nblk + chunks - 1) / chunks;
-        const int lo = chunk * per, hi = lo + per < nblk ? lo + per : nblk;
-        int q = lo;
-        for (; q + 8 <= hi; q += 8) {  // 16 independent loads in flight, summed in block order
-            float va[8], vb[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) { va[j] = partial[(size_t)(q + j) * 2 * c + ch]; vb[j] = partial[(size_t)(q + j) * 2 * c + c + ch]; }
-#pragma unroll
-            for (int j = 0; j < 8; j++) { a += (double)va[j]; b += (double)vb[j]; }
-        }
-        for (; q < hi; q++) { a += (double)partial[(size_t)q * 2 * c + ch]; b += (double)partial[(size_t)q * 2 * c + c + ch]; }
+    liso_chain::bn_bwd_finalize_segment(f, blockIdx.x, blockIdx.y, sh_a, sh_b);
+}
+
+// The finalize of ONE BatchNorm (blocks [0, n_fin): the channel segments) and the slab reduction of a deferred weight gradient (the
+// blocks behind them, four of the reduction's 256-thread blocks per workgroup) in one launch.  Nothing reads the weight gradient before
+// the optimizer, but as a launch of its own the reduction (~8 us, bandwidth-bound) sat on the backward pass's dependent chain in front
+// of the layer's data gradient; here the finalize (~5 us of dependent latency in a few blocks, dispatched first) runs in its shadow.
+// The roles share the launch and nothing else: no flag, fence or atomic, and a block's role depends on blockIdx only.
+template <int PARTS>
+__global__ __launch_bounds__(1024) void bn_bwd_finalize_reduce_kernel(liso_chain::BnBwdFinalizeArgs f, int n_fin,
+                                                                      liso_wgrad_reduce_job j, long n_red) {
+    __shared__ double sh[2048];  // finalize: 2 x 1024 doubles; reduction: 4 x (16 x 16 float4) -- 16 KB either way
+    if ((int)blockIdx.x < n_fin) {
+        liso_chain::bn_bwd_finalize_segment(f, 0, blockIdx.x, sh, sh + 1024);
+        return;
     }
-    sh_a[tid] = a; sh_b[tid] = b;
-    __syncthreads();
-    // the chunk sums per channel in chunk order; 32 chunks (32-channel segments) as a fixed two-level tree: 4 runs of 8, then the 4 run sums
-    if (chunks == 32) {
-        double ra = 0.0, rb = 0.0;
-        if (tid < 4 * cw) {
-            const int run = tid / cw;
-#pragma unroll
-            for (int q = 0; q < 8; q++) { ra += sh_a[(run * 8 + q) * cw + lc]; rb += sh_b[(run * 8 + q) * cw + lc]; }
-        }
-        __syncthreads();
-        if (tid < 4 * cw) { sh_a[tid] = ra; sh_b[tid] = rb; }
-        __syncthreads();
-    }
-    if (tid < cw) {
-        a = 0.0; b = 0.0;
-        const int left = chunks == 32 ? 4 : chunks;
-        for (int q = 0; q < left; q++) { a += sh_a[q * cw + tid]; b += sh_b[q * cw + tid]; }
-        grad_beta[ch] = (float)a;
-        grad_gamma[ch] = (float)b;
-        coef[ch] = gamma[ch] * stats[3 * c + ch];
-        coef[c + ch] = training ? (float)(a / (double)m) : 0.f;
-        coef[2 * c + ch] = training ? (float)(b / (double)m) : 0.f;
-    }
+    const int quarter = threadIdx.x >> 8;
+    const long bid = (long)(blockIdx.x - n_fin) * 4 + quarter;
+    float4(*red)[16] = reinterpret_cast<float4(*)[16]>(sh) + quarter * 16;
+    liso_chain::wgrad_reduce_block<PARTS>(j, bid, threadIdx.x & 255, red, bid < n_red);
 }
 
 // channel segment of the finalize launch: 32 where the channel count allows and there are enough partial sums to spread
@@ -576,7 +546,8 @@ int liso_bn_relu_fwd(const void* x, int is_bf16, long m, int c, const float* gam
 
 static int bn_relu_bwd(const void* dy, const void* x, int is_bf16, long m, int c, const float* gamma, const float* stats,
                        int training, int relu, void* dx, float* grad_gamma, float* grad_beta, void* workspace,
-                       size_t workspace_bytes, unsigned* ticket, void* stream, long dy_stride = 0, long x_stride = 0, long dx_stride = 0) {
+                       size_t workspace_bytes, unsigned* ticket, void* stream, long dy_stride = 0, long x_stride = 0, long dx_stride = 0,
+                       const liso_wgrad_reduce_job* job = nullptr) {
     Geom g;
     int nblk;
     if (!elem_ok(is_bf16) || m <= 0 || !geom(c, is_bf16 ? 8 : 4, m, &g, &nblk)) return LISO_EINVAL;
@@ -594,12 +565,19 @@ static int bn_relu_bwd(const void* dy, const void* x, int is_bf16, long m, int c
     const int grid = stream_grid(m, g);
     const BwdFinal fin{ticket, gamma, training, grad_gamma, grad_beta, coef};
     const int cw = finalize_segment(c, nblk);
+    const liso_chain::BnBwdFinalizeArgs fa{partial, nblk, m, c, cw, gamma, stats, training, grad_gamma, grad_beta, coef};
+    const int n_fin = c / cw;
+    const long n_red = job ? liso_chain::wgrad_reduce_blocks(*job) : 0;
+    const unsigned grid_fr = (unsigned)(n_fin + (n_red + 3) / 4);
 #define LISO_BWD(T, R)                                                                                                     \
     do {                                                                                                                   \
         bn_bwd_reduce_kernel<T, R><<<nblk, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial, fin);     \
-        if (!ticket)                                                                                                       \
-            bn_bwd_finalize_kernel<<<dim3(1, c / cw), 1024, 0, st>>>(partial, nblk, m, c, cw, gamma, stats, training, grad_gamma,  \
-                                                                     grad_beta, coef);                                    \
+        if (job && job->splits > 16)                                                                                       \
+            bn_bwd_finalize_reduce_kernel<16><<<grid_fr, 1024, 0, st>>>(fa, n_fin, *job, n_red);                           \
+        else if (job)                                                                                                      \
+            bn_bwd_finalize_reduce_kernel<1><<<grid_fr, 1024, 0, st>>>(fa, n_fin, *job, n_red);                            \
+        else if (!ticket)                                                                                                  \
+            bn_bwd_finalize_kernel<<<dim3(1, c / cw), 1024, 0, st>>>(fa);                                                  \
         bn_bwd_dx_kernel<T, R><<<grid, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, coef, (T*)dx);          \
     } while (0)
     if (is_bf16 == LISO_ELEM_F16) { if (relu) LISO_BWD(_Float16, true); else LISO_BWD(_Float16, false); }
@@ -630,6 +608,16 @@ int liso_bn_relu_bwd_ticket(const void* dy, const void* x, int is_bf16, long m, 
     if (!ticket) return LISO_EINVAL;
     return bn_relu_bwd(dy, x, is_bf16, m, c, gamma, stats, training, relu, dx, grad_gamma, grad_beta, workspace, workspace_bytes,
                        ticket, stream);
+}
+
+int liso_bn_relu_bwd_chained(const void* dy, long dy_stride, const void* x, long x_stride, int is_bf16, long m, int c, const float* gamma,
+                             const float* stats, int training, int relu, void* dx, long dx_stride, float* grad_gamma, float* grad_beta,
+                             void* workspace, size_t workspace_bytes, const liso_wgrad_reduce_job* job, void* stream) {
+    if (dy_stride < 0 || x_stride < 0 || dx_stride < 0 || ((dy_stride == 0) != (x_stride == 0)) || ((dy_stride == 0) != (dx_stride == 0)))
+        return LISO_EINVAL;
+    if (job && !liso_chain::wgrad_reduce_job_ok(job)) return LISO_EINVAL;
+    return bn_relu_bwd(dy, x, is_bf16, m, c, gamma, stats, training, relu, dx, grad_gamma, grad_beta, workspace, workspace_bytes,
+                       nullptr, stream, dy_stride, x_stride, dx_stride, job);
 }
 
 size_t liso_in_workspace_bytes(int groups, int c) {
@@ -673,14 +661,14 @@ static int in_relu_bwd(const void* dy, const void* x, int is_bf16, int groups, l
     float* coef = partial + (size_t)groups * kMaxBlocks * 2 * c;
     const dim3 gs((unsigned)nblk, (unsigned)groups), ga((unsigned)stream_grid(m, g), (unsigned)groups);
     const int cw = finalize_segment(c, nblk);
+    const liso_chain::BnBwdFinalizeArgs fa{partial, nblk, m, c, cw, gamma, stats, 1, grad_gamma, grad_beta, coef};
 #define LISO_BWD(T, R)                                                                                                     \
     do {                                                                                                                   \
         bn_bwd_reduce_kernel<T, R><<<gs, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial, BwdFinal{}); \
         if (summed)                                                                                                        \
             in_bwd_finalize_sum_kernel<<<1, 1024, 0, st>>>(partial, groups, nblk, m, c, gamma, stats, grad_gamma, grad_beta, coef); \
         else                                                                                                               \
-            bn_bwd_finalize_kernel<<<dim3(groups, c / cw), 1024, 0, st>>>(partial, nblk, m, c, cw, gamma, stats, 1, grad_gamma,     \
-                                                                          grad_beta, coef);                               \
+            bn_bwd_finalize_kernel<<<dim3(groups, c / cw), 1024, 0, st>>>(fa);                                             \
         bn_bwd_dx_kernel<T, R><<<ga, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, coef, (T*)dx);            \
     } while (0)
     if (is_bf16) { if (relu) LISO_BWD(__hip_bfloat16, true); else LISO_BWD(__hip_bfloat16, false); }

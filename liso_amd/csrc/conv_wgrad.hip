@@ -18,6 +18,7 @@
 
 #include "../../include/liso_conv.h"
 #include "../../include/liso_iou3d.h"
+#include "chain_bodies.h"
 #include "elem16.h"
 #include "per_device.h"
 
@@ -881,89 +882,34 @@ __global__ __launch_bounds__(kRsThreads, 1) void conv_wgrad_rs3_kernel(const lis
 #endif
 }
 
-// dw (torch layout) = sum over splits of the slabs, in a fixed order.  PARTS = 16: block = one (tap, k) row x 64 output channels;
-// thread = 4 consecutive channels (one 16-B load per split) x one of 16 split groups (group g adds splits g, g + 16, ... in that
-// order, four loads in flight), then the 16 group sums are added pairwise in a fixed tree.  PARTS = 1 (<= 16 splits): block = 16
-// rows x 64 channels, every thread walks all splits of its 4 channels (all loads in flight), no tree.  The slabs were written a
-// moment ago and sit in L2 / the Infinity Cache; what the reduction needs is bytes in flight (the former version: one 4-B load at a
-// time per thread, 2 TB/s on 37 MB of slabs).
+// the slab reduction (chain_bodies.h: also a role of the BatchNorm-backward finalize launch, include/liso_bn.h)
 template <int PARTS>
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, const float* __restrict__ bias_slab,
-                                                           int splits, int bias_rows, int taps, int ci, int co, long cip, long cop,
-                                                           int transposed, float* __restrict__ dw, float* __restrict__ dbias) {
-    constexpr int RPB = 16 / PARTS;  // rows per block
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(liso_wgrad_reduce_job j) {
     __shared__ float4 red[16][16];
-    const int c4 = threadIdx.x & 15, part = PARTS == 16 ? threadIdx.x >> 4 : 0, rib = PARTS == 16 ? 0 : threadIdx.x >> 4;
-    const int n_tiles = (co + 63) / 64;
-    const long rows = (long)taps * ci;
-    const long row_blocks = (rows + RPB - 1) / RPB;
-    const long bid = blockIdx.x;
-    const bool is_bias = bid >= row_blocks * n_tiles;
-    if (is_bias && !dbias) return;
-    const int ntile = (int)(is_bias ? bid - row_blocks * n_tiles : bid % n_tiles);
-    const long row = is_bias ? 0 : (bid / n_tiles) * RPB + rib;  // tap * ci + k
-    const bool row_ok = is_bias ? rib == 0 : row < rows;
-    const int k = (int)(row % ci), tap = (int)(row / ci);
-    const int n = ntile * 64 + c4 * 4;
-    const int count = is_bias ? bias_rows : splits;
-    const float* src = is_bias ? bias_slab + n : slab + ((long)tap * cip + k) * cop + n;
-    const long stride = is_bias ? cop : (long)taps * cip * cop;
-    float4 s = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (n < co && row_ok) {
-        int sp = part;
-        for (; sp + 3 * PARTS < count; sp += 4 * PARTS) {  // four loads in flight per thread
-            const float4 v0 = *reinterpret_cast<const float4*>(src + (long)sp * stride);
-            const float4 v1 = *reinterpret_cast<const float4*>(src + (long)(sp + PARTS) * stride);
-            const float4 v2 = *reinterpret_cast<const float4*>(src + (long)(sp + 2 * PARTS) * stride);
-            const float4 v3 = *reinterpret_cast<const float4*>(src + (long)(sp + 3 * PARTS) * stride);
-            s.x = (((s.x + v0.x) + v1.x) + v2.x) + v3.x;
-            s.y = (((s.y + v0.y) + v1.y) + v2.y) + v3.y;
-            s.z = (((s.z + v0.z) + v1.z) + v2.z) + v3.z;
-            s.w = (((s.w + v0.w) + v1.w) + v2.w) + v3.w;
-        }
-        for (; sp < count; sp += PARTS) {
-            const float4 v = *reinterpret_cast<const float4*>(src + (long)sp * stride);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-    }
-    if constexpr (PARTS == 16) {
-        red[part][c4] = s;
-        __syncthreads();
-#pragma unroll
-        for (int w = 8; w >= 1; w >>= 1) {  // fixed pairing: (p, p + w)
-            if (part < w) {
-                const float4 o = red[part + w][c4];
-                s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w;
-                red[part][c4] = s;
-            }
-            __syncthreads();
-        }
-    }
-    if (part == 0 && n < co && row_ok) {
-        const float v[4] = {s.x, s.y, s.z, s.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            if (n + e >= co) break;
-            if (is_bias)
-                dbias[n + e] = v[e];
-            else
-                dw[transposed ? (((long)k * co + n + e) * taps + tap) : (((long)(n + e) * ci + k) * taps + tap)] = v[e];
-        }
-    }
+    liso_chain::wgrad_reduce_block<PARTS>(j, blockIdx.x, threadIdx.x, red, true);
 }
 
-int launch_reduce(const float* slab, const float* bias_slab, int splits, int bias_rows, int taps, int ci, int co_w, long cip, long cop,
-                  int transposed, float* dw, float* dbias, hipStream_t st) {
-    const long rows = (long)taps * ci;
-    const int n_tiles = (co_w + 63) / 64;
-    if (splits > 16) {
-        const long blocks = (rows + (dbias ? 1 : 0)) * n_tiles;
-        wgrad_reduce_kernel<16><<<(int)blocks, 256, 0, st>>>(slab, bias_slab, splits, bias_rows, taps, ci, co_w, cip, cop, transposed, dw, dbias);
-    } else {
-        const long blocks = ((rows + 15) / 16 + (dbias ? 1 : 0)) * n_tiles;
-        wgrad_reduce_kernel<1><<<(int)blocks, 256, 0, st>>>(slab, bias_slab, splits, bias_rows, taps, ci, co_w, cip, cop, transposed, dw, dbias);
-    }
+int launch_reduce(const liso_wgrad_reduce_job& j, hipStream_t st) {
+    const long blocks = liso_chain::wgrad_reduce_blocks(j);
+    if (j.splits > 16)
+        wgrad_reduce_kernel<16><<<(int)blocks, 256, 0, st>>>(j);
+    else
+        wgrad_reduce_kernel<1><<<(int)blocks, 256, 0, st>>>(j);
     return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH;
+}
+
+// `job` != nullptr: the caller reduces (liso_conv_wgrad_deferred)
+int launch_reduce(const float* slab, const float* bias_slab, int splits, int bias_rows, int taps, int ci, int co_w, long cip, long cop,
+                  int transposed, float* dw, float* dbias, hipStream_t st, liso_wgrad_reduce_job* job = nullptr) {
+    liso_wgrad_reduce_job j;
+    j.slab = slab; j.bias_slab = dbias ? bias_slab : nullptr; j.dw = dw; j.dbias = dbias;
+    j.cip = cip; j.cop = cop;
+    j.splits = splits; j.bias_rows = bias_rows; j.taps = taps; j.ci = ci; j.co = co_w; j.transposed = transposed;
+    if (job) {
+        *job = j;
+        return LISO_OK;
+    }
+    return launch_reduce(j, st);
 }
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -1628,9 +1574,9 @@ int liso_conv_wgrad_sparse_f32(const liso_conv_desc* d, const float* x, const fl
                          dw, dbias, st);
 }
 
-int liso_conv_wgrad(const liso_conv_desc* d, const void* x, const float* in_scale, const float* in_shift, const void* dy,
-                    int dy_pix_stride, int transposed, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
-                    void* stream) {
+static int conv_wgrad_impl(const liso_conv_desc* d, const void* x, const float* in_scale, const float* in_shift, const void* dy,
+                           int dy_pix_stride, int transposed, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
+                           liso_wgrad_reduce_job* job, void* stream) {
     if (!d || !x || !dy || !dw || !workspace) return LISO_EINVAL;
     if ((in_scale == nullptr) != (in_shift == nullptr)) return LISO_EINVAL;
     const bool h16 = d->mode == LISO_CONV_F16;
@@ -1667,7 +1613,7 @@ int liso_conv_wgrad(const liso_conv_desc* d, const void* x, const float* in_scal
         if (rc3 != LISO_OK) return rc3;
         const int co_w3 = d->wgrad_co > 0 ? d->wgrad_co : d->co;
         return launch_reduce(r3.a.slab, r3.a.bias_slab, r3.a.splits, r3.a.splits, d->w_taps, d->ci, co_w3, (long)r3.a.ci_t * r3.a.ci_w,
-                             (long)r3.a.co_t * CT, transposed, dw, dbias, st3);
+                             (long)r3.a.co_t * CT, transposed, dw, dbias, st3, job);
     }
     WgPlan p;
     if (!make_plan(*d, &p)) return LISO_EINVAL;
@@ -1701,7 +1647,25 @@ int liso_conv_wgrad(const liso_conv_desc* d, const void* x, const float* in_scal
     if (d->wgrad_co < 0 || d->wgrad_co > d->co) return LISO_EINVAL;
     const int co_w = d->wgrad_co > 0 ? d->wgrad_co : d->co;  // channels written (dy may carry zero-padded channels beyond)
     return launch_reduce(p.a.slab, p.a.bias_slab, p.splits, p.splits * d->n_classes, d->w_taps, d->ci, co_w, (long)p.a.ci_t * CT,
-                         (long)p.a.co_t * CT, transposed, dw, dbias, st);
+                         (long)p.a.co_t * CT, transposed, dw, dbias, st, job);
+}
+
+int liso_conv_wgrad(const liso_conv_desc* d, const void* x, const float* in_scale, const float* in_shift, const void* dy,
+                    int dy_pix_stride, int transposed, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    return conv_wgrad_impl(d, x, in_scale, in_shift, dy, dy_pix_stride, transposed, dw, dbias, workspace, workspace_bytes, nullptr, stream);
+}
+
+int liso_conv_wgrad_deferred(const liso_conv_desc* d, const void* x, const float* in_scale, const float* in_shift, const void* dy,
+                             int dy_pix_stride, int transposed, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
+                             liso_wgrad_reduce_job* job, void* stream) {
+    if (!job) return LISO_EINVAL;
+    return conv_wgrad_impl(d, x, in_scale, in_shift, dy, dy_pix_stride, transposed, dw, dbias, workspace, workspace_bytes, job, stream);
+}
+
+int liso_conv_wgrad_reduce(const liso_wgrad_reduce_job* job, void* stream) {
+    if (!liso_chain::wgrad_reduce_job_ok(job)) return LISO_EINVAL;
+    return launch_reduce(*job, (hipStream_t)stream);
 }
 
 size_t liso_conv_wgrad_smallci_workspace_bytes(int batch, int h, int w, int co, int k) {

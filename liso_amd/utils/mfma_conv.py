@@ -485,17 +485,53 @@ def conv_dgrad(dy, weight, spec, x_shape, out_dtype=None, packed=None):
     return dx.permute(0, 3, 1, 2)
 
 
+class WgradReduceJob:
+    """the slab reduction that `conv_wgrad(..., defer_reduce=True)` left to its caller (include/liso_conv.h: liso_wgrad_reduce_job),
+    TOGETHER with the tensors it reads and writes: the slabs live in a workspace that would otherwise go back to the caching
+    allocator when conv_wgrad returns -- the next allocation on the stream (the data gradient's output) could be carved from those
+    very bytes and overwrite the slabs before they are reduced.  The holder keeps them referenced until the launch that reduces them
+    has been issued: `ride()` hands the job to a BatchNorm-backward finalize launch (-> the pointer for liso_bn_relu_bwd_chained),
+    `flush()` launches the plain reduction.  Exactly one of them, once, on the stream of the slab kernel."""
+
+    def __init__(self, job, ws, dw, db, device):
+        self.job, self.ws, self.dw, self.db, self.device, self.done = job, ws, dw, db, device, False
+
+    def ride(self):
+        assert not self.done
+        self.done = True
+        return ctypes.byref(self.job)
+
+    def flush(self):
+        if not self.done:
+            self.done = True
+            with torch.cuda.device(self.device):
+                L.check(L.lib().liso_conv_wgrad_reduce(ctypes.byref(self.job), L.stream_ptr()), "conv_wgrad_reduce")
+
+
+_DEFER_WGRAD_REDUCE = True
+
+
+def set_deferred_wgrad_reduce(on):
+    """off: `_FusedConv.backward` reduces every weight gradient's slabs in a launch of its own, right behind the slab kernel (the
+    form the deferred one is tested against, bit for bit) -> the previous setting"""
+    global _DEFER_WGRAD_REDUCE
+    prev, _DEFER_WGRAD_REDUCE = _DEFER_WGRAD_REDUCE, bool(on)
+    return prev
+
+
 def conv_wgrad(x, dy, weight_shape, spec, in_scale=None, in_shift=None, in_relu=False, want_bias=True, out_dw=None, out_db=None,
-               co_true=None):
+               co_true=None, defer_reduce=False):
     """-> (dw fp32 in torch's layout `weight_shape`, dbias fp32 [Co] | None); None if the geometry is not supported by the
-    kernels (the caller raises: there is no library fallback).  `out_dw` / `out_db`: dense fp32 tensors to write into (overwritten)."""
+    kernels (the caller raises: there is no library fallback).  `out_dw` / `out_db`: dense fp32 tensors to write into (overwritten).
+    `defer_reduce`: -> (dw, dbias, WgradReduceJob | None) -- with a job, dw / dbias are undefined until the caller has had it reduced
+    (None: a kernel without slabs ran, the gradients are complete)."""
     L.require_cuda(x, dy)
     if (x.shape[1] == 4 and x.dtype == torch.float32 and not spec.transposed and spec.stride == 1 and spec.kh == spec.kw and spec.kh in (5, 7)
             and spec.padding == spec.kh // 2 and in_scale is None and tuple(weight_shape[1:]) == (4, spec.kh, spec.kw)
             and os.environ.get("LISO_WGRAD_SMALLCI", "1") != "0"):
         res = _conv_wgrad_smallci(x, dy, weight_shape, spec, want_bias, out_dw, out_db, co_true)
         if res is not None:
-            return res
+            return (*res, None) if defer_reduce else res
     # (7x7 kernels on DENSE inputs with many channels run the row-of-taps MFMA kernel below, which re-stages the halo tile once per
     # kernel row: 1.9 ms on the encoders' stem.  None of the networks' layers gets here -- the stem's canvas is sparse and takes
     # conv_wgrad_sparse (0.11 ms), the motion encoder's 2-4-channel layers (update.py:57,66) take _conv_wgrad_smallci above -- and
@@ -522,11 +558,17 @@ def conv_wgrad(x, dy, weight_shape, spec, in_scale=None, in_shift=None, in_relu=
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     dw = out_dw if out_dw is not None else torch.empty(weight_shape, dtype=torch.float32, device=x.device)
     db = (out_db if out_db is not None else torch.empty(co_true, dtype=torch.float32, device=x.device)) if want_bias else None
-    with torch.cuda.device(x.device):
-        L.check(L.TIMER.launch(_timer_name(mode, "wgrad"), lambda: lib.liso_conv_wgrad(
-            ctypes.byref(d), L.ptr(xv), L.ptr(in_scale) if in_scale is not None else None,
+    args = (ctypes.byref(d), L.ptr(xv), L.ptr(in_scale) if in_scale is not None else None,
             L.ptr(in_shift) if in_shift is not None else None, L.ptr(gv), gps, int(spec.transposed), L.ptr(dw),
-            L.ptr(db) if db is not None else None, L.ptr(ws), nbytes, L.stream_ptr()), units=_flops(d), nbytes=_bytes(d, True)), "conv_wgrad")
+            L.ptr(db) if db is not None else None, L.ptr(ws), nbytes)
+    with torch.cuda.device(x.device):
+        if defer_reduce:  # the slab kernel only (the timer family keeps it; the reduction counts where it rides: bn_bwd)
+            job = L.WgradReduceJob()
+            L.check(L.TIMER.launch(_timer_name(mode, "wgrad"), lambda: lib.liso_conv_wgrad_deferred(*args, ctypes.byref(job), L.stream_ptr()),
+                                   units=_flops(d), nbytes=_bytes(d, True)), "conv_wgrad_deferred")
+            return dw, db, WgradReduceJob(job, ws, dw, db, x.device)
+        L.check(L.TIMER.launch(_timer_name(mode, "wgrad"), lambda: lib.liso_conv_wgrad(*args, L.stream_ptr()),
+                               units=_flops(d), nbytes=_bytes(d, True)), "conv_wgrad")
     return dw, db
 
 
@@ -735,10 +777,11 @@ def _rows_view(t, vec):
     return (v, ps) if regular else (None, 0)
 
 
-def _bn_backward_group(g, x_raw, grp, relu, training, out=None):
+def _bn_backward_group(g, x_raw, grp, relu, training, out=None, job=None):
     """gradient through relu?(bn(x_raw)) of ONE BatchNorm given g = dL/d(output): -> (dx_raw, dgamma, dbeta); g, x_raw logical NCHW.
     Channel slices of wider channels-last tensors are read in place (liso_bn_relu_bwd_strided); `out`: a logical-NCHW tensor (e.g. the
-    group's channel slice of the concatenated input gradient) to write dx_raw into."""
+    group's channel slice of the concatenated input gradient) to write dx_raw into.  `job`: a WgradReduceJob whose slab reduction rides
+    in this call's finalize launch (liso_bn_relu_bwd_chained)."""
     C = grp["gamma"].shape[0]
     vec = 8 if L.is_half(x_raw.dtype) else 4
     xv, xs = _rows_view(x_raw, vec)
@@ -763,7 +806,13 @@ def _bn_backward_group(g, x_raw, grp, relu, training, out=None):
     bf = L.elem_code(xv.dtype)
     units = 5 * M * C * xv.element_size()
     with torch.cuda.device(xv.device):
-        if (xs, gs, ds) != (C, C, C):
+        if job is not None and not job.done:
+            dense = (xs, gs, ds) == (C, C, C)
+            L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd_chained(
+                L.ptr(gv), 0 if dense else gs, L.ptr(xv), 0 if dense else xs, bf, M, C, L.ptr(grp["gamma"]), L.ptr(grp["stats"]), int(training),
+                int(relu), L.ptr(dxv), 0 if dense else ds, L.ptr(gg), L.ptr(gb), L.ptr(ws), nbytes, job.ride(), L.stream_ptr()), units=units),
+                "bn_relu_bwd_chained")
+        elif (xs, gs, ds) != (C, C, C):
             L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd_strided(
                 L.ptr(gv), gs, L.ptr(xv), xs, bf, M, C, L.ptr(grp["gamma"]), L.ptr(grp["stats"]), int(training), int(relu), L.ptr(dxv), ds,
                 L.ptr(gg), L.ptr(gb), L.ptr(ws), nbytes, L.stream_ptr()), units=units), "bn_relu_bwd_strided")
@@ -779,10 +828,10 @@ def _bn_backward_group(g, x_raw, grp, relu, training, out=None):
     return dxv.permute(0, 3, 1, 2), (None if direct else gg), (None if direct else gb)
 
 
-def _bn_backward(g, x_raw, fold):
-    """-> (dx_raw logical NCHW, [dgamma0, dbeta0, dgamma1, dbeta1, ...])"""
+def _bn_backward(g, x_raw, fold, job=None):
+    """-> (dx_raw logical NCHW, [dgamma0, dbeta0, dgamma1, dbeta1, ...]); `job`: see _bn_backward_group (the first group's call takes it)"""
     if len(fold.groups) == 1:
-        dx, gg, gb = _bn_backward_group(g, x_raw, fold.groups[0], fold.relu, fold.training)
+        dx, gg, gb = _bn_backward_group(g, x_raw, fold.groups[0], fold.relu, fold.training, job=job)
         return dx, [gg, gb]
     # several BatchNorms over consecutive channel ranges of one raw tensor (the deblocks' concatenation in front of the head's shared
     # convolution, the four heads' hidden maps): BatchNorm is per channel, so ONE backward over all channels with the groups'
@@ -797,7 +846,7 @@ def _bn_backward(g, x_raw, fold):
         grads, a = [], 0
         for grp in fold.groups:
             C = grp["gamma"].shape[0]
-            dx, gg, gb = _bn_backward_group(g[:, a:a + C], x_raw[:, a:a + C], grp, fold.relu, fold.training, out=dx_full[:, a:a + C])
+            dx, gg, gb = _bn_backward_group(g[:, a:a + C], x_raw[:, a:a + C], grp, fold.relu, fold.training, out=dx_full[:, a:a + C], job=job)
             if dx.data_ptr() != dx_full[:, a:a + C].data_ptr():  # (irregular layout: the group wrote a tensor of its own)
                 dx_full[:, a:a + C].copy_(dx)
             grads += [gg, gb]
@@ -806,7 +855,7 @@ def _bn_backward(g, x_raw, fold):
     gam = torch.cat([grp["gamma"].detach() for grp in fold.groups])
     stats = torch.cat([grp["stats"][k * c:(k + 1) * c] for k in range(4) for grp, c in zip(fold.groups, Cs)])  # scale | shift | mean | invstd
     dx, gg, gb = _bn_backward_group(g, x_raw, {"gamma": gam, "beta": None, "stats": stats, "ticket_key": id(fold.groups[0]["gamma"])},
-                                    fold.relu, fold.training)
+                                    fold.relu, fold.training, job=job)
     grads, a = [], 0
     for c in Cs:
         grads += [gg[a:a + c], gb[a:a + c]]
@@ -852,11 +901,12 @@ class _FusedConv(torch.autograd.Function):
         if ctx.meta["relu"]:  # the ReLU ran in the convolution's epilogue: its mask is the sign of the stored output
             dy = torch.ops.aten.threshold_backward(dy, y, 0.0)  # dy where y > 0 else 0, one launch
         sc, sh = fold.scale_shift() if fold is not None else (None, None)
-        dw = db = dx = None
+        dw = db = dx = job = None
         fold_grads = [None] * ctx.meta["n_fold_params"]
         co_true = dy.shape[1]
         if co_true % _vec(_mode(dy.dtype)):  # 1-3 channels: one zero-padded copy serves the weight AND the data gradient
             dy, _ = _pad_out_channels(dy, None, spec, _vec(_mode(dy.dtype)))
+        want_dx = ctx.needs_input_grad[0] or any(ctx.needs_input_grad[4:])
         if ctx.needs_input_grad[1] or (ctx.meta["has_bias"] and ctx.needs_input_grad[2]):
             tw = _direct_target(weight)
             tb = _direct_target(ctx.meta["bias_param"]) if tw is not None and ctx.meta["has_bias"] else None
@@ -878,8 +928,14 @@ class _FusedConv(torch.autograd.Function):
                     side["keep"].append((x_raw, dy, sc, sh))
                     side["used"] = True
                 else:
+                    # Nothing reads dw before the optimizer: where a BatchNorm-backward finalize launch follows in THIS call (a fold
+                    # behind the data gradient), the slab reduction rides in it instead of taking a launch of its own on the chain.
+                    # The job (and the workspace it holds) never leaves this function.
+                    defer = _DEFER_WGRAD_REDUCE and dy.is_cuda and fold is not None and want_dx
                     res = conv_wgrad(x_raw, dy, tuple(weight.shape), spec, sc, sh, in_relu=fold.relu if fold is not None else False,
-                                     want_bias=ctx.meta["has_bias"], out_dw=tw, out_db=tb, co_true=co_true)
+                                     want_bias=ctx.meta["has_bias"], out_dw=tw, out_db=tb, co_true=co_true, defer_reduce=defer)
+                    if defer and res is not None:
+                        job, res = res[2], res[:2]
             if res is None:  # (none of the networks' layers; there is no library route for a device tensor)
                 raise NotImplementedError(f"liso_amd: no device weight-gradient kernel for {tuple(weight.shape)} stride {spec.stride} "
                                           f"on {tuple(x_raw.shape)} {x_raw.dtype}")
@@ -887,20 +943,24 @@ class _FusedConv(torch.autograd.Function):
                 dw, db = res
                 if tw is not None and dw is tw:  # written in place: nothing for autograd to accumulate
                     dw, db = None, None
-            if dw is not None:
-                dw = dw.to(weight.dtype)
-            if db is not None:
-                db = db.to(weight.dtype)
-        if ctx.needs_input_grad[0] or any(ctx.needs_input_grad[4:]):
-            g = None
-            if ctx.meta.get("occupancy") is not None and fold is None and co_true == dy.shape[1]:
-                g = _sparse_dgrad(dy, ctx.meta["occupancy"], weight, spec, tuple(x_raw.shape), x_raw.dtype, lists=ctx.meta.get("sparse_ws"))
-            if g is None:
-                g = conv_dgrad(dy, weight, spec, tuple(x_raw.shape))
-            if fold is not None:
-                dx, fold_grads = _bn_backward(g, x_raw, fold)
-            else:
-                dx = g
+        try:
+            if want_dx:
+                g = None
+                if ctx.meta.get("occupancy") is not None and fold is None and co_true == dy.shape[1]:
+                    g = _sparse_dgrad(dy, ctx.meta["occupancy"], weight, spec, tuple(x_raw.shape), x_raw.dtype, lists=ctx.meta.get("sparse_ws"))
+                if g is None:
+                    g = conv_dgrad(dy, weight, spec, tuple(x_raw.shape))
+                if fold is not None:
+                    dx, fold_grads = _bn_backward(g, x_raw, fold, job)
+                else:
+                    dx = g
+        finally:
+            if job is not None:
+                job.flush()  # (no finalize launch took it: the plain reduction)
+        if dw is not None:
+            dw = dw.to(weight.dtype)
+        if db is not None:
+            db = db.to(weight.dtype)
         return (dx, dw, db, None, *fold_grads)
 
 
