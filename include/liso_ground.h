@@ -1,0 +1,82 @@
+/*
+ * liso_ground.h -- C ABI of ground segmentation on the device: JCP range-image ground removal for a batch of sweeps, the cone
+ * test, and the order-preserving removal of the ground points, with no host synchronisation (graph-capturable).
+ *
+ * Replaces liso/jcp/jcp.py:253-384 (JPCGroundRemove: RangeProjection, RECM, 5x5 cross dilation, JCP),
+ * liso/datasets/torch_dataset_commons.py:133-144 (infer_ground_label_using_cone) and the point removal of :1165-1185.
+ *
+ * The result of liso_ground_jcp_f32 is defined as the reference's JPCGroundRemove applied to the float64 widening of the
+ * cloud: all projection, threshold and weight arithmetic is fp64 in the reference's operation order (the source file is
+ * compiled without FMA contraction), with the reference's quirks kept (its never-true bounds tests, last-writer-wins pixels,
+ * the transposed cloud_index_ read of the candidate filter, raster-order in-place JCP).
+ *
+ * Stages of liso_ground_jcp_f32, each one or two launches on the caller's stream:
+ *   0 init        workspace tables
+ *   1 elevation   per-point elevation, min / max of the finite ones per cloud (block reduction + ordered-integer atomics)
+ *   2 projection  point -> pixel: atomicMax of the winner index, ordered-key atomicMin of region_minz
+ *   3 recm        per-column scans of region_minz (one column per lane), per-pixel ground / obstacle
+ *   4 candidates  dilation + candidate filter, per-row candidate lists, the 24 JCP weights of every candidate
+ *   5 resolve     the sequential JCP pass as a skewed wavefront, one workgroup per cloud: the lane of row r resolves column
+ *                 t - 3r at step t; equal to the raster-order result bit for bit
+ *   6 gather      per-point label
+ *
+ * Conventions (as include/liso_det_nms.h): device pointers, caller-allocated outputs, no allocation, no host synchronisation;
+ * every entry point checks its arguments before it launches anything and returns LISO_OK, LISO_EINVAL, LISO_EWORKSPACE,
+ * LISO_ELAUNCH or LISO_GROUND_ELENGTH.  Clouds are rows of a [B, n_max, point_stride] fp32 array (x, y, z first); cloud b has
+ * counts[b] rows (counts == NULL: n_max each).  A row with a NaN coordinate is invalid: it is labelled 0 and takes no part.
+ */
+#ifndef LISO_GROUND_H
+#define LISO_GROUND_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "liso_iou3d.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define LISO_GROUND_ELENGTH (-4)          /* int(67 / delta_r) > 255: the reference's uint8 region image would wrap */
+#define LISO_GROUND_MAX_HEIGHT 1024       /* range-image rows: one lane per row in the resolve workgroup */
+#define LISO_GROUND_MAX_PIXELS (1 << 24)  /* width * height */
+#define LISO_GROUND_MAX_N (1 << 24)       /* rows per cloud */
+#define LISO_GROUND_LDS_BYTES (160 * 1024) /* label images up to this size are resolved in LDS, larger ones in global memory */
+#define LISO_GROUND_N_STAGES 7
+
+typedef struct {
+    int batch;            /* B >= 1 */
+    int n_max;            /* rows per cloud, >= 0 */
+    int point_stride;     /* floats per row, >= 3 */
+    int width;            /* range_img_width */
+    int height;           /* range_img_height, <= LISO_GROUND_MAX_HEIGHT; (height-1)*height + width-1 < width*height */
+    double sensor_height;
+    double delta_r;       /* > 0 */
+} liso_ground_cfg;
+
+/* bytes of device scratch liso_ground_jcp_f32 needs; 0 for a configuration it refuses. */
+size_t liso_ground_jcp_workspace_bytes(const liso_ground_cfg* cfg);
+
+/* pcl fp32 [B, n_max, point_stride]; counts int32 [B] or NULL -> is_ground uint8 [B, n_max] (1 = ground). */
+int liso_ground_jcp_f32(const liso_ground_cfg* cfg, const float* pcl, const int32_t* counts, uint8_t* is_ground, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* the stages [stage_begin, stage_end) only, on a workspace the earlier stages have filled (per-stage timing). */
+int liso_ground_jcp_stages_f32(const liso_ground_cfg* cfg, const float* pcl, const int32_t* counts, uint8_t* is_ground,
+                               void* workspace, size_t workspace_bytes, int stage_begin, int stage_end, void* stream);
+
+/* Cone test in fp64: out[b][i] = (or_with ? or_with[b][i] : 0) | (z < z_threshold + slope * sqrt(x*x + y*y)) for valid rows, 0 for
+ * the others.  slope = tan(cone angle), 0 for the flat test; or_with uint8 [B, n_max] or NULL; out may alias or_with. */
+int liso_ground_cone_f32(int batch, int n_max, int point_stride, const float* pcl, const int32_t* counts, double z_threshold,
+                         double slope, const uint8_t* or_with, uint8_t* out, void* stream);
+
+/* Order-preserving removal: the valid rows of cloud b with drop[b][i] == 0 move, in order, to the front of out[b]; the rows
+ * behind them are filled with NaN; out_counts[b] = number of kept rows.  pcl / out fp32 [B, n_max, point_stride]. */
+size_t liso_ground_compact_workspace_bytes(int batch, int n_max);
+int liso_ground_compact_f32(int batch, int n_max, int point_stride, const float* pcl, const int32_t* counts, const uint8_t* drop,
+                            float* out, int32_t* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* LISO_GROUND_H */

@@ -20,7 +20,7 @@ class LisoHipError(RuntimeError):
 
 
 _ERRORS = {-1: "LISO_EINVAL (bad pointer/size)", -2: "LISO_EWORKSPACE (workspace too small)",
-           -3: "LISO_ELAUNCH (HIP launch failed)"}
+           -3: "LISO_ELAUNCH (HIP launch failed)", -4: "LISO_GROUND_ELENGTH (int(67 / delta_R) > 255)"}
 
 
 def _preload_torch_hip_runtime():
@@ -300,6 +300,13 @@ SIGNATURES = {
     "liso_det_nms_order": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
     "liso_det_nms_select": (_i, [_i, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "liso_det_nms_gather": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    # include/liso_ground.h
+    "liso_ground_jcp_workspace_bytes": (_sz, [_vp]),
+    "liso_ground_jcp_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "liso_ground_jcp_stages_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "liso_ground_cone_f32": (_i, [_i, _i, _i, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]),
+    "liso_ground_compact_workspace_bytes": (_sz, [_i, _i]),
+    "liso_ground_compact_f32": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # include/liso_augment.h
     "liso_bev_free_mask_workspace_bytes": (_sz, [_i, _i]),
     "liso_bev_free_mask": (_i, [_vp, ctypes.c_long, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -410,6 +417,12 @@ class MineFilterCfg(ctypes.Structure):
 class DetGatherField(ctypes.Structure):
     """mirror of liso_det_gather_field (include/liso_det_nms.h)"""
     _fields_ = [("src", _vp), ("dst", _vp), ("row_elems", _i), ("elem_bytes", _i), ("pad_bits", ctypes.c_uint64)]
+
+
+class GroundCfg(ctypes.Structure):
+    """mirror of liso_ground_cfg (include/liso_ground.h)"""
+    _fields_ = [("batch", _i), ("n_max", _i), ("point_stride", _i), ("width", _i), ("height", _i),
+                ("sensor_height", ctypes.c_double), ("delta_r", ctypes.c_double)]
 
 
 class TargetsCfg(ctypes.Structure):

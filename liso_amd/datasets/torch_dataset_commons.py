@@ -93,3 +93,35 @@ def collate_list_data(samples):
     for k, v in list(out.items()):
         change_k_v(k, out, v)
     return out
+
+
+# ---- ground removal (reference :133-144 and :1165-1185) --------------------------------------------------------------------
+def infer_ground_label_using_cone(pcl, cone_z_threshold__m: float = -1.70, cone_angle__deg: float = 0.8):
+    """reference :133-144 -- a point is ground when it lies below a cone that rises with `cone_angle__deg` from
+    `cone_z_threshold__m` under the sensor.  numpy arrays take the reference's expression as it stands; device tensors
+    ([N,C] or [B,N,C] float32) go through liso_ground_cone_f32, CPU tensors through the same expression on their float64
+    widening: both evaluate in fp64, and label NaN rows False."""
+    assert 0.0 <= cone_angle__deg <= 10.0  # 10 deg arbitrary high value as sanity check
+    if torch.is_tensor(pcl):
+        if pcl.is_cuda:
+            from liso_amd.jcp.jcp import cone_device
+
+            return cone_device(pcl, cone_z_threshold__m, cone_angle__deg)
+        return torch.from_numpy(infer_ground_label_using_cone(pcl.double().numpy(), cone_z_threshold__m, cone_angle__deg))
+    if cone_angle__deg > 0.0:
+        cone_angle = cone_angle__deg / 180.0 * np.pi
+        d_xy = np.linalg.norm(pcl[..., 0:2], axis=-1)
+        z_t_thresh = cone_z_threshold__m + np.tan(cone_angle) * d_xy
+        is_ground = pcl[..., 2] < z_t_thresh
+    else:
+        is_ground = pcl[..., 2] < cone_z_threshold__m
+    return is_ground
+
+
+def remove_ground_points(pcl, *, range_img_width, range_img_height, sensor_height, delta_R, cone=(-1.70, 0.8), counts=None):
+    """the point removal of `remove_ground_points_from_sample` (reference :1165-1185) on the device:
+    (pcl_no_ground NaN-padded, counts, is_ground = JCP | cone); see liso_amd.jcp.jcp.remove_ground_points"""
+    from liso_amd.jcp.jcp import remove_ground_points as impl
+
+    return impl(pcl, range_img_width=range_img_width, range_img_height=range_img_height, sensor_height=sensor_height, delta_R=delta_R,
+                cone=cone, counts=counts)
