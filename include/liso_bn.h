@@ -49,13 +49,6 @@ int liso_bn_relu_bwd_strided(const void* dy, long dy_stride, const void* x, long
                              const float* stats, int training, int relu, void* dx, long dx_stride, float* grad_gamma, float* grad_beta,
                              void* workspace, size_t workspace_bytes, void* stream);
 
-/* The same backward in TWO launches instead of three: the last block of the reduction to finish also turns the partial sums into
- * grad_gamma / grad_beta / the dx coefficients.  `ticket`: one device-resident unsigned that is ZERO on entry and zero again on
- * return (the caller keeps one per BatchNorm layer, zeroed once; two calls in flight at the same time must not share it). */
-int liso_bn_relu_bwd_ticket(const void* dy, const void* x, int is_bf16, long m, int c, const float* gamma, const float* stats,
-                            int training, int relu, void* dx, float* grad_gamma, float* grad_beta, void* workspace,
-                            size_t workspace_bytes, unsigned* ticket, void* stream);
-
 /* liso_bn_relu_bwd / liso_bn_relu_bwd_strided (dy_stride = x_stride = dx_stride = 0: dense rows) whose finalize launch also carries the
  * blocks of a deferred weight-gradient slab reduction (include/liso_conv.h: liso_conv_wgrad_deferred): grid = the finalize's blocks
  * first, then the reduction's.  The two roles share the launch and nothing else -- no flag, fence or atomic between them; every block

@@ -246,61 +246,10 @@ __global__ __launch_bounds__(kThreads) void bn_apply_kernel(const T* __restrict_
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------
-// `ticket` != nullptr: the LAST block to finish (device-scope counter, left at zero again) also runs the finalize step below on
-// the partial sums of all blocks -- one launch less per layer (the separate finalize launch costs 5-6 us of stream time for < 1 us of
-// work); release / acquire fences at device scope make the other blocks' partial sums visible across the XCDs' L2 caches.
-// Partial sums that another block of the SAME launch reads: device-scope (write-through / L2-bypassing) relaxed atomics instead of
-// plain accesses + __threadfence() -- a device-scope release fence on this 8-XCD part writes back the whole L2 of the XCD (measured:
-// ~15 us per layer, 3x the launch it saves).
-__device__ __forceinline__ void st_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_agent(const float* p) {
-    return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-struct BwdFinal {
-    unsigned* ticket;
-    const float* gamma;
-    int training;
-    float *grad_gamma, *grad_beta, *coef;
-};
-
-__device__ __forceinline__ void bn_bwd_finalize_block(const float* partial, int nblk, long m, int c, const float* gamma,
-                                                      const float* stats, int training, float* grad_gamma, float* grad_beta,
-                                                      float* coef, double* sh_a, double* sh_b, int nthreads) {
-    const int tid = threadIdx.x;
-    const int chunks = nthreads / c > 0 ? nthreads / c : 1;
-    const int ch = tid % c, chunk = tid / c;
-    double a = 0.0, b = 0.0;
-    if (chunk < chunks) {
-        const int per = (nblk + chunks - 1) / chunks;
-        const int lo = chunk * per, hi = lo + per < nblk ? lo + per : nblk;
-        int q = lo;
-        for (; q + 8 <= hi; q += 8) {  // 16 independent loads in flight, original summation order
-            float va[8], vb[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) { va[j] = ld_agent(partial + (size_t)(q + j) * 2 * c + ch); vb[j] = ld_agent(partial + (size_t)(q + j) * 2 * c + c + ch); }
-#pragma unroll
-            for (int j = 0; j < 8; j++) { a += (double)va[j]; b += (double)vb[j]; }
-        }
-        for (; q < hi; q++) { a += (double)ld_agent(partial + (size_t)q * 2 * c + ch); b += (double)ld_agent(partial + (size_t)q * 2 * c + c + ch); }
-    }
-    sh_a[tid] = a; sh_b[tid] = b;
-    __syncthreads();
-    if (tid < c) {
-        a = 0.0; b = 0.0;
-        for (int q = 0; q < chunks; q++) { a += sh_a[q * c + tid]; b += sh_b[q * c + tid]; }
-        grad_beta[tid] = (float)a;
-        grad_gamma[tid] = (float)b;
-        coef[tid] = gamma[tid] * stats[3 * c + tid];
-        coef[c + tid] = training ? (float)(a / (double)m) : 0.f;
-        coef[2 * c + tid] = training ? (float)(b / (double)m) : 0.f;
-    }
-}
-
 template <typename T, bool RELU>
 __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restrict__ x, long m,
                                                                  int c, Geom g, const float* __restrict__ stats,
-                                                                 float* partial, BwdFinal fin) {
+                                                                 float* partial) {
     constexpr int V = Vec<T>::V;
     __shared__ float s_a[kThreads][V + 1];
     __shared__ float s_b[kThreads][V + 1];
@@ -338,39 +287,9 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
         float sa = 0.f, sb = 0.f;
         for (int q = 0; q < g.rl; q++) { sa += s_a[q * g.cg + col2][j2]; sb += s_b[q * g.cg + col2][j2]; }
         float* p = partial + (size_t)blockIdx.x * 2 * c;
-        if (fin.ticket == nullptr) {
-            p[tid] = sa;
-            p[c + tid] = sb;
-        } else {
-            st_agent(p + tid, sa);
-            st_agent(p + c + tid, sb);
-        }
+        p[tid] = sa;
+        p[c + tid] = sb;
     }
-    if (fin.ticket == nullptr) return;
-    __shared__ int s_last;
-    // Hand-off to the last block (MI355X_MICROARCH.md "Correctness boundaries", inter-workgroup visibility): every storing wave drains
-    // its stores (vmcnt(0)), the block's barrier, ONE lane's agent-scope release in front of the ticket, and in the last block an
-    // agent-scope acquire behind it (one lane, then the barrier) before the plain loads of the other blocks' partial sums.  Round 4 had
-    // a workgroup-scope fence and a relaxed ticket here: neither orders the other waves' stores for another CU / XCD.
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    __syncthreads();
-    if (tid == 0) {
-        unsigned* tk = fin.ticket + blockIdx.y;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        s_last = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-        if (s_last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (zero again for the next call)
-        }
-    }
-    __syncthreads();
-    if (!s_last) return;
-    double* sh_a = reinterpret_cast<double*>(&s_a[0][0]);  // (kThreads x (V + 1) floats >= kThreads doubles for V >= 1 ... V = 4 | 8)
-    double* sh_b = reinterpret_cast<double*>(&s_b[0][0]);
-    __syncthreads();
-    bn_bwd_finalize_block(partial, gridDim.x, m, c, fin.gamma, stats, fin.training,
-                          fin.grad_gamma + (size_t)blockIdx.y * c, fin.grad_beta + (size_t)blockIdx.y * c,
-                          fin.coef + (size_t)blockIdx.y * 3 * c, sh_a, sh_b, kThreads);
 }
 
 // sums -> grad_beta, grad_gamma and the three dx coefficients per channel (chain_bodies.h: bn_bwd_finalize_segment)
@@ -546,7 +465,7 @@ int liso_bn_relu_fwd(const void* x, int is_bf16, long m, int c, const float* gam
 
 static int bn_relu_bwd(const void* dy, const void* x, int is_bf16, long m, int c, const float* gamma, const float* stats,
                        int training, int relu, void* dx, float* grad_gamma, float* grad_beta, void* workspace,
-                       size_t workspace_bytes, unsigned* ticket, void* stream, long dy_stride = 0, long x_stride = 0, long dx_stride = 0,
+                       size_t workspace_bytes, void* stream, long dy_stride = 0, long x_stride = 0, long dx_stride = 0,
                        const liso_wgrad_reduce_job* job = nullptr) {
     Geom g;
     int nblk;
@@ -563,7 +482,6 @@ static int bn_relu_bwd(const void* dy, const void* x, int is_bf16, long m, int c
     float* partial = (float*)workspace;
     float* coef = partial + (size_t)kMaxBlocks * 2 * c;
     const int grid = stream_grid(m, g);
-    const BwdFinal fin{ticket, gamma, training, grad_gamma, grad_beta, coef};
     const int cw = finalize_segment(c, nblk);
     const liso_chain::BnBwdFinalizeArgs fa{partial, nblk, m, c, cw, gamma, stats, training, grad_gamma, grad_beta, coef};
     const int n_fin = c / cw;
@@ -571,12 +489,12 @@ static int bn_relu_bwd(const void* dy, const void* x, int is_bf16, long m, int c
     const unsigned grid_fr = (unsigned)(n_fin + (n_red + 3) / 4);
 #define LISO_BWD(T, R)                                                                                                     \
     do {                                                                                                                   \
-        bn_bwd_reduce_kernel<T, R><<<nblk, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial, fin);     \
+        bn_bwd_reduce_kernel<T, R><<<nblk, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial);          \
         if (job && job->splits > 16)                                                                                       \
             bn_bwd_finalize_reduce_kernel<16><<<grid_fr, 1024, 0, st>>>(fa, n_fin, *job, n_red);                           \
         else if (job)                                                                                                      \
             bn_bwd_finalize_reduce_kernel<1><<<grid_fr, 1024, 0, st>>>(fa, n_fin, *job, n_red);                            \
-        else if (!ticket)                                                                                                  \
+        else                                                                                                               \
             bn_bwd_finalize_kernel<<<dim3(1, c / cw), 1024, 0, st>>>(fa);                                                  \
         bn_bwd_dx_kernel<T, R><<<grid, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, coef, (T*)dx);          \
     } while (0)
@@ -591,7 +509,7 @@ int liso_bn_relu_bwd(const void* dy, const void* x, int is_bf16, long m, int c, 
                      int training, int relu, void* dx, float* grad_gamma, float* grad_beta, void* workspace,
                      size_t workspace_bytes, void* stream) {
     return bn_relu_bwd(dy, x, is_bf16, m, c, gamma, stats, training, relu, dx, grad_gamma, grad_beta, workspace, workspace_bytes,
-                       nullptr, stream);
+                       stream);
 }
 
 int liso_bn_relu_bwd_strided(const void* dy, long dy_stride, const void* x, long x_stride, int is_bf16, long m, int c, const float* gamma,
@@ -599,15 +517,7 @@ int liso_bn_relu_bwd_strided(const void* dy, long dy_stride, const void* x, long
                              void* workspace, size_t workspace_bytes, void* stream) {
     if (dy_stride <= 0 || x_stride <= 0 || dx_stride <= 0) return LISO_EINVAL;
     return bn_relu_bwd(dy, x, is_bf16, m, c, gamma, stats, training, relu, dx, grad_gamma, grad_beta, workspace, workspace_bytes,
-                       nullptr, stream, dy_stride, x_stride, dx_stride);
-}
-
-int liso_bn_relu_bwd_ticket(const void* dy, const void* x, int is_bf16, long m, int c, const float* gamma, const float* stats,
-                            int training, int relu, void* dx, float* grad_gamma, float* grad_beta, void* workspace,
-                            size_t workspace_bytes, unsigned* ticket, void* stream) {
-    if (!ticket) return LISO_EINVAL;
-    return bn_relu_bwd(dy, x, is_bf16, m, c, gamma, stats, training, relu, dx, grad_gamma, grad_beta, workspace, workspace_bytes,
-                       ticket, stream);
+                       stream, dy_stride, x_stride, dx_stride);
 }
 
 int liso_bn_relu_bwd_chained(const void* dy, long dy_stride, const void* x, long x_stride, int is_bf16, long m, int c, const float* gamma,
@@ -617,7 +527,7 @@ int liso_bn_relu_bwd_chained(const void* dy, long dy_stride, const void* x, long
         return LISO_EINVAL;
     if (job && !liso_chain::wgrad_reduce_job_ok(job)) return LISO_EINVAL;
     return bn_relu_bwd(dy, x, is_bf16, m, c, gamma, stats, training, relu, dx, grad_gamma, grad_beta, workspace, workspace_bytes,
-                       nullptr, stream, dy_stride, x_stride, dx_stride, job);
+                       stream, dy_stride, x_stride, dx_stride, job);
 }
 
 size_t liso_in_workspace_bytes(int groups, int c) {
@@ -664,7 +574,7 @@ static int in_relu_bwd(const void* dy, const void* x, int is_bf16, int groups, l
     const liso_chain::BnBwdFinalizeArgs fa{partial, nblk, m, c, cw, gamma, stats, 1, grad_gamma, grad_beta, coef};
 #define LISO_BWD(T, R)                                                                                                     \
     do {                                                                                                                   \
-        bn_bwd_reduce_kernel<T, R><<<gs, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial, BwdFinal{}); \
+        bn_bwd_reduce_kernel<T, R><<<gs, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial); \
         if (summed)                                                                                                        \
             in_bwd_finalize_sum_kernel<<<1, 1024, 0, st>>>(partial, groups, nblk, m, c, gamma, stats, grad_gamma, grad_beta, coef); \
         else                                                                                                               \

@@ -1887,10 +1887,6 @@ int liso_conv_forward_sparse(const liso_conv_desc* d, const void* x, const void*
     if (x3 && p.sk == 2)
         return p.cs == 32 ? launch<LISO_CONV_F32X3, 1, 1, true, 32, 2>(*d, p, st) : launch<LISO_CONV_F32X3, 1, 1, true, 16, 2>(*d, p, st);
     if (f32) LISO_SEL(LISO_CONV_F32, true, 32, 16);
-    if (x3 && p.nj == 3) {
-        if (p.mi == 2) LISO_GO(LISO_CONV_F32X3, 2, 3, true, 32, 16);
-        LISO_GO(LISO_CONV_F32X3, 1, 3, true, 32, 16);
-    }
     if (x3) LISO_SEL(LISO_CONV_F32X3, true, 32, 16);
     if (h16 && of32) LISO_SEL(LISO_CONV_F16, true, 64, 32);
     if (h16) LISO_SEL(LISO_CONV_F16, false, 64, 32);

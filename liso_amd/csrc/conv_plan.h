@@ -32,7 +32,6 @@ struct FwdArgs {
     int slab_pipelined; // one register batch holds a whole slab (tile + the panels of all taps): what the SK = 2 kernel needs
     int group_bytes;    // LDS bytes of one split-K group's tile + panels (SK = 2 instantiations)
     const float* occ;   // optional [batch, hi, wi]: 0 = the input pixel is exactly zero in every channel (sparse BEV canvases)
-    int dbg;            // (unused: experiment switches of removed kernels)
     int roles;          // conv_roles_kernel (loader waves + MFMA waves, double-buffered LDS): 3x3 / 1x1, stride 1, one class
     int wide_out;       // roles: 16-byte output stores through an LDS patch (channel count and strides allow them)
     unsigned long long roles_tapw;  // roles: 4 bits per window position (ty * 3 + tx): the tap's index inside the packed weights
@@ -79,9 +78,8 @@ void plan_roles(const liso_conv_desc& d, Plan* p) {
     if (seen != 0x1ff) return;
     const int cs = x3 ? 16 : 32, ks = cs / 16, nslab = (d.ci + cs - 1) / cs;
     // (round 5, before the blocks became persistent: shallow layers -- 2 slabs -- lost to conv_igemm_kernel, 76 vs 67 us on 32 -> 32 at
-    // 8 x 256^2; with the next tile staged under the epilogue: 58 vs 65 us.  LISO_ROLES_MIN_SLABS: experiments)
-    static const int min_slabs = getenv("LISO_ROLES_MIN_SLABS") ? atoi(getenv("LISO_ROLES_MIN_SLABS")) : 1;
-    if (nslab < min_slabs || nslab < 2) return;  // (one slab per tile: the deferred statistics flush would race with the next epilogue)
+    // 8 x 256^2; with the next tile staged under the epilogue: 58 vs 65 us)
+    if (nslab < 2) return;  // (one slab per tile: the deferred statistics flush would race with the next epilogue)
     static const int force_mi = getenv("LISO_ROLES_MI") ? atoi(getenv("LISO_ROLES_MI")) : 0;
     static const int force_nj = getenv("LISO_ROLES_NJ") ? atoi(getenv("LISO_ROLES_NJ")) : 0;
     double best = 1e300;
@@ -121,8 +119,7 @@ void plan_roles(const liso_conv_desc& d, Plan* p) {
     p->lds = 4096 + 2 * buf + 4 * 2048;  // (+ the epilogue's 2-KB patch per MFMA wave)
     const bool of32 = x3 || d.out_f32;
     const int cv = of32 ? 4 : 8;  // channels per 16-byte store
-    static const int wide_env = getenv("LISO_ROLES_WIDE") ? atoi(getenv("LISO_ROLES_WIDE")) : 1;
-    a.wide_out = (wide_env && d.co % cv == 0 && d.y_pix_stride % cv == 0 && d.y_ch_off % cv == 0) ? 1 : 0;
+    a.wide_out = (d.co % cv == 0 && d.y_pix_stride % cv == 0 && d.y_ch_off % cv == 0) ? 1 : 0;
 }
 
 // panel width (in 32-filter tiles) of the direct kernels: the fewest (blocks per pixel tile) x (per-step cost ~ 2 + nj): 128 filters as
@@ -146,8 +143,7 @@ inline int direct_panel_width(int co) {
 void plan_1x1(const liso_conv_desc& d, Plan* p) {
     FwdArgs& a = p->a;
     a.direct1x1 = 0;
-    static const int env = getenv("LISO_CONV_1X1") ? atoi(getenv("LISO_CONV_1X1")) : 1;
-    if (!env || (d.mode != LISO_CONV_F32X3 && d.mode != LISO_CONV_BF16)) return;
+    if (d.mode != LISO_CONV_F32X3 && d.mode != LISO_CONV_BF16) return;
     if (d.n_classes > 1) {  // tap classes: transposed convolutions with kernel = stride -- one tap per class (tap index = class index)
         if (d.n_taps != d.n_classes) return;
         for (int c = 0; c < d.n_classes; c++)
@@ -157,8 +153,7 @@ void plan_1x1(const liso_conv_desc& d, Plan* p) {
     }
     // (the kernel walks any tap list; measured on the heads' 256 -> 6 output layer, 3x3 at 4 x 64 x 64: 47.7 us against 21.2 us on
     // conv_roles_kernel -- re-reading the pixels per tap through L1, 32 lines per load instruction, costs more than staging the tile
-    // once even for a single 32-filter panel.  LISO_CONV_1X1=3 selects it for <= 16 filters on >= 64 channels: experiments)
-    const bool narrow = env == 3 && d.mode == LISO_CONV_F32X3 && d.n_classes == 1 && d.n_taps >= 2 && d.n_taps <= 9 && d.co <= 16 && d.ci >= 64;
+    // once even for a single 32-filter panel: such layers stay off this kernel)
     // kernel = stride (the k = 2 / stride-2 deblock, rpn.py:70-104): the taps tile the input without overlap -- every input pixel is read
     // by exactly one tap, nothing is re-read: a 1x1 problem on s * s * ci channels
     bool cell = d.n_classes == 1 && d.n_taps > 1 && d.n_taps == d.isy * d.isx;
@@ -172,15 +167,12 @@ void plan_1x1(const liso_conv_desc& d, Plan* p) {
     }
     // 3x3 / stride-2 layers on pixels of <= 256 bytes (64 fp32 / 128 bf16 channels): every input pixel is read by 2.25 taps on average,
     // its lines stay in L1 between them -- measured on the encoders' four such layers (4 pairs): 141 -> 105 us against conv_igemm_kernel
-    // (LISO_CONV_1X1=2: one tap only)
-    const bool strided = env != 2 && d.n_classes == 1 && d.n_taps == 9 && d.isy == 2 && d.isx == 2 && d.ci > 8 &&  // (<= 8: conv_taps_kernel)
+    const bool strided = d.n_classes == 1 && d.n_taps == 9 && d.isy == 2 && d.isx == 2 && d.ci > 8 &&  // (<= 8: conv_taps_kernel)
                          d.ci * (d.mode == LISO_CONV_F32X3 ? 4 : 2) <= 256;
-    // (experiment, LISO_CONV_1X1=5: 3x3 / stride-1 layers on pixels of <= 128 bytes -- 32 fp32 channels, the encoders' first stage: 9
-    // reads per pixel through L1.  Measured 114 vs 63.7 us (8 x 256^2) and 47.7 vs 29.9 us (4 x 256^2) against conv_roles_kernel: off)
-    const bool small_px = env == 5 && d.n_classes == 1 && d.n_taps == 9 && d.isy == 1 && d.isx == 1 && d.ci > 8 &&
-                          d.ci * (d.mode == LISO_CONV_F32X3 ? 4 : 2) <= 128;
-    if (d.n_classes == 1 && d.n_taps != 1 && !narrow && !cell && !strided && !small_px) return;
-    if (a.roles && !narrow && !small_px) return;
+    // (3x3 / stride-1 layers on pixels of <= 128 bytes -- 32 fp32 channels, the encoders' first stage: 9 reads per pixel through L1.
+    // Measured 114 vs 63.7 us (8 x 256^2) and 47.7 vs 29.9 us (4 x 256^2) against conv_roles_kernel: they stay there)
+    if (d.n_classes == 1 && d.n_taps != 1 && !cell && !strided) return;
+    if (a.roles) return;
     for (int t = 0; t < d.n_taps; t++)
         if (d.tap_w[t] < 0 || d.tap_w[t] >= d.w_taps) return;
     if (d.in_affine_batch_stride & 3) return;
@@ -206,8 +198,7 @@ void plan_1x1(const liso_conv_desc& d, Plan* p) {
 void plan_taps(const liso_conv_desc& d, Plan* p) {
     FwdArgs& a = p->a;
     a.direct_taps = 0;
-    static const int env = getenv("LISO_CONV_TAPS") ? atoi(getenv("LISO_CONV_TAPS")) : 1;
-    if (!env || a.roles || a.direct1x1 || d.mode != LISO_CONV_F32X3 || d.n_classes != 1 || d.n_taps < 2 || d.ci > 8 || d.osy != 1 || d.osx != 1)
+    if (a.roles || a.direct1x1 || d.mode != LISO_CONV_F32X3 || d.n_classes != 1 || d.n_taps < 2 || d.ci > 8 || d.osy != 1 || d.osx != 1)
         return;
     if (d.in_affine_batch_stride & 3) return;
     for (int t = 0; t < d.n_taps; t++)
@@ -249,27 +240,9 @@ bool make_plan(const liso_conv_desc& d, Plan* p) {
         // without a block -> 32-channel panels double the block count (the tile is re-staged from L2 by twice as many blocks)
         const long tiles4 = (long)d.n_classes * d.batch * ((d.hv + 3) / 4) * ((d.wv + 31) / 32);
         if (p->nj == 2 && tiles4 * ((d.co + 63) / 64) < 160) p->nj = 1;
-        if (p->nj == 2 && x3) {
-            // F32X3 launches of a few hundred blocks are bound by the MFMA stream of the busiest CU: blocks per CU x work per block.
-            // 64-channel panels on 384 blocks (ConvGRU z|r, 4 pairs: 128 tiles x 3 panels) give half the CUs two blocks of work 2;
-            // 32-channel panels give every CU three blocks of work 1 (+ the tile staged twice as often: charged as 0.3 per block)
-            const long b2 = tiles4 * ((d.co + 63) / 64), b1 = tiles4 * ((d.co + 31) / 32);
-            const double c2 = (double)((b2 + 255) / 256) * 2.3, c1 = (double)((b1 + 255) / 256) * 1.3;
-            // MEASURED (round 4): no gain in the loop (5.70 vs 5.69 ms), SLIM train step slower (15.5 vs 14.9 ms): off unless asked for
-            static const bool auto_nj = getenv("LISO_CONV_NJ_AUTO") != nullptr && atoi(getenv("LISO_CONV_NJ_AUTO")) != 0;
-            if (auto_nj && b1 <= 2048 && c1 < c2) p->nj = 1;
-        }
-        // F32X3 layers with 65-96 filters (ConvGRU q 304->96, the motion encoder's 160->80, the encoders' 96->96 stage): one 96-wide
-        // panel instead of two 64-wide ones -- no padded filter columns through the matrix cores (96 -> 128: a quarter of the MFMAs,
-        // 80 -> 128: three eighths) and the input tile staged once
-        // MEASURED (round 4): correct on every test, no gain -- loop 5.10 vs 5.10 ms, SLIM step 13.99 vs 13.88 ms (the 96-wide panel
-        // leaves room for 3 instead of 5 taps per weight stage in the 79-KB plans).  Off unless LISO_CONV_NJ3=1.
-        static const bool nj3 = getenv("LISO_CONV_NJ3") != nullptr && atoi(getenv("LISO_CONV_NJ3")) != 0;
-        if (nj3 && x3 && p->nj == 2 && d.co > 64 && d.co <= 96) p->nj = 3;
-        if (const char* e = getenv("LISO_CONV_NJ")) {  // experiments: 1 | 2 force the panel width
-            if (atoi(e) == 1) p->nj = 1;
-            if (atoi(e) == 2 && d.co > 32) p->nj = 2;
-        }
+        // MEASURED (round 4), both without gain and not kept: 32-filter panels for F32X3 launches of a few hundred blocks (loop 5.70 vs
+        // 5.69 ms, SLIM train step 15.5 vs 14.9 ms), and one 96-wide panel for F32X3 layers with 65-96 filters (loop 5.10 vs 5.10 ms,
+        // SLIM step 13.99 vs 13.88 ms: the wide panel leaves room for 3 instead of 5 taps per weight stage in the 79-KB plans)
     }
     const int bnt = 32 * p->nj;
     a.n_nt = (d.co + bnt - 1) / bnt;
@@ -306,20 +279,14 @@ bool make_plan(const liso_conv_desc& d, Plan* p) {
     // 8-row tiles only when they still give every CU 2 blocks.
     int mi_first = blocks(8) >= 512 ? 2 : 1;
     if (const char* e = getenv("LISO_CONV_MI")) mi_first = atoi(e) == 2 ? 2 : atoi(e) == 1 ? 1 : mi_first;  // experiments
-    int cs_opts[2] = {fin ? 32 : 64, fin ? 16 : 32};
-    if (const char* e = getenv("LISO_CONV_CS")) {  // experiments: force the slab width (bf16: 64 | 32; fp32 tensors: 32 | 16)
-        const int v = atoi(e);
-        if (v == cs_opts[0] || v == cs_opts[1]) cs_opts[0] = cs_opts[1] = v;
-    }
+    const int cs_opts[2] = {fin ? 32 : 64, fin ? 16 : 32};
     long best = -1;
     // at most one block per CU anyway: spend its whole LDS -- unless other streams' kernels share the GPU (the LISO loop's three
     // pipeline stages): a block that owns all 160 KB keeps every other kernel's blocks off its CU while its own 4 waves mostly wait
     // (loop, 60 steps: 6.16 -> 6.04 ms per step with the 79-KB plans)
-    bool few_blocks = !g_shared_gpu && blocks(4 * mi_first) <= 256;
-    if (const char* e = getenv("LISO_CONV_FEW")) few_blocks = few_blocks && atoi(e) != 0;  // experiments
+    const bool few_blocks = !g_shared_gpu && blocks(4 * mi_first) <= 256;
     for (int pass = 0; pass < 2 && best < 0; pass++) {
-        int cap = (pass == 0 && !few_blocks ? 79 : 158) * 1024;
-        if (const char* e = getenv("LISO_CONV_LDS_KB")) { if (pass == 0 && atoi(e) >= 16) cap = atoi(e) * 1024; }  // experiments
+        const int cap = (pass == 0 && !few_blocks ? 79 : 158) * 1024;
         for (int mi = mi_first; mi >= 1; mi--) {
             int inh[LISO_CONV_MAX_CLASSES], inw[LISO_CONV_MAX_CLASSES], y0s[LISO_CONV_MAX_CLASSES], x0s[LISO_CONV_MAX_CLASSES];
             const int max_pix = tile_pixels(4 * mi, inh, inw, y0s, x0s);
@@ -368,11 +335,6 @@ bool make_plan(const liso_conv_desc& d, Plan* p) {
         g_pipe = g_pipe > p->g ? p->g : g_pipe;
         a.slab_pipelined = (p->g >= max_taps && x_chunks <= 12 && w_chunks <= 10) ? 1 : 0;  // (round 4's condition: the SK = 2 kernel needs it)
         a.pipelined = (x_chunks <= 12 && g_pipe >= 1) ? 1 : 0;
-        if (const char* e = getenv("LISO_CONV_PIPE")) {  // experiments: 0 = never, 1 = round 4's whole-slab condition, 2 = stage-granular (default)
-            const int v = atoi(e);
-            if (v == 0) a.pipelined = 0;
-            if (v == 1) a.pipelined = a.slab_pipelined;
-        }
         if (a.pipelined && !(a.slab_pipelined && p->g >= max_taps)) {
             p->g = g_pipe;
             a.g_taps = g_pipe;
@@ -390,7 +352,6 @@ bool make_plan(const liso_conv_desc& d, Plan* p) {
     if (x3 && a.slab_pipelined && p->mi == 1 && p->nj == 1 && a.total <= 256 && d.ci > p->cs && 512 + 2 * a.group_bytes <= 160 * 1024 &&
         a.group_bytes >= 16 * kThreads * 4)
         p->sk = 2;
-    if (const char* e = getenv("LISO_CONV_SK")) p->sk = (atoi(e) >= 2 && p->sk == 2) ? 2 : 1;  // experiments
     if (p->sk == 2) p->lds = 512 + 2 * a.group_bytes;
     // (rounds 3-4 kept an 8-wave variant with LDS-DMA weight stages, conv_igemm8_kernel, behind LISO_CONV_A8: correct, never faster
     // than this kernel -- one block per CU, every wave both loads and multiplies; round 5's conv_roles_kernel is the role-split form

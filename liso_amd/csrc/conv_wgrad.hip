@@ -1001,18 +1001,14 @@ bool make_plan_impl(const liso_conv_desc& d, WgPlan* p, bool compact) {
         return n;
     };
     const long slab_per_split = (long)d.w_taps * a.ci_t * CT * a.co_t * CT * sizeof(float);
-    long slab_mb = 24;
-    if (const char* e = getenv("LISO_WGRAD_SLAB_MB")) slab_mb = atol(e) > 0 ? atol(e) : slab_mb;  // experiments
-    long split_cap = (slab_mb << 20) / slab_per_split;
+    long split_cap = (24l << 20) / slab_per_split;
     // tiles per block at least (the first tile's load is exposed).  fp32 tensors: 2 -- the SLIM encoders' 1x1 / strided layers have 256
     // tiles in all: at 4 per block 64 of the 256 CUs worked, each through four unpipelined load -> multiply rounds (28 us per launch);
     // measured on the SLIM train step: weight-gradient family 2.10-2.13 -> 2.00-2.05 ms (1 tile per block: no better, 4x the slabs)
-    long min_tiles = x3 ? 2 : 4;
-    if (const char* e = getenv("LISO_WGRAD_MIN_TILES")) min_tiles = atol(e) > 0 ? atol(e) : min_tiles;  // experiments
+    const long min_tiles = x3 ? 2 : 4;
     const long by_tiles = a.n_tiles >= min_tiles ? a.n_tiles / min_tiles : 1;
     split_cap = split_cap < 1 ? 1 : (split_cap > by_tiles ? by_tiles : split_cap);
-    long target = 512;  // ~2 blocks per CU
-    if (const char* e = getenv("LISO_WGRAD_BLOCKS")) target = atol(e) > 0 ? atol(e) : target;  // experiments
+    const long target = 512;  // ~2 blocks per CU
     // 7 x 7 kernels (the SLIM encoders' stem, the motion encoder's flow / class convolutions): one kernel ROW of 7 taps per block
     const bool rows7 = max_cls_taps == 49 && d.n_classes == 1;
     const int tg_opts[3] = {rows7 ? 7 : 9, rows7 ? 1 : 3, 1};
@@ -1035,14 +1031,9 @@ bool make_plan_impl(const liso_conv_desc& d, WgPlan* p, bool compact) {
             p->tg = tg;
         }
     }
-    if (const char* e = getenv("LISO_WGRAD_TG")) {  // experiments: force the tap group (9 / 3 / 1)
-        const int v = atoi(e);
-        if ((v == 9 && !x3 && !compact && !rows7) || (v == 3 && !rows7) || v == 1 || (v == 7 && rows7)) p->tg = v;
-    }
     {
         const int xb = p->tg >= 9 ? 4 : 8;
         a.pipelined = (!x3 && max_pix <= xb * (kThreads / 8)) ? 1 : 0;
-        if (const char* e = getenv("LISO_WGRAD_PIPE")) a.pipelined = a.pipelined && atoi(e) != 0;  // experiments
     }
     a.n_groups = 0;
     for (int c = 0; c < d.n_classes; c++)
@@ -1071,9 +1062,7 @@ bool make_plan_impl(const liso_conv_desc& d, WgPlan* p, bool compact) {
 // Strided convolutions (the backbone's three stride-2 layers): a tap group of one kernel row reads every isy-th input row only --
 // its tile then holds those rows alone (2.5x fewer staged pixels for 3x3 / 2, and twice the output rows per tile in the same LDS).
 bool make_plan(const liso_conv_desc& d, WgPlan* p) {
-    bool want = d.isy > 1;
-    if (const char* e = getenv("LISO_WGRAD_COMPACT")) want = want && atoi(e) != 0;  // experiments
-    if (want && make_plan_impl(d, p, true)) return true;
+    if (d.isy > 1 && make_plan_impl(d, p, true)) return true;
     return make_plan_impl(d, p, false);
 }
 
@@ -1314,8 +1303,6 @@ struct Rs3Plan {
 };
 
 bool make_rs3_plan(const liso_conv_desc& d, Rs3Plan* p) {
-    if (const char* e = getenv("LISO_WGRAD_RS3"))  // experiments / A-B runs: 0 = the generic kernel everywhere
-        if (atoi(e) == 0) return false;
     if (d.mode == LISO_CONV_F16) {
         liso_conv_desc e = d;
         e.mode = LISO_CONV_BF16;
@@ -1326,7 +1313,7 @@ bool make_rs3_plan(const liso_conv_desc& d, Rs3Plan* p) {
     const int vec = x3 ? 4 : 8;
     const int S = d.isy;  // 3x3, padding 1, stride 1 or 2 (stride 2: bf16 only -- two buffers of two planes would not fit)
     if ((S != 1 && S != 2) || d.isx != S || d.osy != 1 || d.osx != 1 || d.in_affine_batch_stride != 0) return false;
-    if (S == 2 && (x3 || getenv("LISO_WGRAD_RS3_S2_OFF"))) return false;
+    if (S == 2 && x3) return false;
     if (d.hv != d.ho || d.wv != d.wo || d.ho != (d.hi - 1) / S + 1 || d.wo != (d.wi - 1) / S + 1 || d.batch <= 0) return false;
     if (d.ci % vec || d.co % vec || d.x_pix_stride % vec || d.class_tap_begin[0] != 0 || d.class_tap_begin[1] != 9) return false;
     for (int t = 0; t < 9; t++)
@@ -1336,28 +1323,24 @@ bool make_rs3_plan(const liso_conv_desc& d, Rs3Plan* p) {
     // 32 (the SLIM encoders' first stage: 42.4 -> 38.5 us).  Measured (scripts/wgrad_time.py, wgrad + reduction): bf16 4 x 128 -> 128 at
     // 128^2 39.3 -> 49.1 us, B = 2 32.3 -> 45.9, 64 -> 64 at 256^2 39.4 -> 48.5, 256 -> 256 at 64^2 40.8 -> 51.1; fp32 64 -> 64 35.7 ->
     // 37.3, 304 -> 192 x 12 maps 192.7 -> 227.8: a wave that multiplies one column half per tile row pays the tile's barrier and the
-    // priming of its row-stationary fragments for half the products -- the slab bytes it saves are worth less.  LISO_WGRAD_CIW: experiments
+    // priming of its row-stationary fragments for half the products -- the slab bytes it saves are worth less.
     a.ci_w = (S == 1 && d.ci <= 32) ? 32 : CT;
-    if (const char* e = getenv("LISO_WGRAD_CIW")) a.ci_w = (atoi(e) == 32 && S == 1) ? 32 : CT;
     a.ci_t = (d.ci + a.ci_w - 1) / a.ci_w;
     a.co_t = (d.co + CT - 1) / CT;
     const long cc = (long)a.ci_t * a.co_t;
     long want = 256 / cc;  // one block per CU
-    if (const char* e = getenv("LISO_WGRAD_BLOCKS")) want = (atol(e) > 0 ? atol(e) : 256) / cc;  // experiments
     want = want < 1 ? 1 : want;
     a.tiles_x = (d.wo + TW - 1) / TW;
     const long tiles8 = (long)d.batch * ((d.ho + 7) / 8) * a.tiles_x;
     int th = tiles8 >= 4 * want ? 8 : 4;
-    if (const char* e = getenv("LISO_WGRAD_TH")) th = atoi(e) == 8 ? 8 : atoi(e) == 4 ? 4 : th;  // experiments
     if (x3 || S == 2) th = 3;  // (two planes per operand / the (2 TH + 1) x 65 halo of stride 2: two buffers of a 3-row tile fit the LDS)
     p->stride = S;
     a.th = th;
     a.tiles_y = (d.ho + th - 1) / th;
     a.n_tiles = d.batch * a.tiles_y * a.tiles_x;
-    long min_tiles = 4;  // >= 4 tiles per block: the first tile's load is exposed, the others hide behind MFMAs
-    // (experiments; 2 tiles per block on the SLIM encoders' 64 -> 64 / 96 -> 96 layers -- 172 blocks instead of 86 -- measured no change:
+    const long min_tiles = 4;  // >= 4 tiles per block: the first tile's load is exposed, the others hide behind MFMAs
+    // (2 tiles per block on the SLIM encoders' 64 -> 64 / 96 -> 96 layers -- 172 blocks instead of 86 -- measured no change:
     // SLIM step 10.81-11.06 vs 10.66-11.05 ms, twice the slabs)
-    if (const char* e = getenv("LISO_WGRAD_RS3_MIN_TILES")) min_tiles = atol(e) > 0 ? atol(e) : min_tiles;
     long s = a.n_tiles / min_tiles;
     s = s > want ? want : s;
     s = s < 1 ? 1 : s;

@@ -496,8 +496,7 @@ int liso_dbscan_components(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_ma
     const unsigned blocks = (unsigned)((total + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
     dbscan_core_kernel<<<blocks, 256, 0, st>>>(c, dynamic_mask, row_coords, col_coords, flow, core, parent);
-    static const bool flat_union = getenv("LISO_DBSCAN_FLAT_UNION") != nullptr && atoi(getenv("LISO_DBSCAN_FLAT_UNION")) != 0;
-    if (c.win <= kMaxWin && !flat_union) {
+    if (c.win <= kMaxWin) {
         const int tiles_r = (c.gx + kTR - 1) / kTR, tiles_c = (c.gy + kTC - 1) / kTC;
         dbscan_union_tiled_kernel<<<dim3(tiles_r * tiles_c, c.batch), kUfThreads, 0, st>>>(c, dynamic_mask, core, row_coords, col_coords,
                                                                                          flow, parent, tiles_r, tiles_c);

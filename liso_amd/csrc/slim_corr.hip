@@ -472,10 +472,9 @@ int liso_corr_lookup_fwd_tiled_f32(const liso_corr_cfg* cfg, const float* fmap1,
         !liso_dev::lds_opt_in(attr_set2, (const void*)corr_lookup_tiled_kernel<2>, kLds))
         return LISO_ELAUNCH;
     // 8 x 8-query tiles on the pooled levels once they give every CU a block (4 / 2 samples of 64 x 64 queries: 768 / 384 such blocks,
-    // 49.8 vs 65.5 / 32.8 vs 34.5 us; one sample: 192 blocks, no gain); LISO_CORR_WIDE_TILES = 0 / 1 forces either
-    static const int wide_env = getenv("LISO_CORR_WIDE_TILES") ? atoi(getenv("LISO_CORR_WIDE_TILES")) : -1;
+    // 49.8 vs 65.5 / 32.8 vs 34.5 us; one sample: 192 blocks, no gain)
     const long wide_all = (long)cfg->batch * (cfg->levels - 1) * tiles_y8 * tiles_x;
-    const bool wide = cfg->levels > 1 && (wide_env < 0 ? wide_all >= 256 : wide_env != 0);
+    const bool wide = cfg->levels > 1 && wide_all >= 256;
     const int n_fine = wide ? 1 : cfg->levels;
     const unsigned fine_blocks = (unsigned)(((long)cfg->batch * n_fine * tiles_y4 * tiles_x + 7) / 8 * 8);
     const unsigned wide_blocks = wide ? (unsigned)((wide_all + 7) / 8 * 8) : 0u;

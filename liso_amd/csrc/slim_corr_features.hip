@@ -431,7 +431,7 @@ struct Plan {
 };
 
 inline int pick_splits(long tiles, int slabs) {
-    static const int target = getenv("LISO_CORR_BWD_BLOCKS") ? atoi(getenv("LISO_CORR_BWD_BLOCKS")) : 512;  // (two blocks per CU: 143.7 us at B = 2, 64 x 64 against 171.5 at 256 and 226.4 at 128)
+    constexpr int target = 512;  // (two blocks per CU: 143.7 us at B = 2, 64 x 64 against 171.5 at 256 and 226.4 at 128)
     int s = (int)((target + tiles - 1) / tiles);  // fill the CUs
     if (s > kMaxSplits) s = kMaxSplits;
     if (s > slabs) s = slabs;

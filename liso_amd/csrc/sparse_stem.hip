@@ -479,7 +479,6 @@ int liso_sparse_conv_stat_groups(int hi, int wi, int co) {
     const long per_sample = (long)(hi / 2) * (wi / 2);
     const int ppb = 256 / (co / 16);
     int g = 4;
-    if (const char* e = getenv("LISO_SPARSE_GROUPS")) g = atoi(e) >= 1 && atoi(e) <= 4 ? atoi(e) : 4;  // experiments
     while (g > 1 && per_sample % (ppb * g)) g >>= 1;
     return per_sample % (ppb * g) ? 0 : g;
 }

@@ -103,7 +103,7 @@ class SmallUpdateBlock(nn.Module):
         from liso_amd.utils import mfma_conv as MC
 
         if (torch.is_grad_enabled() or not net.is_cuda or net.dtype != torch.float32 or not self.predict_logits
-                or self.cfg.model.predict_weight_for_static_aggregation or os.environ.get("LISO_UPDATE_SLICES", "1") == "0"):
+                or self.cfg.model.predict_weight_for_static_aggregation):
             return None
         me, gru = self.motion_encoder, self.gru
         ch, ci = net.shape[1], inp.shape[1]
@@ -165,8 +165,7 @@ class SmallUpdateBlock(nn.Module):
                     b_71 = torch.cat([me.conv_class1.bias, me.conv_flow1.bias])
                 P = lambda t: None if t is None else torch.nn.Parameter(t.contiguous(), requires_grad=False)  # noqa: E731
             hit = self._infer_perm = (key, w_conv, w_q, P(w_cf), P(b_cf), P(w_hd), P(b_hd), P(w_71), P(b_71))
-        merged = (os.environ.get("LISO_UPDATE_MERGED", "1") != "0" and tuple(me.conv_class2.kernel_size) == (3, 3)
-                  and tuple(me.conv_flow2.kernel_size) == (3, 3) and tuple(fh.conv2.kernel_size) == (3, 3) and tuple(hd.conv2.kernel_size) == (3, 3)
+        merged = (tuple(me.conv_class2.kernel_size) == (3, 3) and tuple(me.conv_flow2.kernel_size) == (3, 3) and tuple(fh.conv2.kernel_size) == (3, 3) and tuple(hd.conv2.kernel_size) == (3, 3)
                   and me.conv_class1.out_channels % 8 == 0 and me.conv_flow1.out_channels % 8 == 0)
         # the loop's (flow | logits) state as one channels-last pixel of 8 floats, updated by ONE launch per iteration (state_step)
         packed = merged and hit[7] is not None and os.environ.get("LISO_UPDATE_PACKED_STATE", "1") != "0"

@@ -146,7 +146,6 @@ class DetectorTrainer:
             _MC._sparse_flag(device)
         self.use_graph = bool(use_graph) and device.type == "cuda"
         self._graph, self._graph2, self._graph_sig, self._capture_stream = None, None, None, None
-        self._wgrad_stream = None
         self.fused_loss = (fused_centerpoint.supports(cfg) and device.type == "cuda") if fused_loss is None else fused_loss
         self.net = BoxLearner(cfg).to(device)
         self.net.model.set_compute_dtype(compute_dtype)
@@ -347,11 +346,9 @@ class DetectorTrainer:
             torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
         if self._capture_stream is None:
             self._capture_stream = side_stream(dev, "flow")  # (the loop trainer lends the same one: SLIM inference's stream)
-        # LISO_WGRAD_SIDE=1 (opt-in, measured slower): the weight gradients as a parallel branch of the captured backward pass
-        # (mfma_conv.wgrad_side) -- nothing in the backward chain reads them.  Results identical; but every fork edge of a replayed
-        # hipGraph costs ~240 us here: detector replay 7.15 vs 2.54 ms (19 forks + 1 join), loop 6.44 vs 4.38 ms per step.
-        if self._wgrad_stream is None and os.environ.get("LISO_WGRAD_SIDE", "0") == "1":
-            self._wgrad_stream = side_stream(dev, "wgrad")
+        # (MEASURED, removed: the weight gradients as a parallel branch of the captured backward pass -- nothing in the backward chain
+        # reads them.  Results identical; but every fork edge of a replayed hipGraph costs ~240 us here: detector replay 7.15 vs
+        # 2.54 ms (19 forks + 1 join), loop 6.44 vs 4.38 ms per step.)
         side = self._capture_stream  # (kept alive with the graph)
         side.wait_stream(torch.cuda.current_stream(dev))
 
@@ -373,8 +370,6 @@ class DetectorTrainer:
                 if self._pack_jobs:  # the forward / data-gradient panels of every layer from ONE launch (recorded in the warm-up)
                     self._step_packs = MC.batched_pack(self._pack_jobs)
             MC.set_step_packs(getattr(self, "_step_packs", None))
-            det_cus = MC.roles_cus(getattr(self, "roles_cus", 0))  # (experiment knob of the pipelined loop: LisoLoopTrainer.detector_cus)
-            det_cus.__enter__()
             MC.set_direct_grads(True, keep_touched=part == 2)  # gradients of conv / BatchNorm parameters land in the flat buffer without an add each
             gathered = self._gather_params or []
             for p_, _ in gathered:  # (autograd then KEEPS the gradient tensor it is handed instead of adding it into the zeroed slice)
@@ -386,14 +381,11 @@ class DetectorTrainer:
                         total, _, _ = self.loss(None, self._static_targets, canvas=(self._static_bev, self._static_occ))
                     finally:
                         rpn.grad_cut = None
-                    with MC.wgrad_side(self._wgrad_stream):
-                        self._backward(total)
+                    self._backward(total)
                     self._body_loss = total.detach()
                 if cut is not None and part in (None, 2):
-                    with MC.wgrad_side(self._wgrad_stream):
-                        cut.finish()
+                    cut.finish()
             finally:
-                det_cus.__exit__(None, None, None)
                 MC.set_step_packs(None)
                 MC.set_direct_grads(False, keep_touched=True)
                 self._gather_gradients(gathered, add=part == 2)
@@ -404,14 +396,13 @@ class DetectorTrainer:
             MC.record_pack_jobs(True)
             body()
             self._pack_jobs = MC.record_pack_jobs(False)
-            if os.environ.get("LISO_GATHER_GRADS", "1") != "0":
-                # parameters whose gradient no kernel wrote in place during that pass (merged head convolutions, sliced BatchNorm
-                # vectors, block-diagonal filters): autograd would launch one `add_` each into the zeroed flat buffer -- instead
-                # their gradient tensors are collected behind the backward pass by ONE launch (liso_gather_f32)
-                in_place = MC.direct_touched()
-                outside = {id(p_) for p_ in self.net.model.pfn.parameters()}  # (the pillar encoder's backward runs outside the graph)
-                self._gather_params = [(p_, p_.grad) for p_ in self.net.parameters()
-                                       if p_.requires_grad and p_.grad is not None and id(p_) not in in_place and id(p_) not in outside]
+            # parameters whose gradient no kernel wrote in place during that pass (merged head convolutions, sliced BatchNorm
+            # vectors, block-diagonal filters): autograd would launch one `add_` each into the zeroed flat buffer -- instead
+            # their gradient tensors are collected behind the backward pass by ONE launch (liso_gather_f32)
+            in_place = MC.direct_touched()
+            outside = {id(p_) for p_ in self.net.model.pfn.parameters()}  # (the pillar encoder's backward runs outside the graph)
+            self._gather_params = [(p_, p_.grad) for p_ in self.net.parameters()
+                                   if p_.requires_grad and p_.grad is not None and id(p_) not in in_place and id(p_) not in outside]
             body()
         torch.cuda.current_stream(dev).wait_stream(side)
         with torch.no_grad():  # the warm-up passes must not count as training steps (BatchNorm statistics / counters)
@@ -516,7 +507,7 @@ class SlimTrainer:
                 self.net, device_ids=[device.index] if device.type == "cuda" else None, bucket_cap_mb=64,
                 broadcast_buffers=False, gradient_as_bucket_view=True)
         # (flat buffers unless DistributedDataParallel owns the gradients as views of ITS buckets)
-        flat = device.type == "cuda" and self.model is self.net and os.environ.get("LISO_FLAT_RMSPROP", "1") != "0"
+        flat = device.type == "cuda" and self.model is self.net
         self.optimizer, self.lr_scheduler = get_slim_optimizer_scheduler(self.slim_cfg, self.net.parameters(), flat=flat)
         self._flat_opt = hasattr(self.optimizer, "flat_grad")
         import numpy as np
@@ -545,8 +536,7 @@ class SlimTrainer:
             # tensors instead of launching one add_ per parameter into the zeroed flat buffer (~100 launches per step), and one
             # gather launch per 48 tensors moves them into their slices (DetectorTrainer does the same for its few such parameters)
             outside = {id(p) for p in self.net.raft_network.pp_layer.parameters()} if hasattr(self.net.raft_network, "pp_layer") else set()
-            self._gather_params = [(p, p.grad) for p in params if id(p) not in outside] \
-                if os.environ.get("LISO_GATHER_GRADS", "1") != "0" else []
+            self._gather_params = [(p, p.grad) for p in params if id(p) not in outside]
             if self.world > 1:  # replicas start identical (what the DDP constructor would do)
                 for t in list(self.net.parameters()) + list(self.net.buffers()):
                     dist.broadcast(t.data, src=0)
@@ -942,8 +932,6 @@ class LisoLoopTrainer:
         if slim_state_dict is not None:
             self.slim.load_state_dict(slim_state_dict)
         self.slim.eval()
-        if os.environ.get("LISO_ENC_IMAGES"):  # experiment: encoder passes of at most this many images inside an inference batch
-            self.slim.raft_network.encoder_images_per_pass = int(os.environ["LISO_ENC_IMAGES"])
         for p_ in self.slim.parameters():  # frozen: its packed convolution panels are built once and never re-packed
             p_.requires_grad_(False)
         self.cluster_detector = FlowClusterDetector(cfg).to(device)
@@ -965,8 +953,6 @@ class LisoLoopTrainer:
         # compute units the captured SLIM inference's persistent 3x3 convolutions may take while the pipeline overlaps it with the
         # detector step (0 = all): half the chip by default, see _infer_flow_padded
         self.infer_cus = 0
-        if device.type == "cuda" and self.overlap and os.environ.get("LISO_DETECTOR_CUS"):
-            self.detector.roles_cus = int(os.environ["LISO_DETECTOR_CUS"])  # (experiment: the detector's persistent convolutions capped too)
         if device.type == "cuda" and self.overlap:
             n_cu = torch.cuda.get_device_properties(device).multi_processor_count
             self.infer_cus = int(os.environ.get("LISO_INFER_CUS", str(n_cu // 2)))

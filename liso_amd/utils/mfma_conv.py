@@ -169,15 +169,22 @@ def _pix_stride(v):
     return C
 
 
-def as_nhwc(t, vec):
-    """physical NHWC view of a logical-NCHW tensor + its pixel stride (a copy is made unless the layout already is
-    channels-last, possibly as a channel slice of a wider tensor, with a pixel stride that keeps 16-B alignment)"""
+def _rows_view(t, vec):
+    """physical [B,H,W,C] view of a logical-NCHW tensor whose (pixel, channel) rows are regular -- dense, or a channel slice of a wider
+    channels-last tensor, with a pixel stride that keeps 16-B alignment -- and its row stride in elements; (None, 0) otherwise"""
     v = t.permute(0, 2, 3, 1)
     B, H, W, C = v.shape
     ps = _pix_stride(v)
     regular = (v.stride(3) == 1 or C == 1) and ps >= C and (W == 1 or v.stride(2) == ps) and (H == 1 or v.stride(1) == W * ps) and \
         (B == 1 or v.stride(0) == H * W * ps) and ps % vec == 0 and v.data_ptr() % 16 == 0
-    if not regular:
+    return (v, ps) if regular else (None, 0)
+
+
+def as_nhwc(t, vec):
+    """physical NHWC view of a logical-NCHW tensor + its pixel stride (a copy is made unless `_rows_view` can read the layout in place)"""
+    v, ps = _rows_view(t, vec)
+    if v is None:
+        C = t.shape[1]
         if _COPY_LOG is not None:
             import traceback
             fr = [f"{f.name}:{f.lineno}" for f in traceback.extract_stack(limit=7)[:-1] if "mfma_conv" not in f.filename][-3:]
@@ -211,35 +218,6 @@ class shared_gpu:
         _SHARED_DEPTH[0] -= 1
         if _SHARED_DEPTH[0] == 0:
             L.check(L.lib().liso_conv_set_option(L.CONV_OPT_SHARED_GPU, 0), "conv_set_option")
-        return False
-
-
-_WGRAD_SIDE = None  # {"stream", "keep", "used"} while weight gradients are issued on a side stream (wgrad_side)
-
-
-class wgrad_side:
-    """`with wgrad_side(stream):` around a backward pass -- the weight-gradient launches of the fused convolutions (those that write
-    straight into their parameter's gradient buffer: nothing for autograd to consume) go to `stream`, forked off the backward pass's
-    stream by an event behind the gradient they read and joined when the block exits.  Nothing in the backward chain reads a weight
-    gradient: the chain (data gradient -> BatchNorm backward -> data gradient ...) no longer waits for 19 weight-gradient + slab-reduction
-    launches, which run next to it -- inside a captured hipGraph as a parallel branch.  The tensors those launches read are kept alive
-    until the join (no allocator reuse under them)."""
-
-    def __init__(self, stream):
-        self.stream = stream
-
-    def __enter__(self):
-        global _WGRAD_SIDE
-        self.prev = _WGRAD_SIDE
-        _WGRAD_SIDE = {"stream": self.stream, "keep": [], "used": False} if self.stream is not None else None
-        return self
-
-    def __exit__(self, *exc):
-        global _WGRAD_SIDE
-        st, _WGRAD_SIDE = _WGRAD_SIDE, self.prev
-        if st is not None and st["used"]:
-            torch.cuda.current_stream(st["stream"].device).wait_stream(st["stream"])
-            st["keep"].clear()
         return False
 
 
@@ -282,14 +260,8 @@ def batched_pack(jobs):
     out, arr = {}, (L.ConvPackJob * len(jobs))()
     keep = []
     for i, (key, weight, spec, for_dgrad, mode) in enumerate(jobs):
-        w = weight.detach()
-        if w.dtype != torch.float32 or not w.is_contiguous():
-            w = w.float().contiguous()
+        w, d0, d1, dst = _pack_operands(weight, spec, for_dgrad, mode)
         keep.append(w)
-        d0, d1 = w.shape[0], w.shape[1]
-        same = spec.transposed == bool(for_dgrad)
-        K, N = (d1, d0) if same else (d0, d1)
-        dst = torch.empty(L.lib().liso_conv_packed_bytes(K, N, spec.kh * spec.kw, mode), dtype=torch.uint8, device=w.device)
         arr[i] = L.ConvPackJob(w.data_ptr(), dst.data_ptr(), d0, d1, spec.kh, spec.kw, int(spec.transposed), int(bool(for_dgrad)), mode)
         out[key] = dst
     if jobs:
@@ -329,15 +301,19 @@ def pack_weights(weight, spec, for_dgrad, mode):
     return out
 
 
-def _pack_weights(weight, spec, for_dgrad, mode):
+def _pack_operands(weight, spec, for_dgrad, mode):
+    """-> (fp32 contiguous source, its two leading dimensions, uninitialised panel buffer) of one pack job"""
     w = weight.detach()
     if w.dtype != torch.float32 or not w.is_contiguous():
         w = w.float().contiguous()
     d0, d1 = w.shape[0], w.shape[1]
-    same = spec.transposed == bool(for_dgrad)
-    K, N = (d1, d0) if same else (d0, d1)
-    nbytes = L.lib().liso_conv_packed_bytes(K, N, spec.kh * spec.kw, mode)
-    out = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    K, N = (d1, d0) if spec.transposed == bool(for_dgrad) else (d0, d1)
+    dst = torch.empty(L.lib().liso_conv_packed_bytes(K, N, spec.kh * spec.kw, mode), dtype=torch.uint8, device=w.device)
+    return w, d0, d1, dst
+
+
+def _pack_weights(weight, spec, for_dgrad, mode):
+    w, d0, d1, out = _pack_operands(weight, spec, for_dgrad, mode)
     with torch.cuda.device(w.device):
         L.check(L.lib().liso_conv_pack_weights(L.ptr(w), d0, d1, spec.kh, spec.kw, int(spec.transposed), int(bool(for_dgrad)), mode,
                                                L.ptr(out), L.stream_ptr()), "conv_pack_weights")
@@ -527,8 +503,7 @@ def conv_wgrad(x, dy, weight_shape, spec, in_scale=None, in_shift=None, in_relu=
     (None: a kernel without slabs ran, the gradients are complete)."""
     L.require_cuda(x, dy)
     if (x.shape[1] == 4 and x.dtype == torch.float32 and not spec.transposed and spec.stride == 1 and spec.kh == spec.kw and spec.kh in (5, 7)
-            and spec.padding == spec.kh // 2 and in_scale is None and tuple(weight_shape[1:]) == (4, spec.kh, spec.kw)
-            and os.environ.get("LISO_WGRAD_SMALLCI", "1") != "0"):
+            and spec.padding == spec.kh // 2 and in_scale is None and tuple(weight_shape[1:]) == (4, spec.kh, spec.kw)):
         res = _conv_wgrad_smallci(x, dy, weight_shape, spec, want_bias, out_dw, out_db, co_true)
         if res is not None:
             return (*res, None) if defer_reduce else res
@@ -740,43 +715,6 @@ def _direct_target(p):
     return g
 
 
-_BN_TICKETS = {}  # device index -> [int32 zeros, {layer key: slot}]
-
-
-def _bn_ticket(key, device):
-    """the layer's persistent device counter for liso_bn_relu_bwd_ticket (zero between calls), or None: the pool of a device is
-    created on the first EAGER call (memory allocated while a graph is being captured belongs to that graph's pool) and, like every
-    trainer here, a captured step is preceded by an eager warm-up pass; LISO_BN_TICKET=1 enables it"""
-    if os.environ.get("LISO_BN_TICKET", "0") != "1":
-        # MEASURED (round 4): slower than the separate finalize launch it saves -- detector step 4.57-4.63 vs 4.46 ms, loop 5.66 vs
-        # 5.65 ms (with plain stores + __threadfence(): 4.84 / 6.03 ms -- a device-scope release fence writes back the XCD's L2).
-        # Inside a hipGraph the extra launch costs ~2 us of stream time; the last block's 256-thread finalize over L2-bypassing
-        # loads costs more.  Off unless asked for.
-        return None
-    ent = _BN_TICKETS.get(device.index)
-    if ent is None:
-        if torch.cuda.is_current_stream_capturing():
-            return None
-        ent = _BN_TICKETS[device.index] = [torch.zeros(4096, dtype=torch.int32, device=device), {}]
-    slot = ent[1].get(key)
-    if slot is None:
-        if len(ent[1]) >= ent[0].numel():
-            return None
-        slot = ent[1][key] = len(ent[1])
-    return ent[0][slot:slot + 1]
-
-
-def _rows_view(t, vec):
-    """physical [B,H,W,C] view of a logical-NCHW tensor whose (pixel, channel) rows are regular -- dense, or a channel slice of a wider
-    channels-last tensor -- and its row stride in elements; (None, 0) otherwise"""
-    v = t.permute(0, 2, 3, 1)
-    B, H, W, C = v.shape
-    ps = _pix_stride(v)
-    regular = (v.stride(3) == 1 or C == 1) and ps >= C and (W == 1 or v.stride(2) == ps) and (H == 1 or v.stride(1) == W * ps) and \
-        (B == 1 or v.stride(0) == H * W * ps) and ps % vec == 0 and v.data_ptr() % 16 == 0
-    return (v, ps) if regular else (None, 0)
-
-
 def _bn_backward_group(g, x_raw, grp, relu, training, out=None, job=None):
     """gradient through relu?(bn(x_raw)) of ONE BatchNorm given g = dL/d(output): -> (dx_raw, dgamma, dbeta); g, x_raw logical NCHW.
     Channel slices of wider channels-last tensors are read in place (liso_bn_relu_bwd_strided); `out`: a logical-NCHW tensor (e.g. the
@@ -819,12 +757,7 @@ def _bn_backward_group(g, x_raw, grp, relu, training, out=None, job=None):
         else:
             args = (L.ptr(gv), L.ptr(xv), bf, M, C, L.ptr(grp["gamma"]), L.ptr(grp["stats"]), int(training), int(relu), L.ptr(dxv), L.ptr(gg),
                     L.ptr(gb), L.ptr(ws), nbytes)
-            ticket = _bn_ticket(grp.get("ticket_key", id(grp["gamma"])), xv.device)
-            if ticket is not None:  # two launches: the reduction's last block also finalises (include/liso_bn.h)
-                L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd_ticket(*args, L.ptr(ticket), L.stream_ptr()), units=units),
-                        "bn_relu_bwd_ticket")
-            else:
-                L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd(*args, L.stream_ptr()), units=units), "bn_relu_bwd")
+            L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd(*args, L.stream_ptr()), units=units), "bn_relu_bwd")
     return dxv.permute(0, 3, 1, 2), (None if direct else gg), (None if direct else gb)
 
 
@@ -854,8 +787,7 @@ def _bn_backward(g, x_raw, fold, job=None):
         return dx_full, grads
     gam = torch.cat([grp["gamma"].detach() for grp in fold.groups])
     stats = torch.cat([grp["stats"][k * c:(k + 1) * c] for k in range(4) for grp, c in zip(fold.groups, Cs)])  # scale | shift | mean | invstd
-    dx, gg, gb = _bn_backward_group(g, x_raw, {"gamma": gam, "beta": None, "stats": stats, "ticket_key": id(fold.groups[0]["gamma"])},
-                                    fold.relu, fold.training, job=job)
+    dx, gg, gb = _bn_backward_group(g, x_raw, {"gamma": gam, "beta": None, "stats": stats}, fold.relu, fold.training, job=job)
     grads, a = [], 0
     for c in Cs:
         grads += [gg[a:a + c], gb[a:a + c]]
@@ -917,25 +849,14 @@ class _FusedConv(torch.autograd.Function):
                 res = conv_wgrad_sparse(x_raw, ctx.meta["occupancy"], dy, tuple(weight.shape), spec, want_bias=ctx.meta["has_bias"])
                 tw = None if res is not None else tw
             if res is None:
-                side = _WGRAD_SIDE if (tw is not None and dy.is_cuda) else None
-                if side is not None:  # (written in place: autograd never sees the result -- see wgrad_side)
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(dy.device))
-                    with torch.cuda.stream(side["stream"]):
-                        side["stream"].wait_event(ev)
-                        res = conv_wgrad(x_raw, dy, tuple(weight.shape), spec, sc, sh, in_relu=fold.relu if fold is not None else False,
-                                         want_bias=ctx.meta["has_bias"], out_dw=tw, out_db=tb, co_true=co_true)
-                    side["keep"].append((x_raw, dy, sc, sh))
-                    side["used"] = True
-                else:
-                    # Nothing reads dw before the optimizer: where a BatchNorm-backward finalize launch follows in THIS call (a fold
-                    # behind the data gradient), the slab reduction rides in it instead of taking a launch of its own on the chain.
-                    # The job (and the workspace it holds) never leaves this function.
-                    defer = _DEFER_WGRAD_REDUCE and dy.is_cuda and fold is not None and want_dx
-                    res = conv_wgrad(x_raw, dy, tuple(weight.shape), spec, sc, sh, in_relu=fold.relu if fold is not None else False,
-                                     want_bias=ctx.meta["has_bias"], out_dw=tw, out_db=tb, co_true=co_true, defer_reduce=defer)
-                    if defer and res is not None:
-                        job, res = res[2], res[:2]
+                # Nothing reads dw before the optimizer: where a BatchNorm-backward finalize launch follows in THIS call (a fold
+                # behind the data gradient), the slab reduction rides in it instead of taking a launch of its own on the chain.
+                # The job (and the workspace it holds) never leaves this function.
+                defer = _DEFER_WGRAD_REDUCE and dy.is_cuda and fold is not None and want_dx
+                res = conv_wgrad(x_raw, dy, tuple(weight.shape), spec, sc, sh, in_relu=fold.relu if fold is not None else False,
+                                 want_bias=ctx.meta["has_bias"], out_dw=tw, out_db=tb, co_true=co_true, defer_reduce=defer)
+                if defer and res is not None:
+                    job, res = res[2], res[:2]
             if res is None:  # (none of the networks' layers; there is no library route for a device tensor)
                 raise NotImplementedError(f"liso_amd: no device weight-gradient kernel for {tuple(weight.shape)} stride {spec.stride} "
                                           f"on {tuple(x_raw.shape)} {x_raw.dtype}")
@@ -1105,20 +1026,20 @@ def _sparse_mode(el):
     return {L.ELEM_BF16: L.CONV_BF16, L.ELEM_F16: L.CONV_F16}.get(int(el), L.CONV_F32X3)
 
 
-def _sparse_geometry(x_raw, weight, spec):
+def _sparse_geometry(shape, dtype, weight, spec):
     """(element code, k, co) if the sparse-canvas kernels cover this convolution, else None: 7x7 / 2 / 3 with 32 filters on fp32 tensors
     (the SLIM stem) or 3x3 / 2 / 1 with 64 filters on bf16 / fp16 / fp32 tensors (the detector's first layer), 64 input channels, an even canvas
     height and a width that is a multiple of 64; fp32 tensors only in F32X3 arithmetic (the exact-fp32 mode keeps the dense kernels)"""
-    if os.environ.get("LISO_SPARSE_STEM", "1") == "0" or spec.transposed or x_raw.dim() != 4:
+    if os.environ.get("LISO_SPARSE_STEM", "1") == "0" or spec.transposed or len(shape) != 4:
         return None
-    B, C, H, W = x_raw.shape
+    B, C, H, W = shape
     geo = (spec.kh, spec.kw, spec.stride, spec.padding, weight.shape[0])
-    bf = L.elem_code(x_raw.dtype) if x_raw.dtype in (torch.bfloat16, torch.float16) else 0  # (16-bit tensors: non-zero)
+    bf = L.elem_code(dtype) if dtype in (torch.bfloat16, torch.float16) else 0  # (16-bit tensors: non-zero)
     if C != 64 or tuple(weight.shape[1:]) != (64, spec.kh, spec.kw) or H % 2 or W % 64:
         return None
-    if geo == (7, 7, 2, 3, 32) and x_raw.dtype == torch.float32 and fp32_mode() == "x3":
+    if geo == (7, 7, 2, 3, 32) and dtype == torch.float32 and fp32_mode() == "x3":
         return False, 7, 32
-    if geo == (3, 3, 2, 1, 64) and (bf or (x_raw.dtype == torch.float32 and fp32_mode() == "x3")):
+    if geo == (3, 3, 2, 1, 64) and (bf or (dtype == torch.float32 and fp32_mode() == "x3")):
         return bf, 3, 64
     return None
 
@@ -1143,7 +1064,7 @@ def _sparse_stem(x_raw, occupancy, weight, bias, spec, kind, relu, stats_shift=N
     """A stride-2 convolution on the pillar canvas in its sparse form (liso_sparse_conv_forward): only occupied cells are multiplied.
     `kind`: "none" (no statistics; `relu` in the epilogue) | "instance" / "batch" (raw output + per-block statistics partial sums,
     shifted by `stats_shift`).  -> (y logical NCHW, partial sums [blocks, 2, co] | None) or None (the caller takes the dense kernel)."""
-    geo = _sparse_geometry(x_raw, weight, spec)
+    geo = _sparse_geometry(tuple(x_raw.shape), x_raw.dtype, weight, spec)
     if geo is None:
         return None
     bf, k, co = geo
@@ -1183,8 +1104,7 @@ def _sparse_dgrad(dy, occupancy, weight, spec, x_shape, x_dtype, lists=None):
     B, C, H, W = x_shape
     if dy.dtype != x_dtype:
         return None
-    fake = _SparseShape(x_shape, x_dtype)
-    geo = _sparse_geometry(fake, weight, spec)
+    geo = _sparse_geometry(tuple(x_shape), x_dtype, weight, spec)
     if geo is None:
         return None
     bf, k, co = geo
@@ -1212,16 +1132,6 @@ def _sparse_dgrad(dy, occupancy, weight, spec, x_shape, x_dtype, lists=None):
         # (bytes the LAUNCH moves, lower bound: dy read once; the rows it writes at the occupied cells are not counted -- their number
         # is only known on the device -- and the zero fill of the canvas gradient is torch.zeros above, outside the timed launch)
     return dx.permute(0, 3, 1, 2)
-
-
-class _SparseShape:
-    """shape / dtype stand-in for `_sparse_geometry` where only the input's shape is at hand (backward)"""
-
-    def __init__(self, shape, dtype):
-        self.shape, self.dtype = tuple(shape), dtype
-
-    def dim(self):
-        return len(self.shape)
 
 
 @torch.no_grad()

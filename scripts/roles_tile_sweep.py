@@ -1,7 +1,7 @@
 """conv_roles_kernel: tile shape sweep on the layers of the RAFT update block at inference (1, 2, 4 sweep pairs per replay).
 One child process per (MI, NJ) -- the planner's switches are read once --, hipGraph of 20 launches, median of 5 replays.
     python scripts/roles_tile_sweep.py            # the table
-(Round 5 ran this sweep with a third axis, the channel slabs of a tile split over 2-4 compute units with a ticketed hand-over through
+(Round 5 ran this sweep with a third axis, the channel slabs of a tile split over 2-4 compute units with a counted hand-over through
 memory: profiles/r05_roles_split_sweep.txt, DESIGN.md section 10 -- removed, the hand-over cost more than the idle CUs.)
 """
 import os

@@ -1,5 +1,5 @@
 """conv_wgrad (+ slab reduction) of one 3x3 / stride-1 layer, event-timed over 50 calls after warm-up; checks against an fp64 reference.
-python scripts/wgrad_time.py B ci co H [fp32|bf16]      (LISO_WGRAD_CIW = 64 | 32: input channels per block of conv_wgrad_rs3_kernel)"""
+python scripts/wgrad_time.py B ci co H [fp32|bf16]"""
 import os
 import sys
 

@@ -282,7 +282,6 @@ def test_bn_backward_fp16_data_gradient_edges(case, monkeypatch):
     require_fp16()
     from liso_amd.utils import mfma_conv as MC
 
-    monkeypatch.setenv("LISO_BN_TICKET", "0")
     C, B, H, W = 64, 2, 16, 24
     g = torch.Generator().manual_seed(4)
     sign = (1.0 - 2.0 * (torch.arange(C) % 2).double()).view(1, -1, 1, 1)
