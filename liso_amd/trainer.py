@@ -6,7 +6,9 @@ optimizer factory liso_cli.py:792-823).  The reference is single-GPU; data paral
 gradient all-reduce over RCCL/xGMI in a single flat bucket overlapped with backward, per-rank BatchNorm) is the
 only addition.
 """
+import collections
 import contextlib
+import ctypes
 import os
 
 import torch
@@ -16,6 +18,8 @@ from liso_amd import _lib as L
 
 from liso_amd.losses.centerpoint_loss import centerpoint_loss, rotation_vec_on_unit_circle
 from liso_amd.networks.simple_net.simple_net import BoxLearner
+from liso_amd.utils import graph_capture as GC
+from liso_amd.utils import tensor_tree as TT
 
 
 def get_optimizer_scheduler(cfg, box_predictor, total_steps=None, flat=False):
@@ -71,9 +75,6 @@ def gather_gradients(device, params, add=False):
     tensors -> the flat views by one launch per 48 tensors (liso_gather_f32); `.grad` is the flat view again afterwards.  `add`: the
     second half of a split backward pass adds (nothing arrives there for these parameters today).  -> the source tensors (keep them
     alive until the launch has run: inside a capture they belong to the graph's pool anyway)."""
-    from liso_amd import _lib as L
-    import ctypes
-
     jobs = []
     for p_, flat in params:
         g = p_.grad
@@ -107,12 +108,56 @@ def side_stream(device, role, priority=0):
     trainer, stepped again afterwards: 4.37; either trainer without overlap: 9.1-9.4; the second with its side streams replaced by
     fresh high-priority ones: 4.39 -- scripts/second_trainer_bisect.py, round 6; rounds 4-5 had seen it as "a trainer built second
     is 1.5x slower, cause not found" and moved bench.py's parity legs into child processes).  Streams are queues, not state: trainers
-    of one process share them, an idle trainer leaves nothing on them, two active ones interleave on them."""
+    of one process share them, an idle trainer leaves nothing on them, two active ones interleave on them.
+    Every trainer captures on the shared "flow" stream: correct only while ONE host thread drives all trainers of the process.
+    A role has one priority: asking for a cached role with another one is an error."""
     key = (device.index if device.index is not None else torch.cuda.current_device(), role)
-    st = _SIDE_STREAMS.get(key)
-    if st is None:
-        st = _SIDE_STREAMS[key] = torch.cuda.Stream(device=device, priority=priority)
+    if key not in _SIDE_STREAMS:
+        _SIDE_STREAMS[key] = (torch.cuda.Stream(device=device, priority=priority), priority)
+    st, made_with = _SIDE_STREAMS[key]
+    assert priority == made_with, f"side stream {role!r} exists with priority {made_with}, requested with {priority}"
     return st
+
+
+def _prepare_device(device, exact):
+    """before a trainer builds its network.  `exact`: True = fp32 convolutions on the native fp32 MFMA (2^-24 per product, the reference's
+    fp32 semantics; the parity configuration), False = as bf16 hi/lo pairs (F32X3, 2^-16), None = keep mfma_conv.set_fp32_mode's."""
+    from liso_amd.utils import mfma_conv as MC
+
+    if exact is not None:
+        MC.set_fp32_mode("exact" if exact else "x3")
+    if device.type == "cuda":  # (persistent device flag of the sparse canvas convolutions: must exist before the first capture)
+        MC._sparse_flag(device)
+
+
+def _broadcast_replicas(net):  # (replicas start identical: what the DDP constructor would do)
+    for t in list(net.parameters()) + list(net.buffers()):
+        dist.broadcast(t.data, src=0)
+
+
+@contextlib.contextmanager
+def _captured_training_pass(tr, canvases, second_half=False):
+    """prologue and epilogue of a captured training step, around its loss + backward.  `tr` carries `_flat_grad`, `_gather_params`,
+    `device` and `_pack_jobs` (recorded in the warm-up: every layer's forward / data-gradient panels then come from ONE launch);
+    `canvases`: the leaf inputs.  `second_half` of a backward pass split in two (GradCut): gradients and panels of the first stay."""
+    from liso_amd.utils import mfma_conv as MC
+
+    if not second_half:
+        tr._flat_grad.zero_()
+        # (no zeroed gradient buffer for a canvas: with .grad = None autograd keeps the first layer's data gradient as the leaf's
+        # gradient -- a 134-MB fill and a 400-MB accumulation into zeros per detector step at B = 4 otherwise)
+        for c in canvases:
+            c.grad = None
+        tr._step_packs = MC.batched_pack(tr._pack_jobs) if tr._pack_jobs else None
+    MC.set_step_packs(tr._step_packs)
+    gathered = tr._gather_params or []
+    for p_, _ in gathered:  # (autograd then KEEPS the gradient tensor it is handed instead of adding it into the zeroed slice)
+        p_.grad = None
+    try:
+        yield
+    finally:
+        MC.set_step_packs(None)
+        tr._gather_keepalive = gather_gradients(tr.device, gathered, second_half)
 
 
 class DetectorTrainer:
@@ -124,9 +169,7 @@ class DetectorTrainer:
         pillar encoder's backward and the second, small all-reduce; 1 = one graph, one all-reduce behind it.  (ROCm refuses external
         events inside a captured graph -- "External events are disallowed in rocm" -- so the signal cannot come from inside ONE
         graph.)  A single rank always runs one graph.
-        `exact` (with compute_dtype float32): True = fp32 convolutions on the native fp32 MFMA (2^-24 per product, the reference's
-        fp32 semantics; the parity configuration), False = as bf16 hi/lo pairs (F32X3, 2^-16 per product), None = leave the
-        process-wide setting (liso_amd.utils.mfma_conv.set_fp32_mode) as it is.
+        `exact` (with compute_dtype float32): the arithmetic of the fp32 convolutions, see `_prepare_device`.
         `fused_loss`: activations + decode + CenterPoint loss in one HIP pass (include/liso_detector.h) instead of
         ~140 torch launches; default = whenever the configuration is the overlay the kernel implements and the
         network runs on the GPU.
@@ -141,17 +184,12 @@ class DetectorTrainer:
         from liso_amd.losses import fused_centerpoint
 
         self.cfg, self.device = cfg, device
-        if device.type == "cuda":  # (persistent device flag of the sparse canvas convolutions: must exist before the first capture)
-            from liso_amd.utils import mfma_conv as _MC
-            _MC._sparse_flag(device)
+        _prepare_device(device, exact)
         self.use_graph = bool(use_graph) and device.type == "cuda"
-        self._graph, self._graph2, self._graph_sig, self._capture_stream = None, None, None, None
+        self._graph, self._graph2, self._graph_sig = None, None, None
         self.fused_loss = (fused_centerpoint.supports(cfg) and device.type == "cuda") if fused_loss is None else fused_loss
         self.net = BoxLearner(cfg).to(device)
         self.net.model.set_compute_dtype(compute_dtype)
-        from liso_amd.utils import mfma_conv as MC
-        if exact is not None:
-            MC.set_fp32_mode("exact" if exact else "x3")
         if self.use_graph and not self.fused_loss:
             # only the fused loss keeps the captured region free of hipMemsetAsync nodes (graph_safety.py): torch's multi-block
             # reductions (centerpoint_loss) put them into the graph
@@ -190,9 +228,8 @@ class DetectorTrainer:
         self.n_grad_buckets = 1
         if self.use_graph:
             self._flat_grad = self.optimizer.flat_grad  # data parallelism: SUM all-reduce of this buffer, 1 / world inside the AdamW launch
-            if self.world > 1:  # replicas start identical (what the DDP constructor would do)
-                for t in list(self.net.parameters()) + list(self.net.buffers()):
-                    dist.broadcast(t.data, src=0)
+            if self.world > 1:
+                _broadcast_replicas(self.net)
                 self.optimizer.grad_scale = 1.0 / self.world
                 self._setup_gradient_buckets(grad_buckets)
             elif grad_buckets == 2:  # (one rank, asked for explicitly: the two-graph step without a collective -- tests)
@@ -303,133 +340,72 @@ class DetectorTrainer:
         saved = [p.grad for p in self.net.parameters()]
         for p in self.net.parameters():
             p.grad = None
-        bufs = {k: v.clone() for k, v in self.net.state_dict().items() if "running" in k or "num_batches" in k}
         ctx = self.model.no_sync() if hasattr(self.model, "no_sync") else contextlib.nullcontext()
-        with ctx:
+        with GC.frozen_buffers(self.net, keep=lambda k, v: "running" in k or "num_batches" in k), ctx:
             total, _, _ = self.loss(pcls, targets)
             self._backward(total)  # (fp16: seeded with the loss scale like the real step, so the same gradients flow)
-        with torch.no_grad():
-            for k, v in self.net.state_dict().items():
-                if k in bufs:
-                    v.copy_(bufs[k])
         for p, g in zip(self.net.parameters(), saved):
             p.grad = g
         return total.detach()
 
     # ---- hipGraph path ----------------------------------------------------------------------------------------------
     # The graph holds backbone + head + fused loss, forward and backward (~95 % of the step's launches).  The pillar encoder
-    # (voxelise + PFN + scatter; 10 launches) runs eagerly around it.  Rounds 2-4: replaying ITS launches from a graph while other
-    # pillar-encoder calls ran eagerly in the same process (the LISO loop's SLIM inference) ended in a GPU memory fault, bisected to
-    # exactly that combination (scripts/try_loop_graph3.py PART=pfn).  Cause (round 5): rocPRIM's radix sort inside the voxeliser --
-    # the same library path whose captured launches fault for > 1 M keys (see _capture_slim below) and whose memset nodes do not
-    # survive replays (utils/graph_safety.py).  The voxeliser no longer sorts (csrc/pillars.hip: per-cell segments + arrival rank):
-    # the reproducer replays cleanly, and the guard-band runs of tests/test_gpu_canaries.py find no out-of-bounds write in any kernel
-    # of the encoder, at and beyond its capacities.  The encoder still runs eagerly for a different reason: its launches carry the
-    # raw clouds' lengths (host offsets) as kernel arguments, which a captured graph would freeze.
+    # (voxelise + PFN + scatter; 10 launches) runs eagerly around it: its launches carry the raw clouds' lengths as kernel arguments
+    # (the history of that rule, and the capture protocol: liso_amd/utils/graph_capture.py).
     def _pillars(self, pcls, out=None, prep=None):
         """`out`: (canvas rows [B, gx, gy, 64], occupancy) to write into -- the graph's static inputs (no copy afterwards)"""
-        bev, occ = self.net.model.pfn(pcl_t0=pcls, img_t0=None, out=out, prep=prep)
-        return bev, occ
+        return self.net.model.pfn(pcl_t0=pcls, img_t0=None, out=out, prep=prep)
 
     def _capture(self, pcls, targets):
-        dev = self.device
-        # snapshot FIRST: the shape-probing pillar pass below runs the PFN BatchNorm in training mode and must not count as a batch
-        buffers = {k: v.clone() for k, v in self.net.state_dict().items() if v.is_floating_point() or v.dtype == torch.long}
-        with torch.no_grad():
-            bev, occ = self._pillars(pcls)
-        self._static_bev = bev.detach().clone().requires_grad_(True)
-        self._static_occ = occ.detach().clone()
-        self._static_bev.grad = None
-        self._static_targets = {k: v.to(dev).clone() for k, v in targets.items()}
-        quiet = hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch")
-        if quiet:  # the flat gradient views are created on the default stream, warm-up and capture run on a side stream
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        if self._capture_stream is None:
-            self._capture_stream = side_stream(dev, "flow")  # (the loop trainer lends the same one: SLIM inference's stream)
-        # (MEASURED, removed: the weight gradients as a parallel branch of the captured backward pass -- nothing in the backward chain
-        # reads them.  Results identical; but every fork edge of a replayed hipGraph costs ~240 us here: detector replay 7.15 vs
-        # 2.54 ms (19 forks + 1 join), loop 6.44 vs 4.38 ms per step.)
-        side = self._capture_stream  # (kept alive with the graph)
-        side.wait_stream(torch.cuda.current_stream(dev))
-
         from liso_amd.utils import mfma_conv as MC
 
-        self._pack_jobs = None
-        self._gather_params = None
+        dev = self.device
+        # snapshot FIRST: the shape-probing pillar pass below runs the PFN BatchNorm in training mode and must not count as a batch
+        with GC.frozen_buffers(self.net) as restore:
+            with torch.no_grad():
+                bev, occ = self._pillars(pcls)
+            self._static_bev = bev.detach().clone().requires_grad_(True)
+            self._static_occ = occ.detach().clone()
+            self._static_targets = {k: v.to(dev).clone() for k, v in targets.items()}
+            side = side_stream(dev, "flow")  # (the process's one: in the loop trainer, SLIM inference's stream)
+            self._graph2, self._pack_jobs, self._gather_params = None, [], None
+            cut = self._grad_cut if self.n_grad_buckets == 2 else None
+            rpn = self.net.model.rpn
 
-        cut = self._grad_cut if self.n_grad_buckets == 2 else None
-        rpn = self.net.model.rpn
-
-        def body(part=None):
-            """part None: the whole step; 1: forward + loss + backward down to the cut; 2: the backward pass above the cut"""
-            if part in (None, 1):
-                self._flat_grad.zero_()
-                # (no zeroed gradient buffer for the canvas: with .grad = None autograd keeps the first layer's data gradient as the
-                # leaf's gradient -- a 134-MB fill and a 400-MB accumulation into zeros per step at B = 4 otherwise)
-                self._static_bev.grad = None
-                if self._pack_jobs:  # the forward / data-gradient panels of every layer from ONE launch (recorded in the warm-up)
-                    self._step_packs = MC.batched_pack(self._pack_jobs)
-            MC.set_step_packs(getattr(self, "_step_packs", None))
-            MC.set_direct_grads(True, keep_touched=part == 2)  # gradients of conv / BatchNorm parameters land in the flat buffer without an add each
-            gathered = self._gather_params or []
-            for p_, _ in gathered:  # (autograd then KEEPS the gradient tensor it is handed instead of adding it into the zeroed slice)
-                p_.grad = None
-            try:
-                if part in (None, 1):
-                    rpn.grad_cut = cut
+            def body(part=None):
+                """part None: the whole step; 1: forward + loss + backward down to the cut; 2: the backward pass above the cut"""
+                with _captured_training_pass(self, [self._static_bev], second_half=part == 2):
+                    MC.set_direct_grads(True, keep_touched=part == 2)  # gradients of conv / BatchNorm parameters land in the flat buffer without an add each
                     try:
-                        total, _, _ = self.loss(None, self._static_targets, canvas=(self._static_bev, self._static_occ))
+                        if part in (None, 1):
+                            rpn.grad_cut = cut
+                            try:
+                                total, _, _ = self.loss(None, self._static_targets, canvas=(self._static_bev, self._static_occ))
+                            finally:
+                                rpn.grad_cut = None
+                            self._backward(total)
+                            self._body_loss = total.detach()
+                        if cut is not None and part in (None, 2):
+                            cut.finish()
                     finally:
-                        rpn.grad_cut = None
-                    self._backward(total)
-                    self._body_loss = total.detach()
-                if cut is not None and part in (None, 2):
-                    cut.finish()
-            finally:
-                MC.set_step_packs(None)
-                MC.set_direct_grads(False, keep_touched=True)
-                self._gather_gradients(gathered, add=part == 2)
-            return self._body_loss
+                        MC.set_direct_grads(False, keep_touched=True)
+                return self._body_loss
 
-        self._gather_params = None
-        with torch.cuda.stream(side):  # warm-up off the capture: lazy initialisations, allocator pools
-            MC.record_pack_jobs(True)
-            body()
-            self._pack_jobs = MC.record_pack_jobs(False)
-            # parameters whose gradient no kernel wrote in place during that pass (merged head convolutions, sliced BatchNorm
-            # vectors, block-diagonal filters): autograd would launch one `add_` each into the zeroed flat buffer -- instead
-            # their gradient tensors are collected behind the backward pass by ONE launch (liso_gather_f32)
-            in_place = MC.direct_touched()
-            outside = {id(p_) for p_ in self.net.model.pfn.parameters()}  # (the pillar encoder's backward runs outside the graph)
-            self._gather_params = [(p_, p_.grad) for p_ in self.net.parameters()
-                                   if p_.requires_grad and p_.grad is not None and id(p_) not in in_place and id(p_) not in outside]
-            body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        with torch.no_grad():  # the warm-up passes must not count as training steps (BatchNorm statistics / counters)
-            for k, v in self.net.state_dict().items():
-                if k in buffers:
-                    v.copy_(buffers[k])
-        self._graph, self._graph2 = torch.cuda.CUDAGraph(), None
-        # capture on the warm-up's stream: the AccumulateGrad nodes of the parameters were created there; a capture on another
-        # stream forks into it and the replay computes garbage (measured: loss 63 instead of 1082)
-        if cut is None:
-            with torch.cuda.graph(self._graph, stream=side):
-                self._static_loss = body()
-        else:  # two graphs sharing one memory pool: the second one reads the leaf gradient and the saved tensors of the first
-            with torch.cuda.graph(self._graph, stream=side):
-                self._static_loss = body(1)
-            self._graph2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph2, stream=side, pool=self._graph.pool()):
-                body(2)
-        with torch.no_grad():
-            for k, v in self.net.state_dict().items():
-                if k in buffers:
-                    v.copy_(buffers[k])
-        if quiet:
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(True)
+            def after_first_pass():
+                # parameters whose gradient no kernel wrote in place during that pass (merged head convolutions, sliced BatchNorm
+                # vectors, block-diagonal filters): autograd would launch one `add_` each into the zeroed flat buffer -- instead
+                # their gradient tensors are collected behind the backward pass by ONE launch (liso_gather_f32)
+                in_place = MC.direct_touched()
+                outside = {id(p_) for p_ in self.net.model.pfn.parameters()}  # (the pillar encoder's backward runs outside the graph)
+                self._gather_params = [(p_, p_.grad) for p_ in self.net.parameters()
+                                       if p_.requires_grad and p_.grad is not None and id(p_) not in in_place and id(p_) not in outside]
 
-    def _gather_gradients(self, params, add=False):
-        self._gather_keepalive = gather_gradients(self.device, params, add)
+            GC.warm_up(body, side, pack_jobs=self._pack_jobs, after_first=after_first_pass, restore=restore)
+            if cut is None:
+                self._graph, self._static_loss = GC.capture(body, side)
+            else:  # two graphs sharing one memory pool: the second one reads the leaf gradient and the saved tensors of the first
+                self._graph, self._static_loss = GC.capture(lambda: body(1), side)
+                self._graph2, _ = GC.capture(lambda: body(2), side, pool=self._graph.pool())
 
     def _graph_step(self, pcls, targets, prep=None):
         # what the graph consumes: the [B, 64, gx, gy] canvas (batch size; grid and dtype are fixed per trainer) and the target maps.
@@ -483,22 +459,14 @@ class SlimTrainer:
     live in one flat buffer: data parallelism is one RCCL all-reduce of that buffer after the replay (no DDP wrapper),
     then the eager RMSprop step."""
 
-    def __init__(self, cfg, device, num_train_samples=1000, use_graph=False, channels_last=False, exact=None):
-        """`exact`: True = every fp32 convolution on the native fp32 MFMA (parity configuration), False = bf16 hi/lo pairs (F32X3,
-        the production default), None = leave the process-wide setting (mfma_conv.set_fp32_mode)"""
+    def __init__(self, cfg, device, num_train_samples=1000, use_graph=False, exact=None):
+        """`exact`: the arithmetic of the fp32 convolutions (True: the parity configuration, False: the production default), see
+        `_prepare_device`"""
         from liso_amd.slim.model.slim import SLIM
-        if exact is not None:
-            from liso_amd.utils import mfma_conv as MC
-            MC.set_fp32_mode("exact" if exact else "x3")
+
+        _prepare_device(device, exact)
         self.cfg, self.slim_cfg, self.device = cfg, cfg.SLIM, device
-        if device.type == "cuda":  # (persistent device flag of the sparse canvas convolutions: must exist before the first capture)
-            from liso_amd.utils import mfma_conv as _MC
-            _MC._sparse_flag(device)
         self.net = SLIM(cfg, num_train_samples=num_train_samples).to(device)
-        if channels_last:  # measured slower than NCHW filters on gfx950 (65 vs 59 ms per step): MIOpen's fp32 Winograd is NCHW
-            # the pillar canvas is channels-last storage; keep filters in the same layout so MIOpen's NHWC kernels run
-            # without a transpose before and after every convolution
-            self.net.raft_network.to(memory_format=torch.channels_last)
         self.model = self.net
         self.use_graph = bool(use_graph) and device.type == "cuda"
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -537,9 +505,8 @@ class SlimTrainer:
             # gather launch per 48 tensors moves them into their slices (DetectorTrainer does the same for its few such parameters)
             outside = {id(p) for p in self.net.raft_network.pp_layer.parameters()} if hasattr(self.net.raft_network, "pp_layer") else set()
             self._gather_params = [(p, p.grad) for p in params if id(p) not in outside]
-            if self.world > 1:  # replicas start identical (what the DDP constructor would do)
-                for t in list(self.net.parameters()) + list(self.net.buffers()):
-                    dist.broadcast(t.data, src=0)
+            if self.world > 1:
+                _broadcast_replicas(self.net)
 
     def _inputs(self, sample_t0, sample_t1):
         pc1, m1 = sample_t0["pcl_ta"]["pcl"].to(self.device), sample_t0["pcl_ta"]["pcl_is_valid"].to(self.device)
@@ -623,131 +590,53 @@ class SlimTrainer:
         self.optimizer.step()
         self.lr_scheduler.step()
 
-    # ---- hipGraph path ----------------------------------------------------------------------------------------------
-    @staticmethod
-    def _map_tensors(obj, fn):
-        if torch.is_tensor(obj):
-            return fn(obj)
-        if isinstance(obj, dict):
-            return {k: SlimTrainer._map_tensors(v, fn) for k, v in obj.items()}
-        if isinstance(obj, (list, tuple)):
-            return type(obj)(SlimTrainer._map_tensors(v, fn) for v in obj)
-        return obj
-
-    @staticmethod
-    def _copy_tensors(dst, src, _acc=None):
-        """dst <- src over a tree of tensors: the device-to-device ones as ONE launch (_lib.multi_copy)"""
-        top = _acc is None
-        acc = [] if top else _acc
-        if torch.is_tensor(dst):
-            acc.append((dst, src))
-        elif isinstance(dst, dict):
-            for k in dst:
-                SlimTrainer._copy_tensors(dst[k], src[k], acc)
-        elif isinstance(dst, (list, tuple)):
-            for d, s in zip(dst, src):
-                SlimTrainer._copy_tensors(d, s, acc)
-        if top and acc:
-            L.multi_copy(acc)
-
-    def _signature(self, sample_t0, sample_t1, all_valid):
-        shapes = []
-        self._map_tensors((sample_t0, sample_t1), lambda t: shapes.append((tuple(t.shape), t.dtype)) or t)
-        return (tuple(shapes), all_valid)
-
+    # ---- hipGraph path (the capture protocol and why the encoder and the sorts stay outside: utils/graph_capture.py) --------
     def _capture(self, sample_t0, sample_t1, all_valid):
-        dev = self.device
-        self._static = self._map_tensors((sample_t0, sample_t1), lambda t: t.to(dev).clone())
+        self._static = TT.tree_map((sample_t0, sample_t1), lambda t: t.to(self.device).clone())
         s0, s1 = self._static
-        buffers = {k: v.clone() for k, v in self.net.state_dict().items() if v.is_floating_point() or v.dtype == torch.long}
-        # The pillar encoder stays OUTSIDE the graph (as in DetectorTrainer): a graph that holds its launches faults -- a GPU
-        # memory access fault inside a later replay -- once a few thousand eager launches (the optimizer's, here) have run
-        # between replays (scripts/debug_slim_graph_fault*.py: replays alone, copies, allocations, the scheduler are harmless;
-        # RMSprop.step() with lr = 0 is enough; independent of the convolution backend).  The canvases become graph inputs, their
-        # gradients graph outputs, and the encoder's own backward runs eagerly on them.
-        with torch.no_grad():
-            canv = self._pillars(sample_t0, sample_t1)
-        self._static_canv = tuple(c.detach().clone() for c in canv)
-        for i in (0, 2):
-            self._static_canv[i].requires_grad_(True)
-            self._static_canv[i].grad = None
-        quiet = hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch")
-        if quiet:
-            # the flat gradient views are created on the default stream, warm-up and capture run on side streams
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        side = side_stream(dev, "flow")
-        side.wait_stream(torch.cuda.current_stream(dev))
-        # So does the decoder's point -> cell plan: a torch.sort of 12 x B x N (2.9 M) keys.  A captured torch.sort of more than
-        # ~1 M keys is what makes the replay fault after a few thousand unrelated eager launches (scripts/debug_pillar_graph_fault.py:
-        # 1.0 M keys replay cleanly, 1.5 M fault; rocPRIM's large-input radix sort on this ROCm build) -- the root cause of the
-        # "graph + eager launches" faults of rounds 1-2.  The plan depends on the sweeps only: built eagerly, copied in.
-        self._static_plan = None
-        meta = getattr(self.net, "gather_plan_meta", None)
-        if meta is None:
+        with GC.frozen_buffers(self.net) as restore:  # (before the shape-probing passes)
+            # the pillar encoder stays OUTSIDE the graph (as in DetectorTrainer): its canvases are graph inputs, their gradients outputs
             with torch.no_grad():
-                self.net(s0, s1, None, canvases=self._static_canv)
+                canv = self._pillars(sample_t0, sample_t1)
+            self._static_canv = tuple(c.detach().clone() for c in canv)
+            leaves = [self._static_canv[i].requires_grad_(True) for i in (0, 2)]
+            # so does the decoder's point -> cell plan (a torch.sort of 12 x B x N keys): it depends on the sweeps only
+            self._static_plan = None
             meta = getattr(self.net, "gather_plan_meta", None)
-        if meta is not None:
-            self._static_plan = self.net.build_gather_plan(s0, s1, *meta)
-            self._static_plan.lin64  # (its lazily built int64 copy is a graph input too)
+            if meta is None:
+                with torch.no_grad():
+                    self.net(s0, s1, None, canvases=self._static_canv)
+                meta = getattr(self.net, "gather_plan_meta", None)
+            if meta is not None:
+                self._static_plan = self.net.build_gather_plan(s0, s1, *meta)
+                self._static_plan.lin64  # (its lazily built int64 copy is a graph input too)
+            # several ranks + the dynamicness threshold learned from the loss (static aggregation): its updates all-reduce a histogram
+            # increment each -- a collective cannot sit inside the graph -- so the captured step only RECORDS the per-rank increments and
+            # `_graph_step` reduces and applies them behind the replay (movavg_cls_threshold.py: apply_deferred)
+            thr = self.net.moving_dynamicness_threshold
+            defer = self.world > 1 and bool(self.slim_cfg.model.use_static_aggr_flow_for_aggr_flow)
+            self._thr_items = None
 
-        from liso_amd.utils import mfma_conv as MC
+            def body():
+                with _captured_training_pass(self, leaves):
+                    thr._defer = [] if defer else None
+                    try:
+                        total, _, _ = self.loss(s0, s1, all_valid, canvases=self._static_canv, gather_plan=self._static_plan)
+                        total.backward()
+                    finally:
+                        self._thr_items, thr._defer = thr._defer, None
+                return total.detach()
 
-        self._pack_jobs = None
-
-        # several ranks + the dynamicness threshold learned from the loss (static aggregation): its updates all-reduce a histogram
-        # increment each -- a collective cannot sit inside the graph -- so the captured step only RECORDS the per-rank increments and
-        # `_graph_step` reduces and applies them behind the replay (movavg_cls_threshold.py: apply_deferred)
-        thr = self.net.moving_dynamicness_threshold
-        defer = self.world > 1 and bool(self.slim_cfg.model.use_static_aggr_flow_for_aggr_flow)
-        self._thr_items = None
-
-        def body():
-            self._flat_grad.zero_()
-            for i in (0, 2):  # (autograd keeps the stems' data gradients as the canvases' gradients: no fill, one add less)
-                self._static_canv[i].grad = None
-            if self._pack_jobs:  # every layer's forward / data-gradient panels from ONE launch (recorded in the warm-up)
-                MC.set_step_packs(MC.batched_pack(self._pack_jobs))
-            thr._defer = [] if defer else None
-            for p_, _ in self._gather_params:
-                p_.grad = None
-            try:
-                total, _, _ = self.loss(s0, s1, all_valid, canvases=self._static_canv, gather_plan=self._static_plan)
-                total.backward()
-            finally:
-                MC.set_step_packs(None)
-                self._thr_items, thr._defer = thr._defer, None
-                self._gather_keepalive = gather_gradients(self.device, self._gather_params)
-            return total.detach()
-
-        with torch.cuda.stream(side):  # warm-up off the capture: MIOpen / rocBLAS pick their kernels, caches fill
-            MC.record_pack_jobs(True)
-            body()
-            self._pack_jobs = MC.record_pack_jobs(False)
-            body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        with torch.no_grad():  # the warm-up passes must not count as training steps (BN / threshold statistics)
-            for k, v in self.net.state_dict().items():
-                if k in buffers:
-                    v.copy_(buffers[k])
-        self._graph = torch.cuda.CUDAGraph()
-        # capture on the warm-up's stream: the AccumulateGrad nodes of the parameters live there (a capture on another stream
-        # forks into it: wrong results, measured on the detector step)
-        with torch.cuda.graph(self._graph, stream=side):
-            self._static_loss = body()
-        with torch.no_grad():  # capture does not execute, but restore anyway in case the backend ran eagerly
-            for k, v in self.net.state_dict().items():
-                if k in buffers:
-                    v.copy_(buffers[k])
-        if quiet:  # process-wide switch: only silenced while capturing
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(True)
+            self._pack_jobs = []
+            self._graph, self._static_loss = GC.capture(body, side_stream(self.device, "flow"), warm_ups=2, pack_jobs=self._pack_jobs,
+                                                        restore=restore)
 
     def capture(self, sample_t0, sample_t1):
         """Capture the graph for inputs shaped like these (no collective is issued: callers running several ranks can
         agree on the outcome before the first step).  Raises whatever the runtime raises if capture is refused."""
         _, m1, _, m2 = self._inputs(sample_t0, sample_t1)
         all_valid = (bool(m1.all()), bool(m2.all()))
-        sig = self._signature(sample_t0, sample_t1, all_valid)
+        sig = (TT.tree_signature((sample_t0, sample_t1)), all_valid)
         if self._graph is None or sig != self._graph_sig:
             self._graph = None
             self._capture(sample_t0, sample_t1, all_valid)
@@ -764,7 +653,7 @@ class SlimTrainer:
 
     def _graph_step(self, sample_t0, sample_t1):
         if not self.capture(sample_t0, sample_t1):
-            self._copy_tensors(self._static, (sample_t0, sample_t1))
+            TT.tree_copy_(self._static, (sample_t0, sample_t1))
         canv = self._pillars(sample_t0, sample_t1)  # eager, with autograd: the encoder's parameters get their gradients below
         with torch.no_grad():
             for d, c in zip(self._static_canv, canv):
@@ -796,49 +685,6 @@ class _Prefetched:
 
     def is_for(self, pair):
         return self.pair[0] is pair[0] and self.pair[1] is pair[1]
-
-
-def _packed_inputs(tensors):
-    """static copies of a graph's input tensors as typed views of ONE byte buffer, so that a replay refreshes all of them with a
-    single concatenation launch: -> {"in": {name: view}, "in_flat": uint8 buffer | None, "order": names}.  Segments whose byte size
-    is not a multiple of 16 go last (every view then starts 16-B aligned); tensors that are not contiguous or live elsewhere make
-    the caller fall back to one copy per tensor (in_flat None)."""
-    names = sorted(tensors, key=lambda k: (tensors[k].numel() * tensors[k].element_size()) % 16 != 0)
-    sizes = [tensors[k].numel() * tensors[k].element_size() for k in names]
-    ok = all(tensors[k].is_contiguous() and tensors[k].numel() > 0 for k in names) and sum(1 for z in sizes if z % 16) <= 1
-    if not ok:
-        return {"in": {k: v.clone() for k, v in tensors.items()}, "in_flat": None, "order": names}
-    flat = torch.empty(sum(sizes), dtype=torch.uint8, device=tensors[names[0]].device)
-    views, off = {}, 0
-    for k, z in zip(names, sizes):
-        t = tensors[k]
-        views[k] = flat[off:off + z].view(t.dtype).view(t.shape)
-        views[k].copy_(t)
-        off += z
-    return {"in": views, "in_flat": flat, "order": names}
-
-
-def _pack_tensors(named):
-    """[(name, tensor)] -> (flat uint8 tensor = ONE torch.cat launch, layout) with every segment aligned for its dtype: 8-byte types
-    first, then 4-byte, then the rest"""
-    order = sorted(range(len(named)), key=lambda i: -named[i][1].element_size())
-    layout, parts, off = [], [], 0
-    for i in order:
-        name, t = named[i]
-        t = t.contiguous()
-        u = t.view(torch.uint8) if t.dtype != torch.bool else t.view(torch.uint8)
-        layout.append((name, off, u.numel(), t.dtype, tuple(t.shape)))
-        parts.append(u.reshape(-1))
-        off += u.numel()
-    return torch.cat(parts), layout
-
-
-def _unpack_tensors(flat, layout):
-    out = {}
-    for name, off, nbytes, dtype, shape in layout:
-        seg = flat[off:off + nbytes]
-        out[name] = (seg.view(torch.uint8).view(dtype) if dtype != torch.bool else seg.view(torch.bool)).view(shape)
-    return out
 
 
 class _BatchedTargets(dict):
@@ -893,22 +739,15 @@ class LisoLoopTrainer:
         from liso_amd.slim.model.slim import SLIM
 
         self.cfg, self.device = cfg, device
-        if exact is not None:  # arithmetic of the fp32 convolutions (SLIM; the detector too when compute_dtype is float32)
-            from liso_amd.utils import mfma_conv as MC
-            MC.set_fp32_mode("exact" if exact else "x3")
-        if device.type == "cuda":  # (persistent device flag of the sparse canvas convolutions: must exist before the first capture)
-            from liso_amd.utils import mfma_conv as _MC
-            _MC._sparse_flag(device)
+        _prepare_device(device, exact)  # (`exact`: SLIM's convolutions; the detector's too when compute_dtype is float32)
         self.use_graph = bool(use_graph) and device.type == "cuda"
         self._graph_infer = self.use_graph and use_graph in (True, "infer")
         self._graph_det = self.use_graph and use_graph in (True, "detector")
-        import collections
-        self._infer_graph, self._infer_graphs = None, collections.OrderedDict()
-        self._mine_graphs = collections.OrderedDict()
         self._graph_mine = self.use_graph and use_graph is True
+        sync = lambda: torch.cuda.synchronize(device)  # noqa: E731
+        self._infer_graphs, self._mine_graphs = GC.GraphLRU(sync), GC.GraphLRU(sync)
         # real sweeps differ in their point count from sample to sample: the padded loss clouds are grown to the next multiple of
-        # `infer_point_bucket` rows (NaN rows, pcl_is_valid False, pillar_coors -1: the dataset's own collate padding,
-        # torch_dataset_commons.py:380-431) so that the inference graph's input signature repeats, and at most `max_infer_graphs`
+        # `infer_point_bucket` rows (TT.pad_pcl_ta) so that the inference graph's input signature repeats, and at most `max_infer_graphs`
         # captured graphs (each with its static inputs and a private memory pool) stay resident, least recently used first out
         tcfg = cfg.data.tracking_cfg
         self.infer_point_bucket = int(tcfg.setdefault("infer_point_bucket", 8192))
@@ -949,7 +788,6 @@ class LisoLoopTrainer:
             n_mine = max(1, int(os.environ.get("LISO_MINE_STREAMS", "1")))
             self._mine_streams = [self._mine_stream] + [side_stream(device, f"mine{k}", priority=-1) for k in range(1, n_mine)]
             self._mine_turn = 0
-            self.detector._capture_stream = self._flow_stream
         # compute units the captured SLIM inference's persistent 3x3 convolutions may take while the pipeline overlaps it with the
         # detector step (0 = all): half the chip by default, see _infer_flow_padded
         self.infer_cus = 0
@@ -960,8 +798,7 @@ class LisoLoopTrainer:
                 self.infer_cus = 0
         self._pillar_prep = None  # (clouds, pfn.prepare(clouds), event) of the next detector step
         self._prep_ahead = os.environ.get("LISO_PREP_AHEAD", "1") != "0"
-        tc = cfg.data.tracking_cfg
-        self.pre_nms, self.post_nms = tc.max_num_boxes_before_nms, tc.max_num_boxes_after_nms
+        self.pre_nms, self.post_nms = tcfg.max_num_boxes_before_nms, tcfg.max_num_boxes_after_nms
         self.nms_iou = cfg.setdefault("nms_iou_threshold", 0.1)
 
     @torch.no_grad()
@@ -971,39 +808,21 @@ class LisoLoopTrainer:
         _, boxes = self._targets_from_flow(sample_t0, flow)
         return boxes, flow
 
-    @staticmethod
-    def _stack_samples(samples):
-        """batch of sample dicts (each with batch size 1) -> one sample dict: tensors are concatenated along the batch axis, lists
-        (per-sample clouds of different lengths) are chained, anything else is taken from the first sample"""
-        first = samples[0]
-        if torch.is_tensor(first):
-            return torch.cat(list(samples), dim=0) if first.dim() > 0 else first
-        if isinstance(first, dict):
-            return {k: LisoLoopTrainer._stack_samples([s_[k] for s_ in samples]) for k in first}
-        if isinstance(first, (list, tuple)):
-            return type(first)(x for s_ in samples for x in s_)
-        return first
+    _stack_samples = staticmethod(TT.tree_stack)
 
     def _pad_loss_cloud(self, sample):
-        """the sample with the point axis of `pcl_ta` (NaN rows, pcl_is_valid False, pillar_coors -1: the dataset's own collate padding,
-        torch_dataset_commons.py:380-431) and of `pcl_full_w_ground_ta` (NaN rows at the end: no box contains them) grown to the next
-        multiple of `infer_point_bucket`.  A new dict: the caller's sample is not modified."""
-        pa = sample["pcl_ta"]
-        bk = self.infer_point_bucket
+        """the sample with the point axis of `pcl_ta` (TT.pad_pcl_ta) and of `pcl_full_w_ground_ta` (NaN rows at the end: no box
+        contains them) grown to the next multiple of `infer_point_bucket`.  A new dict: the caller's sample is not modified."""
+        pa, bk = sample["pcl_ta"], self.infer_point_bucket
         n = pa["pcl"].shape[1]
         pad = (-n) % bk if bk > 1 else 0
         full = sample.get("pcl_full_w_ground_ta")
         fpad = (-full.shape[1]) % bk if (bk > 1 and torch.is_tensor(full) and full.dim() == 3) else 0
         if pad == 0 and fpad == 0:
             return sample
-        F = torch.nn.functional
-        out = dict(sample)
-        if pad:
-            out["pcl_ta"] = {**pa, "pcl": F.pad(pa["pcl"], (0, 0, 0, pad), value=float("nan")),
-                             "pcl_is_valid": F.pad(pa["pcl_is_valid"], (0, pad), value=False),
-                             "pillar_coors": F.pad(pa["pillar_coors"], (0, 0, 0, pad), value=-1)}
+        out = {**sample, "pcl_ta": TT.pad_pcl_ta(pa, n + pad)}
         if fpad:
-            out["pcl_full_w_ground_ta"] = F.pad(full, (0, 0, 0, fpad), value=float("nan"))
+            out["pcl_full_w_ground_ta"] = torch.nn.functional.pad(full, (0, 0, 0, fpad), value=float("nan"))
         return out
 
     def _view(self, sample):
@@ -1061,41 +880,31 @@ class LisoLoopTrainer:
     @staticmethod
     def _graph_inputs(sample_t0, sample_t1):
         """what the captured inference reads from the samples (the network-input clouds go through the eager pillar encoder)"""
-        return ({"pcl_ta": sample_t0["pcl_ta"], "gt": {"odom_ta_tb": sample_t0["gt"]["odom_ta_tb"]}},
-                {"pcl_ta": sample_t1["pcl_ta"], "gt": {"odom_ta_tb": sample_t1["gt"]["odom_ta_tb"]}})
+        return tuple({"pcl_ta": s_["pcl_ta"], "gt": {"odom_ta_tb": s_["gt"]["odom_ta_tb"]}} for s_ in (sample_t0, sample_t1))
 
     def _infer_flow_padded(self, sample_t0, sample_t1):
         if not self._graph_infer:
             return self.slim.infer_point_flow_t0_t1(sample_t0, sample_t1)
-        shapes = []
-        # the key holds only what the graph consumes: the padded loss clouds + odometry (the raw clouds' lengths do not enter)
-        SlimTrainer._map_tensors(self._graph_inputs(sample_t0, sample_t1), lambda t: shapes.append((tuple(t.shape), t.dtype)) or t)
-        sig = tuple(shapes)
-        dev = self.device
         from liso_amd.slim.model.slim import get_network_input_pcls
+        from liso_amd.utils import mfma_conv as MC
 
+        dev = self.device
+        ins = self._graph_inputs(sample_t0, sample_t1)
+        # the key holds only what the graph consumes: the padded loss clouds + odometry (the raw clouds' lengths do not enter)
+        sig = TT.tree_signature(ins)
         raft = self.slim.raft_network
         pcls = (get_network_input_pcls(self.cfg, sample_t0, "ta", to_device=dev), get_network_input_pcls(self.cfg, sample_t1, "ta", to_device=dev))
-        st = self._infer_graphs.get(sig)
+        st = self._infer_graphs.lookup(sig)
         with torch.no_grad():  # pillar encoder eagerly (its rocPRIM sort memsets: liso_amd/utils/graph_safety.py) ...
             if st is None:
                 canv = raft.encode_pillars(*pcls)
             else:  # ... straight into the graph's input buffers: no copy, no concatenation of the two sweeps
                 raft.encode_pillars(*pcls, out=st["rows"])
-        with torch.no_grad():  # a device scan (torch.cumsum): eagerly, its memset nodes do not survive in a graph (graph_safety.py)
+            # a device scan (torch.cumsum): eagerly, its memset nodes do not survive in a graph (graph_safety.py)
             thr = self.slim.moving_dynamicness_threshold.value()
-        if st is not None:
-            self._infer_graphs.move_to_end(sig)
         if st is None:
-            if len(self._infer_graphs) >= max(self.max_infer_graphs, 1):
-                torch.cuda.synchronize(dev)  # (replays of the graph that goes may still be in flight on the inference stream)
-            while len(self._infer_graphs) >= max(self.max_infer_graphs, 1):  # least recently used graph + its buffers go
-                _, old = self._infer_graphs.popitem(last=False)
-                if self._infer_graph is old.get("graph"):
-                    self._infer_graph = None
-                old.clear()
-            st = self._infer_graphs[sig] = {}
-            st["in"] = SlimTrainer._map_tensors(self._graph_inputs(sample_t0, sample_t1), lambda t: t.to(dev).clone())
+            st = self._infer_graphs.insert(sig, {}, self.max_infer_graphs)  # (the least recently used graphs + their buffers go)
+            st["in"] = TT.tree_map(ins, lambda t: t.to(dev).clone())
             B_ = canv[0].shape[0]
             rows = torch.cat([canv[0], canv[2]], dim=0).permute(0, 2, 3, 1).contiguous()  # [2B, gx, gy, 64]
             occ = torch.cat([canv[1], canv[3]], dim=0).contiguous()
@@ -1103,8 +912,6 @@ class LisoLoopTrainer:
             st["canv"] = (rows[:B_].permute(0, 3, 1, 2), occ[:B_], rows[B_:].permute(0, 3, 1, 2), occ[B_:], rows.permute(0, 3, 1, 2), occ)
             st["thr"] = thr.clone()
             s0, s1 = st["in"]
-            side = self._flow_stream  # (HIP maps streams onto 4 hardware queues: capture on a pipeline stream, no extra one)
-            side.wait_stream(torch.cuda.current_stream(dev))
             # In the pipeline the captured inference leaves compute units to the other streams (`infer_cus`, LISO_INFER_CUS=n; 0 = all;
             # mfma_conv.roles_cus: its 3x3 convolutions are persistent blocks, one per CU, and a 60-us launch that holds all 256 makes
             # every kernel of the detector step -- the critical path, ~250 small dependent launches -- wait for it to drain).  Measured:
@@ -1112,19 +919,13 @@ class LisoLoopTrainer:
             # the slowest stage); round 6, one box, 40 steps, twice each: all 4.38 / 4.40; 128: 4.25 / 4.27; 160: 4.39 / 4.40; 96: 4.33 /
             # 4.34 (scripts/infer_cus_sweep.sh).  Default since round 6: half the chip; bench.py's `roofline` prices the capped launches
             # against the peak of the CUs they may use.
-            from liso_amd.utils import mfma_conv as MC
-
-            cus = self.infer_cus
-            with torch.cuda.stream(side), torch.no_grad(), MC.roles_cus(cus):
-                for _ in range(2):
-                    self.slim.infer_point_flow_t0_t1(s0, s1, canvases=st["canv"], dynamicness_threshold=st["thr"])
-            torch.cuda.current_stream(dev).wait_stream(side)
-            st["graph"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(st["graph"], stream=side), torch.no_grad(), MC.roles_cus(cus):
-                st["flow"] = self.slim.infer_point_flow_t0_t1(s0, s1, canvases=st["canv"], dynamicness_threshold=st["thr"])
-            self._infer_graph = st["graph"]  # (the most recently captured one: scripts / bench introspection)
+            # (HIP maps streams onto 4 hardware queues: capture on a pipeline stream, no extra one)
+            with torch.no_grad(), MC.roles_cus(self.infer_cus):
+                st["graph"], st["flow"] = GC.capture(
+                    lambda: self.slim.infer_point_flow_t0_t1(s0, s1, canvases=st["canv"], dynamicness_threshold=st["thr"]),
+                    self._flow_stream, warm_ups=2)
         else:
-            SlimTrainer._copy_tensors(st["in"], self._graph_inputs(sample_t0, sample_t1))
+            TT.tree_copy_(st["in"], ins)
             st["thr"].copy_(thr, non_blocking=True)
         st["graph"].replay()
         return st["flow"]
@@ -1134,26 +935,25 @@ class LisoLoopTrainer:
 
     def eager_pass_batch(self, pairs, also=()):
         """`_eager_pass_batch` with the convolution plans the pipelined steps use (the kernels bench.py times are the replayed ones)"""
-        if self.device.type != "cuda":
+        with self._shared_gpu():
             return self._eager_pass_batch(pairs, also)
+
+    def _shared_gpu(self):
         from liso_amd.utils import mfma_conv as MC
 
-        with MC.shared_gpu():
-            return self._eager_pass_batch(pairs, also)
+        return MC.shared_gpu() if self.device.type == "cuda" else contextlib.nullcontext()
 
     def _eager_pass_batch(self, pairs, also=()):
         """the whole iteration on a batch of pairs with eager launches and no parameter update (per-kernel event timing in bench.py).
         `also`: further pairs that join the SLIM inference batch, as in the pipeline's stage A (the kernels are then timed at the
         batch they run at; their launches count len(pairs) / (len(pairs) + len(also)) towards this step)"""
-        from liso_amd import _lib as L
+        from liso_amd.utils import mfma_conv as MC
 
         g, self._graph_infer = self._graph_infer, False
         try:
             allp = [*pairs, *also]
             with torch.no_grad():
                 L.TIMER.weight = len(pairs) / len(allp)  # (these launches serve len(allp) pairs, the step consumes len(pairs))
-                from liso_amd.utils import mfma_conv as MC
-
                 try:  # (the plans of the captured inference: the same compute-unit cap as in _infer_flow_padded)
                     with MC.roles_cus(self.infer_cus):
                         flow = self._infer_flow_padded(self._stack_infer_views([p_[0] for p_ in allp]), self._stack_infer_views([p_[1] for p_ in allp]))
@@ -1189,7 +989,7 @@ class LisoLoopTrainer:
         # (one captured graph -- static inputs, intermediates, packed output -- per mining stream: replays on different streams run
         # concurrently and must not share buffers)
         sig = (side.cuda_stream,) + tuple((k, tuple(t.shape), t.dtype) for k, t in ins.items())
-        st = self._mine_graphs.get(sig)
+        st = self._mine_graphs.lookup(sig)
         # the budget is a RATE -- at most `mine_capture_budget` captures per `mine_capture_window` mining calls -- so a signature that
         # was evicted from the LRU can be captured again later; a lifetime budget (round 4) left every non-resident signature on the
         # eager path for the rest of a long run
@@ -1208,42 +1008,31 @@ class LisoLoopTrainer:
             targets, boxes = self._targets_from_flow(sample_t0, flow, capacity=self.box_capacity)
             return targets, boxes, self.cluster_detector.last_num_labels.max().reshape(1)
         if st is not None:
-            self._mine_graphs.move_to_end(sig)
             if st["in_flat"] is not None:  # every input into the captured buffers with ONE launch (a byte-wise concatenation)
-                parts = [ins[k].reshape(-1).view(torch.uint8) for k in st["order"]]
-                assert sum(p_.numel() for p_ in parts) == st["in_flat"].numel()  # (cat(out=) would silently resize the static buffer)
-                torch.cat(parts, out=st["in_flat"])
+                TT.pack_into(st["in_flat"], st["in_layout"], ins)
             else:
                 for k, t in ins.items():
                     st["in"][k].copy_(t, non_blocking=True)
         else:
-            if len(self._mine_graphs) >= max(self.max_mine_graphs, 1):
-                torch.cuda.synchronize(dev)  # (replays of the graph that goes may still be in flight on a mining stream)
-            while len(self._mine_graphs) >= max(self.max_mine_graphs, 1):
-                self._mine_graphs.popitem(last=False)[1].clear()
+            st = self._mine_graphs.insert(sig, {}, self.max_mine_graphs)
             self.mine_captures += 1
             self._mine_capture_calls.append(self._mine_calls)
-            st = self._mine_graphs[sig] = _packed_inputs(ins)
-            si = st["in"]
+            si, st["in_flat"], st["in_layout"] = TT.packed_statics(ins)
+            st["in"] = si
             sample = {"pcl_ta": {"pcl": si["pcl"], "pcl_is_valid": si["valid"], "pillar_coors": si["coors"]},
                       "pcl_full_w_ground_ta": si["full"], "src_trgt_time_delta_s": si["dt"],
                       self.cfg.data.odom_source: {"odom_ta_tb": si["odom"]}}
 
             def body():
                 targets, boxes = self._targets_from_flow(sample, si["flow"], capacity=self.box_capacity, padded=True)
-                named = [("t_" + k, t) for k, t in targets.items()] + \
-                    [("b_" + k, t) for k, t in boxes.__dict__.items() if torch.is_tensor(t)] + \
-                    [("n_clusters", self.cluster_detector.last_num_labels.max().reshape(1))]
-                return _pack_tensors(named)
+                return TT.pack([("t_" + k, t) for k, t in targets.items()] +
+                               [("b_" + k, t) for k, t in boxes.__dict__.items() if torch.is_tensor(t)] +
+                               [("n_clusters", self.cluster_detector.last_num_labels.max().reshape(1))])
 
-            with torch.no_grad():
-                for _ in range(2):  # warm-up on the capture stream: lazy initialisations, allocator pools
-                    body()
-                st["graph"] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(st["graph"], stream=side):
-                    st["flat"], st["layout"] = body()
+            with torch.no_grad():  # (`side` is the current stream: warm-up and capture stay on it)
+                st["graph"], (st["flat"], st["layout"]) = GC.capture(body, side, warm_ups=2)
         st["graph"].replay()
-        out = _unpack_tensors(st["flat"].clone(), st["layout"])
+        out = TT.unpack(st["flat"].clone(), st["layout"])
         targets = {k[2:]: t for k, t in out.items() if k.startswith("t_")}
         boxes = Shape(**{k[2:]: t for k, t in out.items() if k.startswith("b_")})
         return targets, boxes, out["n_clusters"]
@@ -1321,11 +1110,7 @@ class LisoLoopTrainer:
     def _same_shapes(self, pa, pb):
         """can the two pairs share one inference batch?  What the captured inference consumes -- the loss clouds and the odometry --
         must agree in everything but the (bucket-padded) point count, which `_stage_a` levels to the largest bucket of the batch."""
-        def sig(pair):
-            out = []
-            SlimTrainer._map_tensors(self._graph_inputs(self._infer_view(pair[0]), self._infer_view(pair[1])),
-                                     lambda t: out.append((tuple(t.shape[:1]) + tuple(t.shape[2:]), t.dtype)) or t)
-            return out
+        sig = lambda pair: TT.tree_signature(self._graph_inputs(self._infer_view(pair[0]), self._infer_view(pair[1])), skip_dim=1)  # noqa: E731
         return sig(pa) == sig(pb)
 
     def _stack_infer_views(self, samples):
@@ -1337,14 +1122,7 @@ class LisoLoopTrainer:
     @staticmethod
     def _grow_view(view, n):
         """an inference view with its loss cloud padded further, to `n` rows"""
-        pa = view["pcl_ta"]
-        pad = n - pa["pcl"].shape[1]
-        if pad == 0:
-            return view
-        F = torch.nn.functional
-        return {**view, "pcl_ta": {**pa, "pcl": F.pad(pa["pcl"], (0, 0, 0, pad), value=float("nan")),
-                                   "pcl_is_valid": F.pad(pa["pcl_is_valid"], (0, pad), value=False),
-                                   "pillar_coors": F.pad(pa["pillar_coors"], (0, 0, 0, pad), value=-1)}}
+        return {**view, "pcl_ta": TT.pad_pcl_ta(view["pcl_ta"], n)}
 
     @staticmethod
     def _take(store, pair):
@@ -1409,11 +1187,7 @@ class LisoLoopTrainer:
 
     def step_batch(self, pairs, upcoming=(), inputs_ready=None):
         """`_step_batch` with the convolution plans of a shared GPU (the three pipeline stages run next to each other)"""
-        if self.device.type != "cuda":
-            return self._step_batch(pairs, upcoming)
-        from liso_amd.utils import mfma_conv as MC
-
-        with MC.shared_gpu():
+        with self._shared_gpu():
             return self._step_batch(pairs, upcoming, inputs_ready)
 
     def _step_batch(self, pairs, upcoming=(), inputs_ready=None):
