@@ -311,6 +311,13 @@ SIGNATURES = {
     "liso_bev_free_mask": (_i, [_vp, ctypes.c_long, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "liso_bev_select_free_cells": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "liso_snippet_paste": (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _i, _vp, _vp, _vp, _vp]),
+    # include/liso_sample_prep.h
+    "liso_sample_transform_f32": (_i, [_i, _i, _i] + [_vp] * 7),
+    "liso_sample_transform_poses_f64": (_i, [_i, _vp, _vp, _i, _vp, _i, _vp]),
+    "liso_bev_crop_workspace_bytes": (_sz, [_i, _i]),
+    "liso_bev_crop_f32": (_i, [_vp] * 14 + [_sz, _vp]),
+    "liso_bev_point_maps_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "liso_bev_point_maps_f32": (_i, [_i] * 5 + [_vp] * 6 + [ctypes.c_double] + [_vp] * 5 + [_sz, _vp]),
 }
 
 

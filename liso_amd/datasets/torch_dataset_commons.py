@@ -5,6 +5,19 @@ import numpy as np
 import torch
 
 from liso_amd.datasets.nuscenes.analyse_boxes import voxelize_pcl
+from liso_amd.datasets.sample_prep import (  # noqa: F401  (:743-902, :1147-1223, :1291-1483, :1870-1899)
+    add_bev_flow,
+    add_bev_ground_height_occupancy_maps,
+    assemble_bev_sample,
+    augment_sample_content,
+    get_augmentation_transform,
+    moving_mask,
+    pillarize_bev,
+    transform_boxes,
+    transform_flow,
+    transform_odometry,
+    transform_pcl_maybe_with_intensity,
+)
 from liso_amd.datasets.targets import render_center_targets  # noqa: F401  (draw_heat_regression_maps, :190-339)
 from liso_amd.kabsch.shape_utils import Shape
 from liso_amd.tracker.box_points import FP64_PRODUCT, dense_boxes, points_in_boxes
