@@ -318,6 +318,12 @@ SIGNATURES = {
     "liso_bev_crop_f32": (_i, [_vp] * 14 + [_sz, _vp]),
     "liso_bev_point_maps_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "liso_bev_point_maps_f32": (_i, [_i] * 5 + [_vp] * 6 + [ctypes.c_double] + [_vp] * 5 + [_sz, _vp]),
+    # include/liso_label_prep.h
+    "liso_box_has_points_f32": (_i, [_i] * 4 + [_vp] * 7),
+    "liso_filter_boxes": (_i, [_vp] * 6 + [_i] + [_vp] * 3),
+    "liso_object_velocity_f64": (_i, [_i, _i] + [_vp] * 5),
+    "liso_ignore_region_mask": (_i, [_i] * 4 + [ctypes.c_double] * 2 + [_vp] * 6),
+    "liso_render_center_targets_ex_f32": (_i, [_vp] * 15),
 }
 
 

@@ -5,6 +5,14 @@ import numpy as np
 import torch
 
 from liso_amd.datasets.nuscenes.analyse_boxes import voxelize_pcl
+from liso_amd.datasets.label_prep import (  # noqa: F401  (:190-339, :793-876, :904-941, :1013-1059, :1116-1145)
+    assemble_box_labels,
+    create_true_where_ignore_region_mask,
+    draw_heat_regression_maps,
+    filter_objects_to_bev_non_empty,
+    object_velocity_in_obj_coords,
+    select_centermaps_target_confidence,
+)
 from liso_amd.datasets.sample_prep import (  # noqa: F401  (:743-902, :1147-1223, :1291-1483, :1870-1899)
     add_bev_flow,
     add_bev_ground_height_occupancy_maps,
