@@ -324,6 +324,9 @@ SIGNATURES = {
     "liso_object_velocity_f64": (_i, [_i, _i] + [_vp] * 5),
     "liso_ignore_region_mask": (_i, [_i] * 4 + [ctypes.c_double] * 2 + [_vp] * 6),
     "liso_render_center_targets_ex_f32": (_i, [_vp] * 15),
+    # include/liso_snippets.h
+    "liso_snippet_cut_workspace_bytes": (_sz, [_i, _i, _i]),
+    "liso_snippet_cut_f32": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _lg] + [_vp] * 5 + [_sz, _vp]),
 }
 
 

@@ -50,6 +50,30 @@ class BoxSnippetDb:
         self.lidar_rows = [np.asarray(r) for r in db["lidar_rows"]] if "lidar_rows" in db else None
         self.box_T_sensor = db.get("box_T_sensor")
 
+    @classmethod
+    def from_device(cls, points, offsets, boxes, lidar_rows=None, box_T_sensor=None):
+        """Adopts snippets that already lie concatenated in HBM (liso_amd/tracker/snippet_harvest.py), without a copy of the points:
+        `points` float32 [P, 4] on the device, `offsets` int64 [M + 1] (snippet i owns rows offsets[i]:offsets[i + 1]), `boxes` a Shape
+        [M], `lidar_rows` the per-point rows as one array [P] (device or host; the ray-drop draws are made on the host, so they are
+        read here, once) or a list of M arrays."""
+        assert torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float32, "from_device takes the device buffer"
+        assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous(), points.shape
+        db = cls.__new__(cls)
+        db.offsets = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets).astype(np.int64)
+        db.counts = np.diff(db.offsets)
+        assert len(db.counts) > 0 and db.offsets[0] == 0 and db.offsets[-1] == points.shape[0] and np.all(db.counts >= 0), db.offsets
+        db.device = points.device
+        db.points = points
+        db.boxes = boxes.clone().cpu() if torch.is_tensor(boxes.pos) else boxes.to_tensor()
+        assert db.boxes.pos.shape[0] == len(db.counts), (db.boxes.pos.shape, len(db.counts))
+        if lidar_rows is not None and not isinstance(lidar_rows, (list, tuple)):
+            rows = lidar_rows.cpu().numpy() if torch.is_tensor(lidar_rows) else np.asarray(lidar_rows)
+            assert rows.shape == (points.shape[0],), rows.shape
+            lidar_rows = [rows[db.offsets[i]:db.offsets[i + 1]] for i in range(len(db.counts))]
+        db.lidar_rows = [np.asarray(r) for r in lidar_rows] if lidar_rows is not None else None
+        db.box_T_sensor = box_T_sensor
+        return db
+
     def __len__(self):
         return len(self.counts)
 

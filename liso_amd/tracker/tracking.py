@@ -1,8 +1,12 @@
 """Inner loops of box mining / tracking: mirrors of liso/tracker/tracking.py with the
 points-in-boxes passes on the HIP kernel (include/liso_tracking.h)."""
+from typing import Dict, List, Union
+
+import numpy as np
 import torch
 
 from liso_amd.kabsch.shape_utils import Shape, extract_box_motion_transform_without_sensor_odometry
+from liso_amd.utils.torch_transformation import torch_decompose_matrix
 from liso_amd.tracker.box_points import FP32_PRODUCT, FP64_PRODUCT, dense_boxes, points_in_boxes
 
 
@@ -128,3 +132,55 @@ def perform_local_box_refinement(cfg, box_predictor, point_clouds_sensor_cosy, b
             if fcfg.fit_pos:
                 seq.pos[t, :2] = torch.where(has, fit[0, :2].to(seq.pos.dtype), seq.pos[t, :2])
     return set_box_size_keep_closest_point_constant(seq, refined_box_dims)
+
+
+# ---- world <-> sensor box sequences and the keep / drop decision of a track (reference tracking.py:263-316, 2214-2259) -----------------
+def _poses_of_frames(w_T_sensor_ti, n):
+    """the sensor poses of the n frames of a track as one fp64 [n, 4, 4] tensor (the reference is handed a list or a tensor)"""
+    T = torch.stack(list(w_T_sensor_ti)) if isinstance(w_T_sensor_ti, (list, tuple)) else w_T_sensor_ti
+    assert len(T) == n, (len(T), n)
+    return T
+
+
+def _assert_same_sequence(box_sequence_sensor: Shape, box_sequence_world: Shape):
+    box_sequence_sensor.assert_attr_shapes_compatible()
+    box_sequence_world.assert_attr_shapes_compatible()
+    assert box_sequence_sensor.shape == box_sequence_world.shape, (box_sequence_sensor.shape, box_sequence_world.shape)
+
+
+def update_world_boxes_from_sensor_boxes(*, box_sequence_sensor: Shape, box_sequence_world: Shape, w_T_sensor_ti: List[torch.DoubleTensor]):
+    """reference :263-287, in place on `box_sequence_world`: w_T_box = w_T_sensor @ sensor_T_box per frame, dims and probs taken over"""
+    w_T_s = _poses_of_frames(w_T_sensor_ti, box_sequence_sensor.shape[0])
+    _assert_same_sequence(box_sequence_sensor, box_sequence_world)
+    box_sequence_world.dims = box_sequence_sensor.dims
+    box_sequence_world.pos, box_sequence_world.rot = torch_decompose_matrix(w_T_s @ box_sequence_sensor.get_poses())
+    box_sequence_world.probs = box_sequence_sensor.probs
+    return box_sequence_world
+
+
+def update_sensor_boxes_from_world_boxes(*, box_sequence_world: Shape, box_sequence_sensor: Shape, w_T_sensor_ti: List[torch.DoubleTensor]):
+    """reference :290-316, in place on `box_sequence_sensor`: sensor_T_box = inv(w_T_sensor) @ w_T_box per frame, probs taken over (the
+    dims are not: the reference leaves them)"""
+    w_T_s = _poses_of_frames(w_T_sensor_ti, box_sequence_sensor.shape[0])
+    _assert_same_sequence(box_sequence_sensor, box_sequence_world)
+    box_sequence_sensor.pos, box_sequence_sensor.rot = torch_decompose_matrix(torch.linalg.inv(w_T_s) @ box_sequence_world.get_poses())
+    box_sequence_sensor.probs = box_sequence_world.probs
+    return box_sequence_sensor
+
+
+def decide_keep_or_drop_box(*, tracking_cfg: Dict[str, float], box_sequence_world_for_specific_track_id: Shape, min_track_obj_speed_mps: float,
+                            track_id: Union[int, torch.IntTensor], time_between_frames_s: Union[float, np.ndarray], verbose: bool,
+                            is_flow_cluster_detector: bool):
+    """reference :2214-2259 -> (keep, total_dist_covered_m): a track is kept when its end-to-end BEV displacement over its duration
+    reaches the minimum speed (filter off at 0) and, for flow-cluster boxes, the minimum travel distance"""
+    track_coors, _ = torch_decompose_matrix(box_sequence_world_for_specific_track_id.get_poses())
+    coors_xy = track_coors[:, 0:2].cpu().numpy()
+    total_dist_covered_m = np.linalg.norm(coors_xy[-1] - coors_xy[0])
+    keep = True
+    if min_track_obj_speed_mps > 0.0:
+        keep = total_dist_covered_m / (len(coors_xy) * time_between_frames_s) >= min_track_obj_speed_mps
+    if keep and is_flow_cluster_detector:
+        keep = keep and total_dist_covered_m >= tracking_cfg.flow_cluster_detector_min_travel_dist_filter_m
+    if verbose:
+        print(f"{'Keep' if keep else 'Drop'}: Track ID: {track_id}")
+    return keep, total_dist_covered_m
