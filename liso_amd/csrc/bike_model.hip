@@ -9,8 +9,11 @@
 
 #include "../../include/liso_iou3d.h"
 #include "../../include/liso_tracking.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 constexpr float kPi = 3.14159265358979323846f;
 
@@ -81,8 +84,6 @@ __global__ void bike_rollout_bwd_kernel(int batch, int steps, const float* __res
     }
     ginit[5 * b] = gx; ginit[5 * b + 1] = gy; ginit[5 * b + 2] = gh; ginit[5 * b + 3] = gv; ginit[5 * b + 4] = ghd;
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 }  // namespace
 

@@ -14,9 +14,12 @@
 #include "../../include/liso_bn.h"
 #include "../../include/liso_iou3d.h"
 #include "chain_bodies.h"
+#include "dev_common.h"
 #include "elem16.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 constexpr int kThreads = 256;
 constexpr int kRowsPerBlock = 128;
@@ -395,8 +398,6 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_dx_kernel(const T* __restrict
         Vec<T>::store(dx + r * g.ds + col * V, vg);
     }
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 inline bool geom(int c, int v, long m, Geom* g, int* nblk) {
     if (c <= 0 || c % v != 0 || c > kThreads) return false;

@@ -16,16 +16,17 @@
 
 #include "../../include/liso_box_mining.h"
 #include "../../include/liso_iou3d.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 constexpr int kScanThreads = 256;
 constexpr int kScanPer = 8;                            // elements per thread
 constexpr int kScanChunk = kScanThreads * kScanPer;    // elements per block
 constexpr int32_t kUnknownClass = 2147483647;          // shape_utils.py:15
 constexpr int32_t kInvalidClass = kUnknownClass - 1;   // shape_utils.py:16
-
-int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 // ---- scan -----------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int block_exclusive_scan(int v, int* total) {

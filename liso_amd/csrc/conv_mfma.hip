@@ -29,10 +29,13 @@
 #include "../../include/liso_conv.h"
 #include "../../include/liso_iou3d.h"
 #include "conv_plan.h"
+#include "dev_common.h"
 #include "elem16.h"
 #include "per_device.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef float f16v __attribute__((ext_vector_type(16)));
@@ -1665,8 +1668,6 @@ __global__ __launch_bounds__(256) void residual_affine_relu_kernel(const float4*
         out[i] = make_float4(fmaxf(va.x + vb.x, 0.f), fmaxf(va.y + vb.y, 0.f), fmaxf(va.z + vb.z, 0.f), fmaxf(va.w + vb.w, 0.f));
     }
 }
-
-int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 template <int MODE, int MI, int NJ, bool OUT_F32, int NTAPS, bool PRO>
 int launch_roles_pro(const liso_conv_desc& d, const Plan& p, hipStream_t st) {

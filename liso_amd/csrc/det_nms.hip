@@ -20,10 +20,13 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "dev_common.h"
 #include "rbev_geom.h"
 #include "../../include/liso_det_nms.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 using namespace liso_rbev;
 
@@ -322,8 +325,6 @@ __global__ __launch_bounds__(256) void det_nms_gather_kernel(int n, int post, co
         default: gather_rows<uint64_t>(f, b, n, post, count, kb); break;
     }
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 struct SortWs {
     uint32_t* keys;

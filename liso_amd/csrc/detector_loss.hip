@@ -11,8 +11,12 @@
 
 #include "../../include/liso_detector.h"
 #include "../../include/liso_iou3d.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
+using liso_dev::shfl_xor_f64;
 
 constexpr int kThreads = 256;
 constexpr int NS = LISO_CENTERLOSS_NSUM;
@@ -51,13 +55,6 @@ __device__ __forceinline__ Pixel load_pixel(const liso_centerloss_cfg& c, const 
     p.dec_pos[1] = cy + c.res_y * 0.5f * p.tp[1];
     p.dec_pos[2] = c.z_min + 0.5f * (p.tp[2] + 1.0f) * (c.z_max - c.z_min);
     return p;
-}
-
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, m);
-    hi = __shfl_xor(hi, m);
-    return __hiloint2double(hi, lo);
 }
 
 __global__ __launch_bounds__(kThreads) void centerloss_partial_kernel(liso_centerloss_cfg c, Maps m, const float* __restrict__ gt_probs,
@@ -277,7 +274,6 @@ __global__ __launch_bounds__(256) void targets_render_kernel(liso_targets_cfg c,
     center_mask[i] = (uint8_t)center;
 }
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 inline int n_blocks(const liso_centerloss_cfg* c) {
     const long n = (long)c->batch * c->h * c->w;
     const long b = (n + kThreads - 1) / kThreads;

@@ -13,8 +13,11 @@
 
 #include "../../include/liso_flow_cluster.h"
 #include "../../include/liso_iou3d.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 constexpr double kFix = 16777216.0;  // 2^24 fixed-point scale: 6e-8 m resolution, |sum| < 5e11 m fits int64
 
@@ -233,8 +236,6 @@ __global__ void odom_inverse_minus_eye_kernel(const double* __restrict__ m_all, 
     o[14] = (-a30 * s3 + a31 * s1 - a32 * s0) * inv;
     o[15] = (a20 * s3 - a21 * s1 + a22 * s0) * inv - 1.0;
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 inline int fit_blocks(int n) {
     const int tiles = (n + kFitTile - 1) / kFitTile;

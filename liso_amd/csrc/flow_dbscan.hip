@@ -29,8 +29,11 @@
 
 #include "../../include/liso_flow_cluster.h"
 #include "../../include/liso_iou3d.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 struct Cfg {
     int batch, gx, gy, win, min_samples;
@@ -470,7 +473,6 @@ __global__ void region_props_kernel(const unsigned long long* __restrict__ mom, 
     p[0] = cr; p[1] = cc; p[2] = orientation; p[3] = 4.0 * sqrt(l1); p[4] = 4.0 * sqrt(l2);
 }
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 inline bool cfg_ok(const liso_dbscan_cfg* c) {
     return c && c->batch >= 1 && c->gx >= 1 && c->gy >= 1 && c->window >= 0 && c->min_samples >= 1 && c->eps > 0.f &&
            (long)c->gx * c->gy < (1L << 31);

@@ -18,9 +18,16 @@
 
 #include "../../include/liso_box_mining.h"
 #include "../../include/liso_ground.h"
+#include "dev_common.h"
 #include "per_device.h"
 
 namespace {
+
+using liso_dev::Carver;
+using liso_dev::check_launch;
+using liso_dev::cloud_rows;
+using liso_dev::to_i32;
+using liso_dev::up256;
 
 constexpr int kThreads = 256;
 constexpr int kNb = 24;
@@ -47,8 +54,6 @@ struct Dims {
     size_t lab_stride;  // H*W rounded up to 16
 };
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 // 0 = fine, else the error code
 int read_cfg(const liso_ground_cfg* c, Dims* d) {
     if (!c) return LISO_EINVAL;
@@ -69,29 +74,22 @@ int read_cfg(const liso_ground_cfg* c, Dims* d) {
 
 Tables carve(const Dims& d, void* base) {
     Tables t;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = (char*)base + off;
-        off += up256(bytes);
-        return (void*)p;
-    };
+    Carver ws{base};
     const size_t B = d.B, N = d.N, WH = (size_t)d.W * d.H, WL = (size_t)d.W * d.L;
-    t.ele_key = (unsigned long long*)take(B * 2 * sizeof(unsigned long long));
-    t.ele = (double*)take(B * N * sizeof(double));
-    t.pix = (int32_t*)take(B * N * sizeof(int32_t));
-    t.widx = (int32_t*)take(B * WH * sizeof(int32_t));
-    t.minz_key = (uint32_t*)take(B * WL * sizeof(uint32_t));
-    t.minz = (double*)take(B * WL * sizeof(double));
-    t.lab0 = (uint8_t*)take(B * d.lab_stride);
-    t.lab1 = (uint8_t*)take(B * d.lab_stride);
-    t.row_cnt = (int32_t*)take(B * d.H * sizeof(int32_t));
-    t.cols = (int32_t*)take(B * WH * sizeof(int32_t));
-    t.wts = (double*)take(B * WH * kNb * sizeof(double));
-    t.bytes = off;
+    t.ele_key = ws.take<unsigned long long>(B * 2);
+    t.ele = ws.take<double>(B * N);
+    t.pix = ws.take<int32_t>(B * N);
+    t.widx = ws.take<int32_t>(B * WH);
+    t.minz_key = ws.take<uint32_t>(B * WL);
+    t.minz = ws.take<double>(B * WL);
+    t.lab0 = ws.take<uint8_t>(B * d.lab_stride);
+    t.lab1 = ws.take<uint8_t>(B * d.lab_stride);
+    t.row_cnt = ws.take<int32_t>(B * d.H);
+    t.cols = ws.take<int32_t>(B * WH);
+    t.wts = ws.take<double>(B * WH * kNb);
+    t.bytes = ws.bytes;
     return t;
 }
-
-int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 // ---- order-preserving integer keys ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t key_f32(float v) {
@@ -107,16 +105,9 @@ __device__ __forceinline__ double unkey_f64(unsigned long long k) {
     return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
 }
 
-// numpy's astype(int32) of a float64: truncation, INT_MIN for NaN and for values outside int32
-__device__ __forceinline__ int to_i32(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
 // Python's min(a, b)
 __device__ __forceinline__ double pymin(double a, double b) { return b < a ? b : a; }
 
-__device__ __forceinline__ int cloud_rows(const int32_t* counts, int b, int N) {
-    if (!counts) return N;
-    const int n = counts[b];
-    return n < 0 ? 0 : (n > N ? N : n);
-}
 
 __device__ __forceinline__ bool load_point(const float* pcl, const int32_t* counts, int b, int i, int N, int stride, double* x, double* y,
                                            double* z, float* zf) {

@@ -22,6 +22,7 @@
 // sin/cos are evaluated in double and rounded to float, which matches glibc's sinf/cosf in practice.
 #include <hip/hip_runtime.h>
 #include "zero_fill.h"
+#include "dev_common.h"
 #include "rbev_geom.h"
 #include <math.h>
 #include <stdint.h>
@@ -29,6 +30,8 @@
 #include "../../include/liso_iou3d.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 constexpr int kCols = 64;        // columns per tile == wavefront width == bits per mask word
 constexpr int kRows = 16;        // rows per tile
@@ -212,8 +215,6 @@ __global__ __launch_bounds__(kGreedyThreads) void nms_greedy_kernel(const unsign
     }
     if (tid == 0) *num_out = total;
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 template <int MODE>
 int launch_pair_matrix(const float* a, int n, const float* b, int m, float* out, void* stream) {

@@ -17,8 +17,11 @@
 
 #include "../../include/liso_iou3d.h"
 #include "../../include/liso_kabsch.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 128;            // points per tile (32 per wave in phase B)
@@ -392,8 +395,6 @@ __global__ void symm_ortho_bwd_kernel(const double* __restrict__ g, const double
             ga[(size_t)i * 9 + p * 3 + q] = s;
         }
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 inline bool cfg_ok(const liso_kabsch_cfg* c) {
     return c && c->batch >= 1 && c->n_points >= 0 && c->n_slots >= 0 && c->point_stride >= 3 && c->flow_stride >= 2 &&

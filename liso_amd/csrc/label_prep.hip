@@ -13,23 +13,21 @@
 #include <stdint.h>
 
 #include "../../include/liso_label_prep.h"
+#include "dev_common.h"
+#include "zero_fill.h"
 
 namespace {
+
+using liso_dev::affine_inv;
+using liso_dev::check_launch;
+using liso_dev::cloud_rows;
+using liso_dev::distinct;
+using liso_dev::mat4_mul;
+using liso_dev::to_i32;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kChunk = 256;  // boxes resident in LDS at a time
-
-int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
-
-__device__ __forceinline__ int cloud_rows(const int32_t* counts, int b, int N) {
-    if (!counts) return N;
-    const int n = counts[b];
-    return n < 0 ? 0 : (n > N ? N : n);
-}
-
-// numpy's astype(int32) of a float64: truncation, INT_MIN for NaN and for values outside int32
-__device__ __forceinline__ int to_i32(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
 
 __device__ __forceinline__ double cell_center(int i, int n, double range) { return (((double)i + 0.5) / (double)n) * range - 0.5 * range; }
 
@@ -38,11 +36,6 @@ struct BoxFrame {
     float r0[3], r1[3], tz;  // fp32 inverse pose: rows 0 and 1 as (a, b, t), row 2 as its translation
     double hx, hy, hz;       // half extents
 };
-
-__global__ __launch_bounds__(kThreads) void zero_flags_kernel(size_t n, uint32_t* flags) {
-    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i < n) flags[i] = 0u;
-}
 
 __global__ __launch_bounds__(kThreads) void has_points_kernel(int K, int N, int stride, const double* __restrict__ box_pos,
                                                               const double* __restrict__ box_dims, const double* __restrict__ box_rot,
@@ -142,28 +135,6 @@ __global__ __launch_bounds__(kThreads) void filter_boxes_kernel(liso_box_filter_
 }
 
 // ---- 3. object velocity -----------------------------------------------------------------------------------------------------------
-__device__ void mat4_mul(const double* A, const double* B, double* C) {
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c)
-            C[4 * r + c] = ((A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c]) + A[4 * r + 3] * B[12 + c];
-}
-
-// inverse of an affine matrix [A t; 0 0 0 1]: adjugate(A) / det(A), -A^-1 t
-__device__ void affine_inv(const double* M, double* R) {
-    const double a = M[0], b = M[1], c = M[2], d = M[4], e = M[5], f = M[6], g = M[8], h = M[9], k = M[10];
-    const double c00 = e * k - f * h, c01 = c * h - b * k, c02 = b * f - c * e;
-    const double c10 = f * g - d * k, c11 = a * k - c * g, c12 = c * d - a * f;
-    const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
-    const double det = (a * c00 + b * c10) + c * c20;
-    const double inv[9] = {c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det};
-    const double tx = M[3], ty = M[7], tz = M[11];
-    for (int r = 0; r < 3; ++r) {
-        R[4 * r] = inv[3 * r], R[4 * r + 1] = inv[3 * r + 1], R[4 * r + 2] = inv[3 * r + 2];
-        R[4 * r + 3] = -((inv[3 * r] * tx + inv[3 * r + 1] * ty) + inv[3 * r + 2] * tz);
-    }
-    R[12] = 0.0, R[13] = 0.0, R[14] = 0.0, R[15] = 1.0;
-}
-
 __global__ __launch_bounds__(64) void velocity_kernel(int K, const double* __restrict__ odom, const double* __restrict__ pose_ta,
                                                       const double* __restrict__ pose_tb, double* __restrict__ out) {
     const int b = blockIdx.y, k = blockIdx.x * 64 + threadIdx.x;
@@ -354,8 +325,6 @@ __global__ __launch_bounds__(kThreads) void targets_ex_render_kernel(liso_target
     center_mask[at] = center ? 1 : 0;
 }
 
-bool distinct(const void* a, const void* b, size_t n) { return (const char*)a + n <= (const char*)b || (const char*)b + n <= (const char*)a; }
-
 }  // namespace
 
 extern "C" {
@@ -367,8 +336,7 @@ int liso_box_has_points_f32(int batch, int n_boxes, int n_max, int point_stride,
     if (n_boxes == 0) return LISO_OK;
     if (!box_pos || !box_dims || !box_rot || !flags || (n_max > 0 && !pcl)) return LISO_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const size_t words = (size_t)batch * n_boxes;
-    zero_flags_kernel<<<(unsigned)((words + kThreads - 1) / kThreads), kThreads, 0, st>>>(words, flags);
+    if (liso_zero::zero_async(flags, (size_t)batch * n_boxes * sizeof(uint32_t), st) != hipSuccess) return LISO_ELAUNCH;
     if (n_max > 0)
         has_points_kernel<<<dim3((unsigned)((n_max + kThreads - 1) / kThreads), batch), kThreads, 0, st>>>(n_boxes, n_max, point_stride, box_pos,
                                                                                                         box_dims, box_rot, pcl, counts, flags);

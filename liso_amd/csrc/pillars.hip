@@ -31,8 +31,11 @@
 #include "../../include/liso_iou3d.h"  // error codes
 #include "../../include/liso_conv.h"  // element codes (LISO_ELEM_*)
 #include "../../include/liso_pillars.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 constexpr int kTile = 1024;          // points per tile in the rank pass
 constexpr int kOut = LISO_PFN_OUT;
@@ -821,8 +824,6 @@ __global__ __launch_bounds__(64) void pfn_backward_finalize_kernel(const double*
         grad_weight[c * F + k] = (float)dw;
     }
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 inline bool cfg_ok(const liso_pillar_cfg* c, int batch) {
     return c && batch >= 1 && batch <= LISO_PILLARS_MAX_BATCH && c->gx > 0 && c->gy > 0 && c->max_points >= 1 &&

@@ -16,23 +16,22 @@
 
 #include "../../include/liso_box_mining.h"
 #include "../../include/liso_sample_prep.h"
+#include "dev_common.h"
+#include "zero_fill.h"
 
 namespace {
+
+using liso_dev::Carver;
+using liso_dev::affine_inv;
+using liso_dev::check_launch;
+using liso_dev::cloud_rows;
+using liso_dev::mat4_mul;
+using liso_dev::to_i32;
+using liso_dev::up256;
 
 constexpr int kThreads = 256;
 constexpr int kFixedBits = 38;
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
-
-// numpy's astype(int32) of a float64: truncation, INT_MIN for NaN and for values outside int32
-__device__ __forceinline__ int to_i32(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
-
-__device__ __forceinline__ int cloud_rows(const int32_t* counts, int b, int N) {
-    if (!counts) return N;
-    const int n = counts[b];
-    return n < 0 ? 0 : (n > N ? N : n);
-}
 
 // ---- 1. transform -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void transform_kernel(int N, int stride, const double* T, const float* pcl, const int32_t* counts,
@@ -69,29 +68,6 @@ struct PoseJobs {
     liso_sample_odom_job odom[LISO_SAMPLE_MAX_JOBS];
     int n_boxes, n_odoms;
 };
-
-// C = A * B for 4x4 row-major, each entry ((a0*b0 + a1*b1) + a2*b2) + a3*b3
-__device__ void mat4_mul(const double* A, const double* B, double* C) {
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c)
-            C[4 * r + c] = ((A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c]) + A[4 * r + 3] * B[12 + c];
-}
-
-// inverse of an affine matrix [A t; 0 0 0 1]: adjugate(A) / det(A), -A^-1 t
-__device__ void affine_inv(const double* M, double* R) {
-    const double a = M[0], b = M[1], c = M[2], d = M[4], e = M[5], f = M[6], g = M[8], h = M[9], k = M[10];
-    const double c00 = e * k - f * h, c01 = c * h - b * k, c02 = b * f - c * e;
-    const double c10 = f * g - d * k, c11 = a * k - c * g, c12 = c * d - a * f;
-    const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
-    const double det = (a * c00 + b * c10) + c * c20;
-    const double inv[9] = {c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det};
-    const double tx = M[3], ty = M[7], tz = M[11];
-    for (int r = 0; r < 3; ++r) {
-        R[4 * r] = inv[3 * r], R[4 * r + 1] = inv[3 * r + 1], R[4 * r + 2] = inv[3 * r + 2];
-        R[4 * r + 3] = -((inv[3 * r] * tx + inv[3 * r + 1] * ty) + inv[3 * r + 2] * tz);
-    }
-    R[12] = 0.0, R[13] = 0.0, R[14] = 0.0, R[15] = 1.0;
-}
 
 // blockIdx.y = job (boxes first, then odometries), blockIdx.z = b
 __global__ __launch_bounds__(kThreads) void poses_kernel(PoseJobs jobs, const double* T) {
@@ -203,11 +179,6 @@ __global__ __launch_bounds__(kThreads) void crop_move_kernel(Crop c, const float
     }
 }
 
-__global__ void zero_counts_kernel(int n, int32_t* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = 0;
-}
-
 // ---- 4. maps ------------------------------------------------------------------------------------------------------------------
 struct MapTables {
     int32_t* count;            // [B*cells]
@@ -218,23 +189,14 @@ struct MapTables {
 
 MapTables carve_maps(size_t cells_total, int n_flows, void* base) {
     MapTables t;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = (char*)base + off;
-        off += up256(bytes);
-        return (void*)p;
-    };
-    t.count = (int32_t*)take(cells_total * sizeof(int32_t));
+    Carver ws{base};
+    t.count = ws.take<int32_t>(cells_total);
     for (int s = 0; s < 2; ++s) {
-        t.maxbits[s] = s < n_flows ? (uint32_t*)take(cells_total * 3 * sizeof(uint32_t)) : nullptr;
-        t.sum[s] = s < n_flows ? (unsigned long long*)take(cells_total * 3 * sizeof(unsigned long long)) : nullptr;
+        t.maxbits[s] = s < n_flows ? ws.take<uint32_t>(cells_total * 3) : nullptr;
+        t.sum[s] = s < n_flows ? ws.take<unsigned long long>(cells_total * 3) : nullptr;
     }
-    t.bytes = off;
+    t.bytes = ws.bytes;
     return t;
-}
-
-__global__ __launch_bounds__(kThreads) void zero_words_kernel(size_t n_words, uint32_t* p) {
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n_words; i += (size_t)gridDim.x * kThreads) p[i] = 0u;
 }
 
 struct Maps {
@@ -393,8 +355,7 @@ int liso_bev_crop_f32(const liso_bev_crop_cfg* cfg, const float* pcl, const int3
     hipStream_t st = (hipStream_t)stream;
     if (N == 0) {
         if (pcl || drop || flow || lidar_rows || attr || out_pcl || pillar_coors) return LISO_EINVAL;
-        zero_counts_kernel<<<(B + 63) / 64, 64, 0, st>>>(B, out_counts);
-        return check_launch();
+        return liso_zero::zero_async(out_counts, (size_t)B * sizeof(int32_t), st) == hipSuccess ? LISO_OK : LISO_ELAUNCH;
     }
     if (!pcl || !out_pcl || !pillar_coors || !workspace || pcl == out_pcl || (flow && flow == out_flow)) return LISO_EINVAL;
     if (workspace_bytes < liso_bev_crop_workspace_bytes(B, N)) return LISO_EWORKSPACE;
@@ -434,10 +395,7 @@ int liso_bev_point_maps_f32(int batch, int n_max, int point_stride, int grid_x, 
     const MapTables t = carve_maps(cells_total, n_flows, workspace);
     if (workspace_bytes < t.bytes) return LISO_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const size_t words = t.bytes / sizeof(uint32_t);
-    size_t zero_blocks = (words + kThreads * 4 - 1) / (kThreads * 4);
-    if (zero_blocks > 65535) zero_blocks = 65535;
-    zero_words_kernel<<<(unsigned)zero_blocks, kThreads, 0, st>>>(words, (uint32_t*)workspace);
+    if (liso_zero::zero_async(workspace, t.bytes, st) != hipSuccess) return LISO_ELAUNCH;
     const Maps m = {n_max, point_stride, grid_x, grid_y};
     if (n_max > 0) {
         const dim3 pts((unsigned)((n_max + kThreads - 1) / kThreads), batch);

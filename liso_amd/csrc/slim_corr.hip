@@ -13,9 +13,12 @@
 
 #include "../../include/liso_iou3d.h"
 #include "../../include/liso_slim.h"
+#include "dev_common.h"
 #include "per_device.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 constexpr int kWavesPerBlock = 4;
 constexpr int kTransposeStride = 36;  // floats per lane row in the LDS transpose (32 + 4: 16-B aligned, conflict-free columns)
@@ -424,8 +427,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void corr_lookup_bwd_dvol_kern
     float* dst = lp.g2[lvl] + ((size_t)b * hw + pix) * ((size_t)pt.H * pt.W) + (size_t)y * pt.W + x;
     *dst += s * (1.0f / sqrtf((float)c.dim));
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 inline bool cfg_ok(const liso_corr_cfg* c) {
     return c && c->batch >= 1 && c->h >= 1 && c->w >= 1 && (c->dim == 128 || c->dim == 256) && c->levels >= 1 &&

@@ -8,13 +8,15 @@
 
 #include "../../include/liso_iou3d.h"
 #include "../../include/liso_slim_decode.h"
+#include "dev_common.h"
 
 namespace {
 
+using liso_dev::check_launch;
+using liso_dev::shfl_xor_f64;
+
 constexpr int kThreads = 256;
 constexpr int kRedBlocks = 512;  // block partials of the masked means
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 // ---- the decode of one point (head_decoder.py:517-717 on one row) --------------------------------------------------------------
 struct Consts {
@@ -309,13 +311,6 @@ __global__ __launch_bounds__(kThreads) void decode_points_bwd_kernel(liso_slim_d
 
 // ---- masked means ------------------------------------------------------------------------------------------------------------------
 // workspace: double partial[2 * kRedBlocks] | double total[2] (sum, count)
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, m);
-    hi = __shfl_xor(hi, m);
-    return __hiloint2double(hi, lo);
-}
-
 __device__ __forceinline__ void block_partial(double sum, double cnt, double* __restrict__ partial) {
     __shared__ double red[2][kThreads / 64];
 #pragma unroll

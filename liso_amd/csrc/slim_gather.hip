@@ -10,8 +10,11 @@
 
 #include "../../include/liso_iou3d.h"
 #include "../../include/liso_slim.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 __global__ void bev_gather_fwd_kernel(const float* __restrict__ grid, const int* __restrict__ lin, long n_rows, int c,
                                       float default_value, float* __restrict__ out) {
@@ -240,8 +243,6 @@ __global__ __launch_bounds__(256) void bev_plan_expand_kernel(const int* __restr
         rank[o] = 0;
     }
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 }  // namespace
 

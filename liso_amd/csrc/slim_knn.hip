@@ -20,8 +20,11 @@
 
 #include "../../include/liso_iou3d.h"
 #include "../../include/liso_slim.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -292,7 +295,6 @@ __global__ __launch_bounds__(256) void knn_query_kernel(Level fine, Level coarse
     if (dist_sqr) dist_sqr[gid] = best;
 }
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 inline bool grid_ok(const liso_knn_grid* g) {
     return g && g->cell > 0.f && g->z_cell > 0.f && g->nx >= 1 && g->ny >= 1 && g->nz >= 1 &&
            (long)g->nx * g->ny * g->nz <= (1L << 24);

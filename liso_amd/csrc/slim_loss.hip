@@ -6,8 +6,11 @@
 
 #include "../../include/liso_iou3d.h"
 #include "../../include/liso_slim.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::check_launch;
 
 struct Eval {
     float d2, loss, dx, dy, dz, scale;  // scale: d loss / d (q - nn) = scale * (q - nn)
@@ -72,7 +75,6 @@ __global__ void nploss_bwd_kernel(liso_nploss_cfg c, const float* __restrict__ c
     g_flow[3 * row + 2] = ok ? s * e.dz : 0.f;
 }
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 inline bool cfg_ok(const liso_nploss_cfg* c) {
     return c && c->batch >= 1 && c->n >= 0 && c->n_b >= 1 && c->fov_mode >= 0 && c->fov_mode <= 2 && c->delta >= 0.f;
 }

@@ -11,17 +11,14 @@
 
 #include "../../include/liso_iou3d.h"
 #include "../../include/liso_kabsch.h"
+#include "dev_common.h"
 
 namespace {
 
-constexpr int kBlocks = 256, kThreads = 256;
+using liso_dev::check_launch;
+using liso_dev::shfl_xor_f64;
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, m);
-    hi = __shfl_xor(hi, m);
-    return __hiloint2double(hi, lo);
-}
+constexpr int kBlocks = 256, kThreads = 256;
 
 __global__ __launch_bounds__(kThreads) void moments_partial_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                    const float* __restrict__ w, long n,
@@ -111,8 +108,6 @@ __global__ void moments_bwd_kernel(const float* __restrict__ x, const float* __r
         if (gy) gy[3 * i + a] = (float)(wi * dy[a]);
     }
 }
-
-inline int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 }  // namespace
 

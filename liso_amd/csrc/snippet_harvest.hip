@@ -15,8 +15,12 @@
 #include <stdint.h>
 
 #include "../../include/liso_snippets.h"
+#include "dev_common.h"
 
 namespace {
+
+using liso_dev::Carver;
+using liso_dev::check_launch;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -28,8 +32,6 @@ struct JobRow {
     int job;       // index of the job in the caller's order
 };
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-int check_launch() { return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH; }
 
 struct Tables {
     JobRow* rows;     // [J] in sorted order
@@ -41,17 +43,12 @@ struct Tables {
 
 Tables carve(int J, int chunks, void* base) {
     Tables t;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = (char*)base + off;
-        off += up256(bytes);
-        return (void*)p;
-    };
-    t.rows = (JobRow*)take((size_t)J * sizeof(JobRow));
-    t.key = (int32_t*)take((size_t)J * sizeof(int32_t));
-    t.total = (int32_t*)take((size_t)J * sizeof(int32_t));
-    t.counts = (int32_t*)take((size_t)J * chunks * sizeof(int32_t));
-    t.bytes = off;
+    Carver ws{base};
+    t.rows = ws.take<JobRow>((size_t)J);
+    t.key = ws.take<int32_t>((size_t)J);
+    t.total = ws.take<int32_t>((size_t)J);
+    t.counts = ws.take<int32_t>((size_t)J * chunks);
+    t.bytes = ws.bytes;
     return t;
 }
 

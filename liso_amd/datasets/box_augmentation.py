@@ -28,6 +28,7 @@ from liso_amd.datasets.targets import render_center_targets
 from liso_amd.datasets.torch_dataset_commons import voxelize_sample
 from liso_amd.kabsch.shape_utils import Shape
 from liso_amd.utils.bev_utils import get_bev_setup_params
+from liso_amd.utils.device_args import opt_ptr
 
 
 class BoxSnippetDb:
@@ -124,7 +125,7 @@ def paste_snippets(db, src_index, out_offsets, pose, flow_rand, vmin, vmax, want
     with torch.cuda.device(dev):
         L.check(L.TIMER.launch("snippet_paste", lambda: L.lib().liso_snippet_paste(
             L.ptr(db.points), db.points.shape[0], L.ptr(src), L.ptr(offs), L.ptr(pose_d), L.ptr(rnd), float(vmin), float(vmax), k,
-            L.ptr(pts), L.ptr(flow) if flow is not None else None, L.ptr(velo), L.stream_ptr())), "snippet_paste")
+            L.ptr(pts), opt_ptr(flow), L.ptr(velo), L.stream_ptr())), "snippet_paste")
     return pts, flow, velo
 
 

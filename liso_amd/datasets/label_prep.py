@@ -29,13 +29,10 @@ from liso_amd import _lib as L
 from liso_amd.datasets.sample_prep import _mat4_mul, affine_inverse
 from liso_amd.kabsch.shape_utils import Shape
 from liso_amd.utils.bev_utils import get_metric_voxel_center_coords
+from liso_amd.utils.device_args import as_u8, cloud3, counts_arg, is_np, opt_ptr as _p
 
 _ATTRS = ("pos", "dims", "rot", "probs", "velo", "class_id", "difficulty")  # everything of a Shape that rides with `valid`
 OCCUPANCY_THRESH = 0.01  # reference :212
-
-
-def _is_np(x):
-    return isinstance(x, np.ndarray)
 
 
 # ---- host path -------------------------------------------------------------------------------------------------------------------
@@ -213,10 +210,6 @@ class TargetsExCfg(ctypes.Structure):
 MAX_ATTRS = 8  # LISO_LABEL_MAX_ATTRS
 
 
-def _p(t):
-    return None if t is None or t.numel() == 0 else L.ptr(t)
-
-
 def _device_shape(shape, name="boxes"):
     """a Shape of device tensors, [K] or [B,K] -> (the [B,K] view of it, whether it came unbatched)"""
     if not isinstance(shape, Shape) or not torch.is_tensor(shape.pos):
@@ -232,23 +225,14 @@ def _geometry(s):
     """fp64 contiguous pos [B,K,3], dims [B,K,3], rot [B,K], valid uint8 [B,K] of a batched device Shape"""
     pos, dims = s.pos.to(torch.float64).contiguous(), s.dims.to(torch.float64).contiguous()
     rot = (s.rot[..., 0] if s.rot is not None and s.rot.shape[-1] > 0 else torch.zeros_like(s.pos[..., 0])).to(torch.float64).contiguous()
-    valid = s.valid.contiguous()
-    return pos, dims, rot, (valid.view(torch.uint8) if valid.dtype == torch.bool else valid.to(torch.uint8))
+    return pos, dims, rot, as_u8(s.valid, convert=True)
 
 
 def _cloud(pcl, counts, B):
-    if not torch.is_tensor(pcl) or pcl.dim() not in (2, 3) or pcl.shape[-1] < 3:
-        raise L.LisoHipError("pcl must be a [N, C] or [B, N, C] tensor with C >= 3")
-    L.require_cuda(pcl)
-    if pcl.dtype != torch.float32:
-        raise L.LisoHipError(f"pcl must be float32 on the device, got {pcl.dtype}")
-    p3 = (pcl if pcl.dim() == 3 else pcl[None]).contiguous()
+    p3 = cloud3(pcl, allow_empty_batch=True)
     if p3.shape[0] != B:
         raise L.LisoHipError(f"pcl holds {p3.shape[0]} clouds for {B} box sets")
-    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or tuple(counts.shape) != (B,)
-                               or counts.device != p3.device):
-        raise L.LisoHipError("counts must be an int32 [B] tensor on the cloud's device")
-    return p3, (None if counts is None else counts.contiguous())
+    return p3, counts_arg(counts, p3)
 
 
 def box_has_points_flags(objects, pcl, counts=None):
@@ -275,8 +259,7 @@ def _filter_device(objects, pcl, counts, bev_range_m, filter_bev, filter_range_m
     else:
         if not torch.is_tensor(has) or not has.is_cuda or has.numel() != B * K or has.dtype not in (torch.bool, torch.uint8):
             raise L.LisoHipError("box_has_points_inside must be a bool device tensor with the shape of objects.valid")
-        has = has.reshape(B, K).contiguous()
-        has = has.view(torch.uint8) if has.dtype == torch.bool else has
+        has = as_u8(has.reshape(B, K))
     out, jobs, keep_alive = {}, (AttrJob * MAX_ATTRS)(), []
     n = 0
     for k in _ATTRS:
@@ -310,7 +293,7 @@ def filter_objects_to_bev_non_empty(objects, pcl, counts=None, *, bev_range_m, f
     the INPUT of this call and may be passed to a second call on the same input, as the reference's second call does.  A sample
     without a valid box comes back as padding only.  `pcl` is the cloud itself ([N,C] / [B,N,C], x y z first), not its homogeneous
     form."""
-    if _is_np(objects.pos):
+    if is_np(objects.pos):
         return filter_objects_host(objects, pcl, counts, bev_range_m=bev_range_m, filter_bev=filter_bev, filter_range_m=filter_range_m,
                                    box_has_points_inside=box_has_points_inside)
     return _filter_device(objects, pcl, counts, bev_range_m, filter_bev, filter_range_m, box_has_points_inside)
@@ -319,7 +302,7 @@ def filter_objects_to_bev_non_empty(objects, pcl, counts=None, *, bev_range_m, f
 def object_velocity_in_obj_coords(odom_ta_tb, obj_pose_ta, obj_pose_tb):
     """reference :1116-1145 -- fp64 [B,K,3] (numpy: also [K,3] from an unbatched odometry): the non-rigid flow of every object's
     origin, rotated by its pose at ta; the source of `Shape.velo` for tracked ground truth"""
-    if _is_np(obj_pose_ta):
+    if is_np(obj_pose_ta):
         return object_velocity_host(odom_ta_tb, obj_pose_ta, obj_pose_tb)
     for t in (odom_ta_tb, obj_pose_ta, obj_pose_tb):
         if not torch.is_tensor(t):
@@ -342,7 +325,7 @@ def object_velocity_in_obj_coords(odom_ta_tb, obj_pose_ta, obj_pose_tb):
 def create_true_where_ignore_region_mask(ignore_boxes, grid_size, bev_range_m):
     """reference :919-941 -- bool [H,W] / [B,H,W]: true where a cell centre lies strictly inside a valid ignore box"""
     H, W = int(grid_size[0]), int(grid_size[1])
-    if _is_np(ignore_boxes.pos):
+    if is_np(ignore_boxes.pos):
         if ignore_boxes.valid.ndim == 1:
             return _ignore_mask_one_host(ignore_boxes, (H, W), bev_range_m)
         return np.stack([_ignore_mask_one_host(ignore_boxes[b], (H, W), bev_range_m) for b in range(ignore_boxes.valid.shape[0])])
@@ -367,7 +350,7 @@ def draw_heat_regression_maps(boxes, grid_size, bev_range_m, box_pred_cfg, per_o
         assert not normalize_gaussian
         assert per_obj_prob_scale.shape[-1] == 1, per_obj_prob_scale.shape
     H, W = int(grid_size[0]), int(grid_size[1])
-    if _is_np(boxes.pos):
+    if is_np(boxes.pos):
         if boxes.valid.ndim == 1:
             return _draw_one_host(boxes, (H, W), bev_range_m, rot_ch, log_dims, per_obj_prob_scale, normalize_gaussian)
         per = [_draw_one_host(boxes[b], (H, W), bev_range_m, rot_ch, log_dims,
@@ -408,7 +391,7 @@ def select_centermaps_target_confidence(cfg, gt_boxes):
     target = cfg.loss.supervised.centermaps.confidence_target
     if target != "gaussian":
         raise NotImplementedError(target)
-    return np.ones_like(gt_boxes.probs) if _is_np(gt_boxes.probs) else torch.ones_like(gt_boxes.probs)
+    return np.ones_like(gt_boxes.probs) if is_np(gt_boxes.probs) else torch.ones_like(gt_boxes.probs)
 
 
 def assemble_box_labels(sample, *, cfg, gt_boxes, gt_object_is_movable=None, src_key="ta", target_key="tb", counts=None,
@@ -440,7 +423,7 @@ def assemble_box_labels(sample, *, cfg, gt_boxes, gt_object_is_movable=None, src
         if mined_boxes is not None:
             sample["mined"]["boxes"] = mined_boxes
             if name not in ("pointrcnn", "pointpillars"):
-                ones = np.ones_like(mined_boxes.probs) if _is_np(mined_boxes.probs) else torch.ones_like(mined_boxes.probs)
+                ones = np.ones_like(mined_boxes.probs) if is_np(mined_boxes.probs) else torch.ones_like(mined_boxes.probs)
                 for k, v in draw_heat_regression_maps(mined_boxes, target_grid(), bev_range_m, cfg.box_prediction, per_obj_prob_scale=ones).items():
                     sample["mined"][f"centermaps_{k}"] = v
         sample["mined"].pop(f"objects_{target_key}", None)

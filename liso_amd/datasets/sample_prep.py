@@ -24,6 +24,7 @@ import torch
 
 from liso_amd import _lib as L
 from liso_amd.kabsch.shape_utils import Shape
+from liso_amd.utils.device_args import as_u8, cloud3, counts_arg, is_np, opt_ptr as _p
 
 
 # ---- the random transform (host) --------------------------------------------------------------------------------------------------
@@ -185,22 +186,6 @@ class CropCfg(ctypes.Structure):
 MAX_JOBS = 16  # LISO_SAMPLE_MAX_JOBS
 
 
-def _p(t):
-    return None if t is None or t.numel() == 0 else L.ptr(t)
-
-
-def _cloud(pcl, name="pcl"):
-    if not torch.is_tensor(pcl) or pcl.dim() not in (2, 3) or pcl.shape[-1] < 3:
-        raise L.LisoHipError(f"{name} must be a [N, C] or [B, N, C] tensor with C >= 3")
-    L.require_cuda(pcl)
-    if pcl.dtype != torch.float32:
-        raise L.LisoHipError(f"{name} must be float32 on the device, got {pcl.dtype}")
-    p3 = pcl if pcl.dim() == 3 else pcl[None]
-    if p3.shape[0] < 1:
-        raise L.LisoHipError(f"{name}: need at least one cloud")
-    return p3.contiguous()
-
-
 def _rider(t, p3, dtype, tail, name):
     """an optional per-point array riding with the cloud p3: [.., N] + tail in `dtype` on the cloud's device -> [B, N] + tail"""
     if t is None:
@@ -208,19 +193,11 @@ def _rider(t, p3, dtype, tail, name):
     if not torch.is_tensor(t) or not t.is_cuda or t.device != p3.device:
         raise L.LisoHipError(f"{name} must be a tensor on the cloud's device (CPU tensor given?)")
     if t.dtype == torch.bool and dtype == torch.uint8:
-        t = t.view(torch.uint8) if t.is_contiguous() else t.contiguous().view(torch.uint8)
+        t = as_u8(t)
     want = tuple(p3.shape[:2]) + tail
     if t.dtype != dtype or t.numel() != int(np.prod(want)):
         raise L.LisoHipError(f"{name} must be {dtype} with shape {want}, got {t.dtype} {tuple(t.shape)}")
     return t.reshape(want).contiguous()
-
-
-def _counts(counts, p3):
-    if counts is None:
-        return None
-    if not torch.is_tensor(counts) or counts.dtype != torch.int32 or tuple(counts.shape) != (p3.shape[0],) or counts.device != p3.device:
-        raise L.LisoHipError("counts must be an int32 [B] tensor on the cloud's device")
-    return counts.contiguous()
 
 
 def _transform_arg(T, batch, device):
@@ -241,10 +218,10 @@ def _transform_arg(T, batch, device):
 def transform_cloud_device(pcl, T, flow=None, counts=None, out=None, out_flow=None):
     """float32 device cloud [N,C] / [B,N,C] (and its flow [..,3]) under T -> new tensors, or written into `out` / `out_flow`
     (which may be the inputs: in place).  No host synchronisation."""
-    p3 = _cloud(pcl)
+    p3 = cloud3(pcl)
     B, N, C = p3.shape
     f3 = _rider(flow, p3, torch.float32, (3,), "flow")
-    counts = _counts(counts, p3)
+    counts = counts_arg(counts, p3)
     Tm = _transform_arg(T, B, p3.device)
     o3 = torch.empty_like(p3) if out is None else _rider(out, p3, torch.float32, (C,), "out")
     of3 = None if f3 is None else (torch.empty_like(f3) if out_flow is None else _rider(out_flow, p3, torch.float32, (3,), "out_flow"))
@@ -280,7 +257,7 @@ def transform_poses_device(T, boxes=(), odoms=(), batch=None):
             raise L.LisoHipError(f"box pos must be [B,K,2|3] and rot [B,K,1], got {tuple(pos.shape)} {tuple(rot.shape)}")
         v = None
         if valid is not None:
-            v = valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else valid.contiguous()
+            v = as_u8(valid) if valid.dtype == torch.bool else valid.contiguous()
             if v.dtype != torch.uint8 or v.numel() != B * pos.shape[1] or not v.is_cuda:
                 raise L.LisoHipError("box valid must be a bool [B,K] device tensor")
             keep.append(v)
@@ -299,13 +276,9 @@ def transform_poses_device(T, boxes=(), odoms=(), batch=None):
 
 
 # ---- the reference's names --------------------------------------------------------------------------------------------------------
-def _is_np(x):
-    return isinstance(x, np.ndarray)
-
-
 def transform_pcl_maybe_with_intensity(pcl, T, counts=None):
     """reference :1464-1483; any number of channels behind x, y, z is carried along"""
-    if _is_np(pcl):
+    if is_np(pcl):
         assert np.asarray(T).shape == (4, 4), np.asarray(T).shape
         return transform_cloud_host(pcl, T)
     return transform_cloud_device(pcl, T, counts=counts)
@@ -313,7 +286,7 @@ def transform_pcl_maybe_with_intensity(pcl, T, counts=None):
 
 def transform_flow(flow, T):
     """reference :1369-1384 -- the linear part of T on a flow field [N,3] / [B,N,3]"""
-    if _is_np(flow):
+    if is_np(flow):
         with np.errstate(invalid="ignore"):
             return _lin3(np.asarray(T, np.float64), flow[:, :3].astype(np.float64), False).astype(np.float32)
     if not torch.is_tensor(flow) or flow.shape[-1] != 3:
@@ -329,7 +302,7 @@ def transform_flow(flow, T):
 
 def transform_odometry(odom, T):
     """reference :1347-1365 -- (T * O * T^-1, its inverse)"""
-    if _is_np(odom):
+    if is_np(odom):
         return transform_odometry_host(odom, T)
     L.require_cuda(odom)
     o3 = (odom if odom.dim() == 3 else odom[None]).to(torch.float64).contiguous()
@@ -341,7 +314,7 @@ def transform_odometry(odom, T):
 def transform_boxes(shape: Shape, T):
     """reference :1435-1462 -- a copy of `shape` with pos / rot under T, in the dtypes they came in; invalid boxes untouched"""
     out = shape.clone()
-    if _is_np(shape.pos):
+    if is_np(shape.pos):
         out.pos, out.rot = transform_boxes_host(shape.pos, shape.rot, shape.valid, T)
         return out
     L.require_cuda(shape.pos)
@@ -390,13 +363,13 @@ def augment_sample_content(sample_content, src_key, target_key, dataset_name, *,
         for k in gt_keys:  # kitti_object keeps its objects as a dictionary of poses (reference :1392-1398)
             v = sc.get("gt", {}).get(k)
             if isinstance(v, dict) and "poses" in v:
-                Tp = np.asarray(T, np.float64) if _is_np(v["poses"]) else _transform_arg(T, 1, v["poses"].device).view(4, 4)
+                Tp = np.asarray(T, np.float64) if is_np(v["poses"]) else _transform_arg(T, 1, v["poses"].device).view(4, 4)
                 v["poses"] = Tp @ v["poses"]
     else:
         raise NotImplementedError(dataset_name)
     if "mined" in sc:
         boxes += [(sc["mined"], f"{kind}_{t}") for t in ("t0", "t1", "t2") for kind in ("objects", "boxes") if f"{kind}_{t}" in sc["mined"]]
-    if any(_is_np(sub[k]) for sub, k, _ in odoms) or any(_is_np(sub[k].pos) for sub, k in boxes):
+    if any(is_np(sub[k]) for sub, k, _ in odoms) or any(is_np(sub[k].pos) for sub, k in boxes):
         for sub, fwd, rev in odoms:
             sub[fwd], sub[rev] = transform_odometry(sub[fwd], T)
         for sub, k in boxes:
@@ -436,12 +409,12 @@ def pillarize_bev(pcl, counts=None, *, bev_range_m, img_grid_size, height_range_
     float32, flow [..,3] float32, lidar_rows int32, attr uint8 / bool, drop bool -> dict(pcl, counts int32 [B], pillar_coors int32
     [..,2], and flow / lidar_rows / attr when given), kept rows first, paddings NaN / -1 / 0.  numpy: one cloud [N,C] -> the kept
     rows only (`bev_crop_host`)."""
-    if _is_np(pcl):
+    if is_np(pcl):
         return bev_crop_host(pcl, bev_range_m=bev_range_m, img_grid_size=img_grid_size, height_range_m=height_range_m, flow=flow,
                              lidar_rows=lidar_rows, attr=attr, drop=drop)
-    p3 = _cloud(pcl)
+    p3 = cloud3(pcl)
     B, N, C = p3.shape
-    counts = _counts(counts, p3)
+    counts = counts_arg(counts, p3)
     f3 = _rider(flow, p3, torch.float32, (3,), "flow")
     rows = _rider(lidar_rows, p3, torch.int32, (), "lidar_rows")
     was_bool = attr is not None and attr.dtype == torch.bool
@@ -487,7 +460,7 @@ def bev_point_maps(pillar_coors, counts, img_grid_size, *, pcl=None, flow=None, 
     co = (pillar_coors[None] if unb else pillar_coors).contiguous()
     B, N = co.shape[:2]
     dev = co.device
-    counts = _counts(counts, co)
+    counts = counts_arg(counts, co)
     H, W = _grid(img_grid_size)
     f0 = _rider(flow, co, torch.float32, (3,), "flow")
     f1 = _rider(flow2, co, torch.float32, (3,), "flow2")
@@ -498,7 +471,7 @@ def bev_point_maps(pillar_coors, counts, img_grid_size, *, pcl=None, flow=None, 
     if want_mask:
         if pcl is None or f0 is None or threshold_dt is None:
             raise L.LisoHipError("the moving mask needs pcl, flow, odom_tb_ta and threshold_dt")
-        p3 = _cloud(pcl)
+        p3 = cloud3(pcl)
         C = p3.shape[2]
         if tuple(p3.shape[:2]) != (B, N):
             raise L.LisoHipError("pcl and pillar_coors disagree in shape")
@@ -532,21 +505,21 @@ def bev_point_maps(pillar_coors, counts, img_grid_size, *, pcl=None, flow=None, 
 
 def add_bev_flow(pillar_coors, flow, img_grid_size, counts=None):
     """reference :1200-1213 -- float32 [H,W,3] / [B,H,W,3]: the per-cell mean of `flow`, 0 in empty cells"""
-    if _is_np(pillar_coors):
+    if is_np(pillar_coors):
         return bev_point_maps_host(pillar_coors, img_grid_size, flow)[1]
     return bev_point_maps(pillar_coors, counts, img_grid_size, flow=flow, want_occupancy=False)["flow_bev"]
 
 
 def add_bev_ground_height_occupancy_maps(pillar_coors, img_grid_size, counts=None):
     """reference :1215-1223 -- float32 [1,H,W] / [B,1,H,W]: 1 where a pillar has a point"""
-    if _is_np(pillar_coors):
+    if is_np(pillar_coors):
         return bev_point_maps_host(pillar_coors, img_grid_size)[0]
     return bev_point_maps(pillar_coors, counts, img_grid_size)["occupancy_f32"]
 
 
 def moving_mask(pcl, flow, odom_tb_ta, threshold_dt, counts=None, pillar_coors=None):
     """reference :776-792 -- bool [N] / [B,N]; False behind the count"""
-    if _is_np(pcl):
+    if is_np(pcl):
         return moving_mask_host(pcl, flow, odom_tb_ta, threshold_dt)
     L.require_cuda(pcl)
     if pillar_coors is None:

@@ -9,6 +9,7 @@ import ctypes
 import torch
 
 from liso_amd import _lib as L
+from liso_amd.utils.device_args import as_u8, opt_ptr as _p
 
 MAX_POST = 1024  # LISO_DET_NMS_MAX_POST
 MAX_N = 1 << 24  # LISO_DET_NMS_MAX_N
@@ -25,10 +26,6 @@ def _need(t, name, dtype, shape):
         raise L.LisoHipError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
     if not t.is_contiguous():
         raise L.LisoHipError(f"{name} must be contiguous")
-
-
-def _p(t):
-    return None if t is None or t.numel() == 0 else L.ptr(t)
 
 
 def _bn(scores):
@@ -52,7 +49,7 @@ def order(scores, gate=None, valid=None, logit_threshold=None):
         _need(gate, "gate", torch.float32, (B, N))
     if valid is not None:
         if valid.dtype == torch.bool:
-            valid = valid.view(torch.uint8) if valid.is_contiguous() else valid.contiguous().view(torch.uint8)
+            valid = as_u8(valid)
         _need(valid, "valid", torch.uint8, (B, N))
     dev = scores.device
     keys = torch.empty((B, N), dtype=torch.int32, device=dev)

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from liso_amd import _lib as L
+from liso_amd.utils.device_args import as_u8, cloud3, counts_arg, opt_ptr as _p
 
 MIN_RANGE, MAX_RANGE, TH_G, SIGMA_DEG = 3.0, 70.0, 0.3, 7.0
 MAX_HEIGHT, MAX_PIXELS = 1024, 1 << 24  # LISO_GROUND_MAX_HEIGHT, LISO_GROUND_MAX_PIXELS
@@ -212,30 +213,6 @@ def jcp_host(pcl, range_img_width, range_img_height, sensor_height, delta_R, deb
 
 
 # ---- device ---------------------------------------------------------------------------------------------------------------------
-def _batched(pcl, name="pcl"):
-    if not torch.is_tensor(pcl) or pcl.dim() not in (2, 3) or pcl.shape[-1] < 3:
-        raise L.LisoHipError(f"{name} must be a [N, C] or [B, N, C] tensor with C >= 3")
-    L.require_cuda(pcl)
-    if pcl.dtype != torch.float32:
-        raise L.LisoHipError(f"{name} must be float32 on the device, got {pcl.dtype}")
-    p3 = pcl if pcl.dim() == 3 else pcl[None]
-    if p3.shape[0] < 1:
-        raise L.LisoHipError(f"{name}: need at least one cloud")
-    return p3 if p3.is_contiguous() else p3.contiguous()
-
-
-def _counts(counts, p3):
-    if counts is None:
-        return None
-    if not torch.is_tensor(counts) or counts.dtype != torch.int32 or tuple(counts.shape) != (p3.shape[0],) or counts.device != p3.device:
-        raise L.LisoHipError("counts must be an int32 [B] tensor on the cloud's device")
-    return counts.contiguous()
-
-
-def _p(t):
-    return None if t is None or t.numel() == 0 else L.ptr(t)
-
-
 def _cfg(p3, width, height, sensor_height, delta_R):
     return L.GroundCfg(p3.shape[0], p3.shape[1], p3.shape[2], int(width), int(height), float(sensor_height), float(delta_R))
 
@@ -244,8 +221,8 @@ def jcp_device(pcl, range_img_width, range_img_height, sensor_height, delta_R, c
     """float32 device tensor [N,C] or [B,N,C] (x, y, z first; NaN rows are padding) -> bool tensor [N] / [B,N], no host sync.
     `counts` int32 [B]: rows per cloud.  `stages=(begin, end)` runs that range of STAGES only and returns (labels uint8 [B,N],
     workspace); pass the pair back as `state` to go on with the same workspace (scripts/ground_seg_time.py times stage by stage)."""
-    p3 = _batched(pcl)
-    counts = _counts(counts, p3)
+    p3 = cloud3(pcl)
+    counts = counts_arg(counts, p3)
     B, N = p3.shape[0], p3.shape[1]
     cfg = _cfg(p3, range_img_width, range_img_height, sensor_height, delta_R)
     lib = L.lib()
@@ -267,14 +244,14 @@ def jcp_device(pcl, range_img_width, range_img_height, sensor_height, delta_R, c
 
 def cone_device(pcl, cone_z_threshold__m, cone_angle__deg, counts=None, or_with=None):
     """the cone test in fp64 on the device, OR-ed with `or_with` (bool, same leading shape); invalid rows are False"""
-    p3 = _batched(pcl)
-    counts = _counts(counts, p3)
+    p3 = cloud3(pcl)
+    counts = counts_arg(counts, p3)
     B, N = p3.shape[0], p3.shape[1]
     slope = float(np.tan(cone_angle__deg / 180.0 * np.pi)) if cone_angle__deg > 0.0 else 0.0
     if or_with is not None:
         if or_with.dtype != torch.bool or or_with.numel() != B * N or or_with.device != p3.device:
             raise L.LisoHipError("or_with must be a bool tensor of the cloud's leading shape on its device")
-        or_with = or_with.contiguous().view(torch.uint8)
+        or_with = as_u8(or_with)
     out = torch.empty((B, N), dtype=torch.uint8, device=p3.device)
     with torch.cuda.device(p3.device):
         L.check(L.lib().liso_ground_cone_f32(B, N, p3.shape[2], _p(p3), _p(counts), float(cone_z_threshold__m), slope, _p(or_with), _p(out),
@@ -287,8 +264,8 @@ def remove_ground_points(pcl, *, range_img_width, range_img_height, sensor_heigh
     """float32 device tensor [N,C] or [B,N,C] -> (pcl_no_ground [.., N, C] with the kept rows first, in order, NaN behind them;
     counts int32 [B]; is_ground bool [.., N] = JCP label | cone label).  `cone` = (cone_z_threshold__m, cone_angle__deg) or None
     for the JCP label alone.  Nothing is read back: the call can be captured in a hipGraph."""
-    p3 = _batched(pcl)
-    counts = _counts(counts, p3)
+    p3 = cloud3(pcl)
+    counts = counts_arg(counts, p3)
     B, N, C = p3.shape
     is_ground = jcp_device(p3, range_img_width, range_img_height, sensor_height, delta_R, counts=counts)
     if cone is not None:
@@ -299,7 +276,7 @@ def remove_ground_points(pcl, *, range_img_width, range_img_height, sensor_heigh
     ws_bytes = lib.liso_ground_compact_workspace_bytes(B, N)
     ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=p3.device)
     with torch.cuda.device(p3.device):
-        L.check(lib.liso_ground_compact_f32(B, N, C, _p(p3), _p(counts), _p(is_ground.view(torch.uint8)), _p(out), L.ptr(kept),
+        L.check(lib.liso_ground_compact_f32(B, N, C, _p(p3), _p(counts), _p(as_u8(is_ground)), _p(out), L.ptr(kept),
                                             L.ptr(ws) if N else None, ws_bytes, L.stream_ptr()), "ground compact")
     if pcl.dim() == 2:
         return out[0], kept, is_ground[0]

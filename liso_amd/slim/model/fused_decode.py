@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from liso_amd import _lib as L
+from liso_amd.utils.device_args import as_u8
 
 _MODES = {"net": 0, True: 1, False: 2}
 
@@ -170,10 +171,6 @@ decode_weights = _DecodeWeights.apply
 
 
 # ---- losses ----------------------------------------------------------------------------------------------------------------------
-def _u8(mask):
-    return mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8).contiguous()
-
-
 class _StaticPointsLossMean(torch.autograd.Function):
     """masked mean over the valid rows of static_points_loss (slim_loss_adaptor.py:55-91): one reduction launch forward, one
     elementwise launch backward"""
@@ -182,7 +179,7 @@ class _StaticPointsLossMean(torch.autograd.Function):
     def forward(ctx, pc, valid, flow, weight, trafo):
         S, N = valid.shape
         pc, flow, weight = pc.detach().float().contiguous(), flow.float().contiguous(), weight.float().contiguous()
-        v8, T = _u8(valid), trafo.detach().double().contiguous()
+        v8, T = as_u8(valid, convert=True), trafo.detach().double().contiguous()
         lib = L.lib()
         nbytes = lib.liso_slim_loss_workspace_bytes()
         ws = torch.empty(nbytes, dtype=torch.uint8, device=pc.device)
@@ -216,7 +213,7 @@ class _NearestPointLossMean(torch.autograd.Function):
     def forward(ctx, pc, valid, flow, cloud_b, index, order, cfg):
         S, N = valid.shape
         pc, flow, cloud_b = pc.detach().float().contiguous(), flow.float().contiguous(), cloud_b.detach().float().contiguous()
-        v8 = _u8(valid)
+        v8 = as_u8(valid, convert=True)
         lib = L.lib()
         nbytes = lib.liso_slim_loss_workspace_bytes()
         ws = torch.empty(nbytes, dtype=torch.uint8, device=pc.device)
@@ -271,7 +268,7 @@ def knn_losses(pc_a, valid_a, cloud_b, flows, knn_indices, query_order_indices, 
             order = order.contiguous()
     types = sorted(flows)
     pc = pc_a.detach().float().contiguous()
-    v8 = _u8(valid_a)
+    v8 = as_u8(valid_a, convert=True)
     fl = [flows[t].detach().float().contiguous() for t in types]
     dev = pc.device
     query = torch.empty((len(types), S, N, 3), dtype=torch.float32, device=dev)

@@ -23,6 +23,7 @@ import torch
 from liso_amd import _lib as L
 from liso_amd.kabsch.shape_utils import Shape
 from liso_amd.tracker.augm_box_db_utils import get_empty_augm_box_db
+from liso_amd.utils.device_args import opt_ptr
 
 BLOAT_HALF = np.float32(0.55)  # 1.1 * 0.5 as the reference's float32 tensor product sees it
 POINT_BYTES = 16  # one stored point: box-frame x, y, z and the intensity, float32
@@ -127,13 +128,12 @@ def cut_box_snippets(clouds, counts, lidar_rows, job_cloud, boxes, capacity=None
     if ws_bytes == 0:
         raise L.LisoHipError(f"snippet_cut: sizes out of range (T={T}, n_max={n_max}, J={J})")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    opt = lambda t: L.ptr(t) if t is not None else None  # noqa: E731
 
     def call(cap, points, rows):
         with torch.cuda.device(dev):
             L.check(L.TIMER.launch("snippet_cut", lambda: L.lib().liso_snippet_cut_f32(
-                T, n_max, stride, L.ptr(clouds), opt(cnt), opt(rows_in if rows is not None else None), J, L.ptr(jc), L.ptr(b7), cap,
-                L.ptr(offsets), opt(points), opt(rows), L.ptr(box_T), L.ptr(ws), ws_bytes, L.stream_ptr())), "snippet_cut")
+                T, n_max, stride, L.ptr(clouds), opt_ptr(cnt), opt_ptr(rows_in if rows is not None else None), J, L.ptr(jc), L.ptr(b7), cap,
+                L.ptr(offsets), opt_ptr(points), opt_ptr(rows), L.ptr(box_T), L.ptr(ws), ws_bytes, L.stream_ptr())), "snippet_cut")
 
     if capacity is None:
         call(0, None, None)
