@@ -291,14 +291,15 @@ __global__ __launch_bounds__(64) void nms_prepare_kernel(int k, int pre_nms_max,
     for (int i = lane; i < k; i += 64) {
         // position in the stable descending order of key = valid ? probs : -inf.  A NaN confidence (a diverging detector) compares
         // false both ways and would give several slots one rank -- slots overwritten, others stale: NaN ranks as -inf (behind every
-        // number, stable among themselves), so the order stays a permutation like the reference's torch.argsort
+        // number, stable among themselves), so the order stays a permutation like the reference's torch.argsort.  The key is the fp64
+        // confidence itself: two confidences that differ only below fp32 resolution are sorted apart, as the reference sorts them
         const bool vi = sc[i].valid != 0;
-        float ki = vi ? (float)sc[i].probs : -INFINITY;
-        ki = ki != ki ? -INFINITY : ki;
+        double ki = vi ? sc[i].probs : -(double)INFINITY;
+        ki = ki != ki ? -(double)INFINITY : ki;
         int rank = 0;
         for (int j = 0; j < k; j++) {
-            float kj = sc[j].valid ? (float)sc[j].probs : -INFINITY;
-            kj = kj != kj ? -INFINITY : kj;
+            double kj = sc[j].valid ? sc[j].probs : -(double)INFINITY;
+            kj = kj != kj ? -(double)INFINITY : kj;
             rank += (kj > ki || (kj == ki && j < i)) ? 1 : 0;
         }
         const Slot s = sc[i];

@@ -108,6 +108,152 @@ def regionprops_restated(label_img):
     return np.array(out, dtype=np.float64).reshape(-1, 5)
 
 
+# ---- the per-box steps between the clusters and the detector targets (include/liso_box_mining.h) ------------------------------
+# numpy, fp64, one plain statement per line of the reference; `flow_cluster_detector_forward` below is built from the first
+# three, so the end-to-end oracle and the per-kernel oracles of tests/test_gpu_box_mining.py are one text.
+UNKNOWN_CLASS_ID = 2**31 - 1             # shape_utils.py:15
+INVALID_CLASS_ID = UNKNOWN_CLASS_ID - 1  # shape_utils.py:16
+
+
+def boxes_from_regions(props, row_coords, col_coords, pix_per_m):
+    """flow_cluster_detector.py:176-206.  props fp64 [..., 5] = (centroid_row, centroid_col, orientation, axis_major, axis_minor);
+    row_coords fp32 [gx] / col_coords fp32 [gy]: the metric centres of a separable pillar grid (grid_pts_3d[r, c] =
+    (row_coords[r], col_coords[c])); pix_per_m fp32 [2].
+    -> (center fp32 [..., 2], dims fp64 [..., 2], rot fp64 [...], dims fp32, rot fp32)"""
+    import numpy as np
+
+    props = np.asarray(props, np.float64)
+    row_coords, col_coords = np.asarray(row_coords, np.float32), np.asarray(col_coords, np.float32)
+    # :177-181: astype(int) truncates toward zero; BOTH indices are clipped to the smaller grid extent
+    pix = np.clip(props[..., 0:2].astype(np.int64), 0, min(row_coords.shape[0], col_coords.shape[0]) - 1)
+    center = np.stack([row_coords[pix[..., 0]], col_coords[pix[..., 1]]], axis=-1)  # :197-199
+    dims = props[..., 3:5] * 1.0 / np.asarray(pix_per_m, np.float32).astype(np.float64)  # :191-195 (fp64 / fp32 -> fp64)
+    rot = props[..., 2].copy()  # :182-184
+    return center, dims, rot, dims.astype(np.float32), rot.astype(np.float32)
+
+
+def mine_filter_compact(num_labels, center, dims2, rot, num_pts, fit_z, fit_h, *, min_points, aspect_ratio_max, max_box_len_m,
+                        min_box_area_m2, min_box_volume_m3, park_invalid=False):
+    """flow_cluster_detector.py:221-250 (the five rules), :250 drop_padding_boxes (survivors first, label order kept) and :310
+    Shape.from_list_of_shapes(numeric_padding_value=0.0), for fixed K slots per sample.
+    num_labels int [B]; center fp32 [B,K,2]; dims2 fp64 [B,K,2]; rot fp64 [B,K]; num_pts int64 [B,K]; fit_z / fit_h fp32 [B,K].
+    -> dict of numpy arrays with the shapes and dtypes of liso_mine_filter_compact: pos, dims, rot, probs, velo, valid, class_id,
+    difficulty, counts, kabsch_pos, kabsch_dims, kabsch_rot.  The volume is (d0 * d1) * h, the order a left-to-right product takes."""
+    import numpy as np
+
+    center, dims2, rot = np.asarray(center, np.float32), np.asarray(dims2, np.float64), np.asarray(rot, np.float64)
+    fit_z, fit_h, num_pts = np.asarray(fit_z, np.float32), np.asarray(fit_h, np.float32), np.asarray(num_pts, np.int64)
+    B, K = center.shape[:2]
+    d0, d1, h = dims2[..., 0], dims2[..., 1], fit_h.astype(np.float64)
+    with np.errstate(all="ignore"):
+        ok = np.arange(K)[None, :] < np.asarray(num_labels, np.int64).reshape(B, 1)  # regions 1..num_labels exist
+        ok &= num_pts >= min_points                                                   # :221
+        ok &= d0 / np.maximum(d1, 0.001) <= aspect_ratio_max                          # :222-226
+        ok &= d0 <= max_box_len_m                                                     # :227
+        ok &= d0 * d1 > min_box_area_m2                                               # :228-230
+        ok &= (d0 * d1) * h > min_box_volume_m3                                       # :237-240
+    park = np.float32(1e6 if park_invalid else 0.0)
+    o = {"pos": np.zeros((B, K, 3), np.float32), "dims": np.zeros((B, K, 3), np.float64), "rot": np.zeros((B, K, 1), np.float64),
+         "probs": np.zeros((B, K, 1), np.float64), "velo": np.zeros((B, K, 1), np.float64), "valid": np.zeros((B, K), np.uint8),
+         "class_id": np.full((B, K, 1), INVALID_CLASS_ID, np.int32), "difficulty": np.full((B, K, 1), INVALID_CLASS_ID, np.int32),
+         "counts": ok.sum(1).astype(np.int32), "kabsch_pos": np.full((B, K, 3), park, np.float32),
+         "kabsch_dims": np.zeros((B, K, 3), np.float32), "kabsch_rot": np.zeros((B, K), np.float32)}
+    for b in range(B):
+        s = np.nonzero(ok[b])[0]
+        n = s.size
+        o["pos"][b, :n] = np.concatenate([center[b, s], fit_z[b, s, None]], -1)      # :234-236
+        o["dims"][b, :n] = np.concatenate([dims2[b, s], h[b, s, None]], -1)          # :231-233
+        o["rot"][b, :n, 0] = rot[b, s]
+        o["probs"][b, :n] = 1.0                                                      # :202
+        o["valid"][b, :n] = 1
+        o["class_id"][b, :n] = UNKNOWN_CLASS_ID                                      # shape_utils.py:66
+        o["difficulty"][b, :n] = 1                                                   # shape_utils.py:82
+        o["kabsch_pos"][b, :n] = o["pos"][b, :n]
+        o["kabsch_dims"][b, :n] = o["dims"][b, :n].astype(np.float32)
+        o["kabsch_rot"][b, :n] = rot[b, s].astype(np.float32)
+    return o
+
+
+def box_motion(trafos, pos, rot):
+    """flow_cluster_detector.py:325-331 with shape_utils.py:563-605 and torch_transformation.py:16-62.
+    trafos fp64 [B,S+1,4,4] (slot S = background); pos [B,S,3]; rot fp64 [B,S,1] -> (rot + atan2(t_y, t_x) [B,S,1], |t| [B,S,1]),
+    t = the translation of inv(T_box) inv(T_bg) (T_fg T_box), T_box = translation(pos) * yaw(rot); inverses by LU (torch.linalg.inv)"""
+    trafos, pos, rot = torch.as_tensor(trafos).double(), torch.as_tensor(pos), torch.as_tensor(rot).double()
+    B, S = pos.shape[:2]
+    fg, bg = trafos[:, :-1], trafos[:, -1:]
+    c, s = torch.cos(rot[..., 0]), torch.sin(rot[..., 0])
+    Tb = torch.zeros(B, S, 4, 4, dtype=torch.float64)  # shape_utils.py:271-319: translation * yaw
+    Tb[..., 0, 0], Tb[..., 0, 1], Tb[..., 1, 0], Tb[..., 1, 1] = c, -s, s, c
+    Tb[..., 0, 3], Tb[..., 1, 3], Tb[..., 2, 3] = pos[..., 0].double(), pos[..., 1].double(), pos[..., 2].double()
+    Tb[..., 2, 2] = Tb[..., 3, 3] = 1.0
+    M = torch.linalg.inv(Tb) @ torch.linalg.inv(bg) @ (fg @ Tb)  # shape_utils.py:583-605
+    tr = M[..., :3, 3]
+    return rot + torch.atan2(tr[..., [1]], tr[..., [0]]), torch.linalg.norm(tr, dim=-1)[..., None]
+
+
+_BOX_KEYS = ("pos", "dims", "rot", "probs", "velo", "valid", "class_id", "difficulty")
+
+
+def nms_prepare(arrays, pre_nms_max):
+    """nms_iou.py:33-44 and :257-268 for fixed slots: per sample, every field permuted into the STABLE descending order of
+    key = probs where valid else -inf (a NaN confidence ranks as -inf too, so the order stays a permutation); the first
+    `pre_nms_max` (<= 0: all) valid slots enter the NMS.  arrays: dict of numpy [B,K,...] (pos fp32, dims / rot / probs / velo
+    fp64, valid uint8, class_id / difficulty int32).
+    -> (permuted dict, enters uint8 [B,K], dense fp32 [B,K,7]); a slot that does not enter is parked at (1e6 + 10 rank, 1e6, 0)
+    with 1e-3 edges (perform_nms_on_shapes_padded)."""
+    import numpy as np
+
+    B, K = arrays["valid"].shape
+    out = {k: np.array(arrays[k], copy=True) for k in _BOX_KEYS}
+    enters = np.zeros((B, K), np.uint8)
+    dense = np.zeros((B, K, 7), np.float32)
+    for b in range(B):
+        valid = arrays["valid"][b] != 0
+        p = np.asarray(arrays["probs"][b], np.float64).reshape(K)
+        key = np.where(valid & ~np.isnan(p), p, -np.inf)
+        order = np.argsort(-key, kind="stable")
+        for k in _BOX_KEYS:
+            out[k][b] = arrays[k][b][order]
+        rank = np.arange(K)
+        enters[b] = valid[order] & ((rank < pre_nms_max) if pre_nms_max > 0 else True)
+        dense[b, :, 0] = np.float32(1e6) + np.float32(10.0) * rank.astype(np.float32)
+        dense[b, :, 1] = 1e6
+        dense[b, :, 3:6] = 1e-3
+        e = enters[b] != 0
+        dense[b, e] = np.concatenate([out["pos"][b, e], out["dims"][b, e].astype(np.float32),
+                                      out["rot"][b, e].reshape(-1, 1).astype(np.float32)], -1)  # :230-242
+    return out, enters, dense
+
+
+def nms_finish(b, arrays, enters, keep, num, max_boxes, targets):
+    """nms_iou.py:54-58, :10-20 and :277-282 for sample b of fixed slots: of keep[:num] (num clamped to [0, K], indices outside
+    [0, K) ignored) the slots that entered and are valid survive, the first `max_boxes` of them in slot order stay valid; every
+    other slot of the sample takes the padding values of Shape.set_padding_val_to(0.0) (shape_utils.py:439-462).
+    targets = (t_pos fp32 [B,K,3], t_dims fp32 [B,K,3], t_rot fp32 [B,K], t_valid uint8 [B,K]): sample b is rewritten with the
+    fp32 box arrays (dims clamped to >= 1e-3).  -> (dict, targets), copies; the other samples pass through."""
+    import numpy as np
+
+    out = {k: np.array(arrays[k], copy=True) for k in _BOX_KEYS}
+    t_pos, t_dims, t_rot, t_valid = (np.array(t, copy=True) for t in targets)
+    K = out["valid"].shape[1]
+    hit = np.zeros(K, bool)
+    for j in np.asarray(keep).reshape(-1)[:min(max(int(num), 0), K)]:
+        if 0 <= j < K:
+            hit[j] = True
+    kept = hit & (np.asarray(enters)[b] != 0) & (out["valid"][b] != 0)
+    ok = kept & (np.cumsum(kept) <= max_boxes)
+    for k in ("pos", "dims", "rot", "probs", "velo"):
+        out[k][b][~ok] = 0.0
+    for k in ("class_id", "difficulty"):
+        out[k][b][~ok] = INVALID_CLASS_ID
+    out["valid"][b] = ok
+    t_valid[b] = ok
+    t_pos[b] = out["pos"][b]
+    t_dims[b] = np.maximum(out["dims"][b].astype(np.float32), np.float32(1e-3))
+    t_rot[b] = out["rot"][b].reshape(K).astype(np.float32)
+    return out, (t_pos, t_dims, t_rot, t_valid)
+
+
 def flow_cluster_detector_forward(pcl, pcl_is_valid, pcl_w_ground, pillar_coors, point_flow, odom_ta_tb, time_delta_s,
                                   grid_pts_xy, pix_per_m, *, min_num_pts_per_box=10, max_box_len_m=7.0, aspect_ratio_max=4.0,
                                   min_box_area_m2=0.35, min_box_volume_m3=0.5, slope=15.0, buffer=0.25):
@@ -128,22 +274,17 @@ def flow_cluster_detector_forward(pcl, pcl_is_valid, pcl_w_ground, pillar_coors,
         label_imgs.append(lab)
         props = regionprops_restated(lab)
         K = props.shape[0]
-        pix = np.clip(props[:, 0:2].astype(int), 0, G - 1)
-        pos2 = torch.from_numpy(grid_pts_xy[pix[:, 0], pix[:, 1]]).reshape(K, 2)
-        rot = torch.from_numpy(props[:, 2:3])
-        dims2 = torch.from_numpy(props[:, 3:5]) * 1.0 / torch.from_numpy(pix_per_m)
+        center, dims2, rot1, dims2_f32, rot1_f32 = boxes_from_regions(props, grid_pts_xy[:, 0, 0], grid_pts_xy[0, :, 1], pix_per_m)
         if K > 0:
-            n, z, h = fit_box_z(pcl_w_ground[b][:, :3], pos2, dims2.float(), rot[:, 0].float(), box_height=1000.0)
+            n, z, h = fit_box_z(pcl_w_ground[b][:, :3], torch.from_numpy(center), torch.from_numpy(dims2_f32), torch.from_numpy(rot1_f32),
+                                box_height=1000.0)
         else:
             n, z, h = torch.zeros(0, dtype=torch.int64), torch.zeros(0), torch.zeros(0)
-        ok = n >= min_num_pts_per_box
-        ok &= dims2[:, 0] / torch.max(dims2[:, 1], 0.001 * torch.ones_like(dims2[:, 1])) <= aspect_ratio_max
-        ok &= dims2[:, 0] <= max_box_len_m
-        ok &= torch.prod(dims2, dim=-1) > min_box_area_m2
-        dims3 = torch.cat([dims2, h[:, None].double()], dim=-1)
-        pos3 = torch.cat([pos2, z[:, None]], dim=-1)
-        ok &= torch.prod(dims3, dim=-1) > min_box_volume_m3
-        per_sample.append((pos3[ok], dims3[ok], rot[ok]))
+        o = mine_filter_compact([K], center[None], dims2[None], rot1[None], n.numpy()[None], z.numpy()[None], h.numpy()[None],
+                                min_points=min_num_pts_per_box, aspect_ratio_max=aspect_ratio_max, max_box_len_m=max_box_len_m,
+                                min_box_area_m2=min_box_area_m2, min_box_volume_m3=min_box_volume_m3)
+        k = int(o["counts"][0])
+        per_sample.append((torch.from_numpy(o["pos"][0, :k]), torch.from_numpy(o["dims"][0, :k]), torch.from_numpy(o["rot"][0, :k])))
     S = max(p[0].shape[0] for p in per_sample)
     pos = torch.zeros(B, S, 3)
     dims = torch.zeros(B, S, 3, dtype=torch.float64)
@@ -155,14 +296,5 @@ def flow_cluster_detector_forward(pcl, pcl_is_valid, pcl_w_ground, pillar_coors,
     velo = torch.zeros(B, S, 1, dtype=torch.float64)
     if S > 0:
         T, _, _ = OK.kabsch_trafos(pos, dims.float(), rot.float(), pcl[..., :3], pcl_is_valid, point_flow, slope=slope, buffer=buffer)
-        fg, bg = T[:, :-1], T[:, -1:]
-        c, s = torch.cos(rot[..., 0].double()), torch.sin(rot[..., 0].double())
-        Tb = torch.zeros(B, S, 4, 4, dtype=torch.float64)  # shape_utils.py:271-319: translation * yaw
-        Tb[..., 0, 0], Tb[..., 0, 1], Tb[..., 1, 0], Tb[..., 1, 1] = c, -s, s, c
-        Tb[..., 0, 3], Tb[..., 1, 3], Tb[..., 2, 3] = pos[..., 0].double(), pos[..., 1].double(), pos[..., 2].double()
-        Tb[..., 2, 2] = Tb[..., 3, 3] = 1.0
-        M = torch.linalg.inv(Tb) @ torch.linalg.inv(bg) @ (fg @ Tb)  # shape_utils.py:583-605
-        tr = M[..., :3, 3]
-        rot = rot + torch.atan2(tr[..., [1]], tr[..., [0]])
-        velo[..., 0] = torch.linalg.norm(tr, dim=-1)
+        rot, velo = box_motion(T, pos, rot)
     return dict(pos=pos, dims=dims, rot=rot, velo=velo, valid=valid, labels=np.stack(label_imgs))
