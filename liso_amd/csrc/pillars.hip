@@ -573,8 +573,11 @@ __global__ __launch_bounds__(1024) void pfn_bn_finalize_kernel(const double* __r
         bn_out[2 * kOut + c] = (float)mean;
         bn_out[3 * kOut + c] = (float)invstd;
         if (M > 1.0) {  // torch.nn.BatchNorm1d running stats: unbiased variance
-            running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-            running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)(var * M / (M - 1.0));
+            // blended in fp64 and rounded once: in fp32 the two terms cancel where the batch mean opposes the running one, and the
+            // result was 7 ulps off (one pillar of one point)
+            const double mo = (double)momentum;
+            running_mean[c] = (float)((1.0 - mo) * (double)running_mean[c] + mo * mean);
+            running_var[c] = (float)((1.0 - mo) * (double)running_var[c] + mo * (var * M / (M - 1.0)));
         }
     }
 }
