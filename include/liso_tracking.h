@@ -114,6 +114,69 @@ int liso_bike_rollout_bwd_f32(int batch, int timesteps, const float* accel, cons
                               float max_yaw_rate, float max_velocity, const float* states, const float* grad_states,
                               float* grad_initial_state, float* grad_accel, float* grad_steering, void* stream);
 
+/* ---- sequence tracker: a sequence's per-frame boxes associated into tracks -------------------------------------------------------
+ * Replaces FlowBasedBoxTracker.run_tracker / track_one_way and the constant-velocity step of liso/tracker/global_box_tracker.py
+ * (:78-259 run_tracker with its hole filling :197-240, :261-467 track_one_way, :303-326 the carried boxes) and the odometry chain
+ * of liso/tracker/tracking_helpers.py:30-44, for n_seq padded sequences per call; one workgroup walks one sequence.
+ *
+ *   n_frames   int32   [S]           frames of each sequence (clamped to [0, T])
+ *   n_det      int32   [S,T]         detections of each frame (clamped to [0, K])
+ *   boxes      float32 [S,T,K,7]     x, y, z, dx, dy, dz, yaw in sensor coordinates
+ *   conf       float32 [S,T,K] or NULL   detection confidences: not read (the reference does not use them either); `src` carries them
+ *   odom       float64 [S,T,4,4]     sensor(t) <- sensor(t + 1); the entry of a sequence's last frame is not read
+ *   into_prev, into_next  float64 [S,T,K,4,4]   each detection's pose propagated into the sensor frame of t - 1 / t + 1
+ *   threshold  box_matching_threshold_m; a pair matches when its fp32 distance, widened to fp64, is < threshold
+ *   cap        rows per frame of the result tables, 1 <= cap <= LISO_TRACK_MAX_CAP.  The walk itself keeps min(3 K, LISO_TRACK_MAX_CAP)
+ *              rows per frame (detections plus carried boxes), whatever `cap` is: a frame holds its detections and the boxes carried
+ *              from the previous frame's alive rows, which are that frame's detections and once-carried detections of the frame
+ *              before, so 3 K rows always suffice and a small `cap` never changes the tracks
+ *
+ * Per sequence: world_T_sensor(0) = I, world_T_sensor(t + 1) = world_T_sensor(t) * odom(t), entries ((a0 b0 + a1 b1) + a2 b2) + a3 b3 in
+ * fp64.  A detection's world position is row r of world_T_sensor: ((W_r0 x + W_r1 y) + W_r2 z) + W_r3, its world yaw
+ * atan2(W_10 cos yaw + W_11 sin yaw, W_00 cos yaw + W_01 sin yaw); the propagated poses' translations go through
+ * world_T_sensor(max(t - 1, 0)) / world_T_sensor(min(t + 1, n_frames - 1)) in the same way and are rounded to fp32.
+ * Forward walk, frame t >= 1: the rows of frame t - 1 with confidence >= 0 are visited in descending confidence, EQUAL CONFIDENCES IN
+ * ASCENDING ROW INDEX (the reference sorts with an unstable argsort: its order of ties is unspecified from 17 rows on).  Each takes
+ * the not yet taken detection of frame t nearest in x, y to its own position rounded to fp32 -- dx = a.x - b.x, dy = a.y - b.y,
+ * d = sqrtf(dx dx + dy dy) -- the first detection on equal distance; the pair is a match when d < threshold.  A matched detection
+ * inherits the row's track id, the others get counter + 1 + rank among the unmatched.  Unmatched visited rows are carried into frame
+ * t behind its detections, in row order: position p + (p - p') in fp64 when the id had position p' in frame t - 2, else p; confidence
+ * (0.0001f + confidence) - 1.0f.  Frame 0 numbers its detections counter + 1 + slot.  The backward walk is the same routine over the
+ * reversed frames with into_next; only the id counter it advances is kept.  Hole filling: a carried row of the forward walk whose track
+ * has a detection in a later frame is appended to its frame's detections, such rows of one frame in ascending track id.
+ *
+ *   n_out      int32   [S,T]         rows of each frame: its detections, then the hole-filling rows
+ *   track_ids  int64   [S,T,cap]     -1 beyond n_out (every output row beyond n_out is blank: positions 0, src -1)
+ *   pos_world  float64 [S,T,cap,3], rot_world float64 [S,T,cap]
+ *   src        int32   [S,T,cap,2]   frame and slot of the detection a row is, or that its chain of carries started from
+ *   is_fill    uint8   [S,T,cap]     1 for a hole-filling row
+ *   w_T_sensor float64 [S,T,4,4]     identity behind a sequence's last frame
+ *   id_counter int64   [S]           the id counter after both walks
+ *   overflow   int32   [S]           rows that did not fit: sum over the frames of max(0, detections + hole-filling rows - cap).  The
+ *                                    rows that fit are the first rows of the result with room, in every frame; nothing is written
+ *                                    outside the tables.  Only with K > LISO_TRACK_MAX_CAP / 3 can the walk itself run out of rows:
+ *                                    its surplus (max(0, detections + carried - LISO_TRACK_MAX_CAP) per frame, dropped from the back
+ *                                    and forgotten) is added to `overflow`, and frames behind the first such one are tracked without
+ *                                    the dropped rows.
+ *   workspace  liso_track_sequences_workspace_bytes(...) bytes (0 = sizes refused), 8-byte aligned
+ *
+ * The walk keeps three frames of min(3 K, LISO_TRACK_MAX_CAP) rows in LDS, 124 bytes per row: LISO_TRACK_MAX_CAP rows are 124 KiB of
+ * the 160 KiB of a compute unit (the post-NMS cap of 500 boxes fits: its walk takes the full 1024 rows).  A frame's result is never
+ * longer than the walk's rows, so a cap above LISO_TRACK_MAX_CAP is LISO_EINVAL.
+ */
+#define LISO_TRACK_MAX_CAP 1024
+/* MAX_PROPAGATION_TIME, INITIAL_TRACK_CONF, MIN_ALIVE_TRACK_CONF of the host tracker (global_box_tracker.py:269-271): a carried box
+ * loses INITIAL_TRACK_CONF / MAX_PROPAGATION_TIME - 0.0001 of confidence per frame and is alive while its confidence is >= the last */
+#define LISO_TRACK_MAX_PROPAGATION_TIME 1
+#define LISO_TRACK_INITIAL_CONF 1.0f
+#define LISO_TRACK_MIN_ALIVE_CONF 0.0f
+size_t liso_track_sequences_workspace_bytes(int n_seq, int max_frames, int max_det, int cap);
+int liso_track_sequences(int n_seq, int max_frames, int max_det, int cap, const int32_t* n_frames, const int32_t* n_det,
+                         const float* boxes, const float* conf, const double* odom, const double* into_prev, const double* into_next,
+                         double threshold, int32_t* n_out, int64_t* track_ids, double* pos_world, double* rot_world, int32_t* src,
+                         uint8_t* is_fill, double* w_T_sensor, int64_t* id_counter, int32_t* overflow, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -327,6 +327,9 @@ SIGNATURES = {
     # include/liso_snippets.h
     "liso_snippet_cut_workspace_bytes": (_sz, [_i, _i, _i]),
     "liso_snippet_cut_f32": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _lg] + [_vp] * 5 + [_sz, _vp]),
+    # include/liso_tracking.h: the sequence tracker
+    "liso_track_sequences_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "liso_track_sequences": (_i, [_i] * 4 + [_vp] * 7 + [ctypes.c_double] + [_vp] * 10 + [_sz, _vp]),
 }
 
 

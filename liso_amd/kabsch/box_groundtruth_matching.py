@@ -38,8 +38,11 @@ def _greedy_host(dist_matrix, sortind, matching_threshold):
 def slow_greedy_match_boxes_by_desending_confidence_by_dist(non_batched_gt_boxes_pos: Union[torch.Tensor, np.ndarray],
                                                             non_batched_pred_boxes_pos: Union[torch.Tensor, np.ndarray],
                                                             non_batched_pred_confidence: Union[torch.Tensor, np.ndarray],
-                                                            matching_threshold: float, match_in_nd=3):
-    """reference :154-229 -> (idxs_into_gt, idxs_into_preds, matching_dists, matched_preds_mask, det_gts_mask) as numpy arrays"""
+                                                            matching_threshold: float, match_in_nd=3, tie_order=None):
+    """reference :154-229 -> (idxs_into_gt, idxs_into_preds, matching_dists, matched_preds_mask, det_gts_mask) as numpy arrays.
+    `tie_order` (extension, host tensors only): "stable" visits predictions of equal confidence in ascending index, the rule of the
+    device tracker (include/liso_tracking.h); None leaves their order to torch.argsort, as the reference does."""
+    assert tie_order in (None, "stable"), tie_order
     assert len(non_batched_gt_boxes_pos.shape) == 2, non_batched_gt_boxes_pos.shape
     assert len(non_batched_pred_boxes_pos.shape) == 2, non_batched_pred_boxes_pos.shape
     assert len(non_batched_pred_confidence.shape) == 1, non_batched_pred_confidence.shape
@@ -59,6 +62,8 @@ def slow_greedy_match_boxes_by_desending_confidence_by_dist(non_batched_gt_boxes
                     np.zeros(n_true, dtype=bool))
         dist = torch.cdist(non_batched_gt_boxes_pos[..., :match_in_nd].to(torch.float32),
                            non_batched_pred_boxes_pos[..., :match_in_nd].to(torch.float32)).numpy()
+        if tie_order == "stable":
+            return _greedy_host(dist, torch.argsort(non_batched_pred_confidence, descending=True, stable=True).numpy(), matching_threshold)
         return _greedy_host(dist, torch.argsort(non_batched_pred_confidence, descending=True).numpy(), matching_threshold)
     L.require_cuda(non_batched_gt_boxes_pos, non_batched_pred_boxes_pos, non_batched_pred_confidence)
     if n_pred == 0 or n_true == 0:
