@@ -130,6 +130,7 @@ def require_cuda(*tensors):
 
 
 _vp, _i, _f, _sz, _lg = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
+_d = ctypes.c_double
 
 # symbol -> (restype, argtypes); mirrors include/*.h exactly (tests/test_abi.py parses the headers and checks)
 SIGNATURES = {
@@ -330,6 +331,11 @@ SIGNATURES = {
     # include/liso_tracking.h: the sequence tracker
     "liso_track_sequences_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "liso_track_sequences": (_i, [_i] * 4 + [_vp] * 7 + [ctypes.c_double] + [_vp] * 10 + [_sz, _vp]),
+    # include/liso_track_mining.h
+    "liso_track_mining_workspace_bytes": (_sz, [_i] * 5),
+    "liso_select_tracks": (_i, [_i] * 5 + [_vp] * 7 + [_i, _f, _d, _d, _i, _d, _d, _i, _d] + [_vp] * 13 + [_vp, _sz, _vp]),
+    "liso_refine_tracks_apply": (_i, [_i] * 3 + [_vp] * 12 + [_i, _i, _d] + [_vp] * 7 + [_vp]),
+    "liso_export_tracks": (_i, [_i] * 6 + [_vp] * 11 + [_i] + [_vp] * 13 + [_vp, _sz, _vp]),
 }
 
 

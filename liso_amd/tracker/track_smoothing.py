@@ -28,7 +28,7 @@ def batched_displacement_from_pos(pos, num_skip=1):
     assert num_skip >= 1, num_skip
     disp = torch.linalg.norm(pos[:, num_skip:, :] - pos[:, :-num_skip, :], dim=-1)
     if num_skip == 1:
-        disp = torch.cat([disp, disp[:, [-num_skip]]], dim=1)
+        disp = torch.cat([disp, disp[:, -1:]], dim=1)  # (a slice, not an index list: no host-to-device copy, capturable)
     else:
         disp = torch.cat([disp[:, :(num_skip // 2)], disp, disp[:, (-num_skip // 2):]], dim=1)
     assert pos.shape[:-1] == disp.shape, (pos.shape, disp.shape)
@@ -41,7 +41,7 @@ def get_orientations_along_track(pos, pad_borders=True, num_skip=2):
     track_angle = torch.atan2(dir_vecs[:, :, 1], dir_vecs[:, :, 0])
     if pad_borders:
         if num_skip == 1:
-            track_angle = torch.cat([track_angle, track_angle[:, [-num_skip]]], dim=1)
+            track_angle = torch.cat([track_angle, track_angle[:, -1:]], dim=1)
         else:
             track_angle = torch.cat([track_angle[:, :(num_skip // 2)], track_angle, track_angle[:, (-num_skip // 2):]], dim=1)
         assert pos.shape[:-1] == track_angle.shape, (pos.shape, track_angle.shape)
