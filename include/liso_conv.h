@@ -244,13 +244,21 @@ int liso_conv_set_option(int option, int value);
  * (dx rows of other cells are not written: the caller zero-fills dx; the pillar encoder's backward reads occupied cells only);
  * `w_packed_dgrad` = liso_conv_pack_weights(..., for_dgrad = 1, ...).  Workspace query: for_dgrad != 0 omits the product buffer.
  * reuse_lists != 0: `workspace` is the (unmodified) workspace of the liso_sparse_conv_forward call on the same canvas -- its cell
- * lists are used as they are (occupancy may be NULL) instead of being rebuilt. */
+ * lists are used as they are (occupancy may be NULL) instead of being rebuilt.
+ * liso_sparse_conv_forward_rows: the same convolution on a COMPACT canvas (include/liso_pillars.h: liso_pfn_forward_rows): `rows`
+ * [n_rows, row_stride] holds one feature row per pillar and `cell_to_row` [batch, hi, wi] the row + 1 of every cell (0 = none).  The cell
+ * lists are built from `occupancy` exactly as above; a listed cell without a row (or with one >= n_rows) is multiplied as zeros.  Bit
+ * for bit the result of liso_sparse_conv_forward on the dense canvas these rows scatter to. */
 int liso_sparse_conv_stat_groups(int hi, int wi, int co);
 size_t liso_sparse_conv_workspace_bytes(int batch, int hi, int wi, int k, int co, int max_cells_per_sample, int for_dgrad);
 int liso_sparse_conv_forward(const void* x, long x_pix_stride, int is_bf16, const float* occupancy, const void* w_packed,
                              const float* bias, int batch, int hi, int wi, int k, int co, int max_cells_per_sample, int relu, void* y,
                              float* stats_partial, const float* stats_shift, int* overflow, void* workspace, size_t workspace_bytes,
                              void* stream);
+int liso_sparse_conv_forward_rows(const void* rows, long row_stride, int is_bf16, const int* cell_to_row, long n_rows,
+                                  const float* occupancy, const void* w_packed, const float* bias, int batch, int hi, int wi, int k, int co,
+                                  int max_cells_per_sample, int relu, void* y, float* stats_partial, const float* stats_shift,
+                                  int* overflow, void* workspace, size_t workspace_bytes, void* stream);
 int liso_sparse_conv_dgrad(const void* dy, long dy_pix_stride, int is_bf16, const float* occupancy, const void* w_packed_dgrad, int batch,
                            int hi, int wi, int k, int co, int max_cells_per_sample, void* dx, long dx_pix_stride, int* overflow,
                            void* workspace, size_t workspace_bytes, int reuse_lists, void* stream);

@@ -87,6 +87,15 @@ int liso_pfn_forward_scatter(const float* feat, const int* pt_off, const int* vo
                              const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas, int out_bf16,
                              float* occupancy, void* stream);
 
+/* The same pass with a COMPACT canvas: the row of pillar v (voxel row order, as voxel_cell) is written to rows[v] ([batch *
+ * max_voxels, 64], element code out_bf16) and no dense canvas exists.  cell_to_row [batch, gx, gy] receives cell_to_voxel + row_base
+ * (0 = empty cell): `rows` may be a slice starting at row `row_base` of a larger array that the map indexes (several sweeps stacked
+ * along the batch axis).  occupancy as above.  Rows of unused pillars (beyond num_voxels) are not written and must not be read: the
+ * map never points at them.  Consumer: liso_sparse_conv_forward_rows (include/liso_conv.h). */
+int liso_pfn_forward_rows(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
+                          const int* cell_to_voxel, const float* weight, const float* bn_out, void* rows, int out_bf16, int row_base,
+                          int* cell_to_row, float* occupancy, void* stream);
+
 /* Backward of the fused op w.r.t. weight, gamma, beta (inputs carry no gradient: voxelize is no_grad,
  * pcl_to_feature_grid.py:56).  grad_canvas has the canvas layout/dtype.  grad_weight [64, C+6],
  * grad_gamma/grad_beta [64] are overwritten.  partials: liso_pfn_partials_bytes() bytes of scratch. */

@@ -149,6 +149,7 @@ SIGNATURES = {
     "liso_pfn_decorate_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_pfn_bn_prepare_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "liso_pfn_forward_scatter": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "liso_pfn_forward_rows": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "liso_pfn_backward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     # include/liso_kabsch.h
     "liso_kabsch_workspace_bytes": (_sz, [_vp]),
@@ -276,6 +277,8 @@ SIGNATURES = {
     "liso_sparse_conv_stat_groups": (_i, [_i, _i, _i]),
     "liso_sparse_conv_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "liso_sparse_conv_forward": (_i, [_vp, ctypes.c_long, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "liso_sparse_conv_forward_rows": (_i, [_vp, ctypes.c_long, _i, _vp, ctypes.c_long, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                           _sz, _vp]),
     "liso_sparse_conv_dgrad": (_i, [_vp, ctypes.c_long, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_long, _vp, _vp, _sz, _i, _vp]),
     "liso_sparse_stem_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "liso_sparse_stem_forward_f32": (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

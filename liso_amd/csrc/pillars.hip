@@ -626,13 +626,17 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ feat, const
 //                            threads -> consecutive chunks), the occupancy map is written (alone: 21 us = 6.4 TB/s at B = 4).
 constexpr int kCellsPerBlock = 256;
 
-template <int C, typename OutT>
+// ROWS (the compact canvas): a pillar's row goes to canvas[v] instead of canvas[cell] -- `canvas` is then the [rows, 64] row array of
+// this call -- and the last blocks write the occupancy map and the caller's cell -> row map (cell_to_voxel + row_base, 0 = empty: the
+// rows of several calls may share one array) but no zeros: the rows of unused pillars are never written.
+template <int C, typename OutT, bool ROWS>
 __global__ __launch_bounds__(kPfnThreads) void pfn_forward_kernel(const float* __restrict__ feat, const int* __restrict__ pt_off,
                                                                   const int* __restrict__ voxel_cell, int rows, int max_points,
                                                                   long total_cells, int zero_blocks,
                                                                   const int* __restrict__ cell_to_voxel,
                                                                   const float* __restrict__ weight, const float* __restrict__ bn,
-                                                                  OutT* __restrict__ canvas, float* __restrict__ occupancy) {
+                                                                  OutT* __restrict__ canvas, float* __restrict__ occupancy,
+                                                                  int* __restrict__ map_out, int row_base) {
     constexpr int F = C + 6;
     constexpr int kChunks = kOut * (int)sizeof(OutT) / 16;  // 16-B chunks per cell (8 for bf16, 16 for fp32)
     __shared__ __attribute__((aligned(16))) float frow[kPfnThreads / 64][kStage][kFP];
@@ -646,7 +650,9 @@ __global__ __launch_bounds__(kPfnThreads) void pfn_forward_kernel(const float* _
         if (cell < total_cells) {
             v1 = cell_to_voxel[cell];
             occupancy[cell] = v1 > 0 ? 1.f : 0.f;
+            if constexpr (ROWS) map_out[cell] = v1 > 0 ? v1 + row_base : 0;
         }
+        if constexpr (ROWS) return;
         vox[tid] = v1;
         __syncthreads();
         const uint4 z = make_uint4(0u, 0u, 0u, 0u);
@@ -686,7 +692,7 @@ __global__ __launch_bounds__(kPfnThreads) void pfn_forward_kernel(const float* _
                 for (int k = 0; k < F; k++) x = fmaf(w[k], f[k], x);
                 best = fmaxf(best, fmaxf(fmaf(x, scale, shift), 0.f));
             }
-            store_out<OutT>(canvas + (size_t)cell * kOut + lane, best);
+            store_out<OutT>(canvas + (size_t)(ROWS ? v0 + g : cell) * kOut + lane, best);
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -972,9 +978,9 @@ int liso_pfn_bn_prepare_f32(const float* feat, const int* pt_off, const liso_pil
     return check_launch();
 }
 
-int liso_pfn_forward_scatter(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
-                             const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas, int out_bf16,
-                             float* occupancy, void* stream) {
+static int pfn_forward_launch(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
+                              const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas, int out_bf16,
+                              float* occupancy, int* map_out, int row_base, bool compact, void* stream) {
     if (!cfg_ok(cfg, batch) || !feat || !pt_off || !voxel_cell || !cell_to_voxel || !weight || !bn_out || !canvas || !occupancy)
         return LISO_EINVAL;
     if (out_bf16 != LISO_ELEM_F32 && out_bf16 != LISO_ELEM_BF16 && out_bf16 != LISO_ELEM_F16) return LISO_EINVAL;
@@ -986,7 +992,8 @@ int liso_pfn_forward_scatter(const float* feat, const int* pt_off, const int* vo
     int pfn_blocks = (groups + kPfnThreads / 64 - 1) / (kPfnThreads / 64);
     if (pfn_blocks > 4096) pfn_blocks = 4096;
     const unsigned grid = (unsigned)(zero_blocks + pfn_blocks);
-#define LISO_FWD(CC, T) pfn_forward_kernel<CC, T><<<grid, kPfnThreads, 0, st>>>(feat, pt_off, voxel_cell, rows, cfg->max_points, cells, zero_blocks, cell_to_voxel, weight, bn_out, (T*)canvas, occupancy)
+#define LISO_FWD_(CC, T, R) pfn_forward_kernel<CC, T, R><<<grid, kPfnThreads, 0, st>>>(feat, pt_off, voxel_cell, rows, cfg->max_points, cells, zero_blocks, cell_to_voxel, weight, bn_out, (T*)canvas, occupancy, map_out, row_base)
+#define LISO_FWD(CC, T) do { if (compact) LISO_FWD_(CC, T, true); else LISO_FWD_(CC, T, false); } while (0)
     switch (cfg->n_channels * 3 + out_bf16) {  // (n_channels 3..5, element code 0..2)
         case 9: LISO_FWD(3, float); break;
         case 10: LISO_FWD(3, __hip_bfloat16); break;
@@ -999,7 +1006,23 @@ int liso_pfn_forward_scatter(const float* feat, const int* pt_off, const int* vo
         default: LISO_FWD(5, _Float16); break;
     }
 #undef LISO_FWD
+#undef LISO_FWD_
     return check_launch();
+}
+
+int liso_pfn_forward_scatter(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
+                             const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas, int out_bf16,
+                             float* occupancy, void* stream) {
+    return pfn_forward_launch(feat, pt_off, voxel_cell, cfg, batch, cell_to_voxel, weight, bn_out, canvas, out_bf16, occupancy, nullptr,
+                              0, false, stream);
+}
+
+int liso_pfn_forward_rows(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
+                          const int* cell_to_voxel, const float* weight, const float* bn_out, void* rows, int out_bf16, int row_base,
+                          int* cell_to_row, float* occupancy, void* stream) {
+    if (!cell_to_row || row_base < 0 || (long)row_base + (long)batch * (cfg ? cfg->max_voxels : 0) >= (1L << 31)) return LISO_EINVAL;
+    return pfn_forward_launch(feat, pt_off, voxel_cell, cfg, batch, cell_to_voxel, weight, bn_out, rows, out_bf16, occupancy, cell_to_row,
+                              row_base, true, stream);
 }
 
 int liso_pfn_backward(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,

@@ -123,9 +123,12 @@ __global__ __launch_bounds__(1024) void cells_scan_kernel(const int* __restrict_
 }
 
 // ---- 1c. per canvas row: list position of every occupied cell (class base + row offset + rank among the row's cells of its column
-//          parity), cell index into the list, position into the map ------------------------------------------------------------------
+//          parity), cell index into the list, position into the map; with a compact canvas (`cell_map`: feature row + 1 of every
+//          cell, 0 = none) also the listed cell's feature row, -1 for a cell without one (a pillar dropped at the voxel capacity) or
+//          with one outside the row array ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void cells_fill_kernel(const float* __restrict__ occ, int wi, int n_rows, const int* __restrict__ off4,
-                                                        const int* __restrict__ seg, int* __restrict__ cells, int* __restrict__ cell_pos) {
+                                                        const int* __restrict__ seg, int* __restrict__ cells, int* __restrict__ cell_pos,
+                                                        const int* __restrict__ cell_map, int map_rows, int* __restrict__ cell_row) {
     const long row = blockIdx.x;
     const int lane = threadIdx.x;
     const int cy = (int)((row + 1) & 1);
@@ -144,6 +147,10 @@ __global__ __launch_bounds__(64) void cells_fill_kernel(const float* __restrict_
             if (pos < end[cx]) {
                 cells[pos] = (int)(row * wi + c);
                 cell_pos[row * wi + c] = pos;
+                if (cell_map) {
+                    const int fr = cell_map[row * wi + c] - 1;
+                    cell_row[pos] = fr < map_rows ? fr : -1;
+                }
             } else {
                 cell_pos[row * wi + c] = -1;  // beyond the capacity (seg[8] is set): the cell is dropped
             }
@@ -179,8 +186,9 @@ __device__ __forceinline__ int class_of_block(const int* __restrict__ seg, int p
 }
 
 // EL (LISO_ELEM_*) = BF16 / F16: 16-bit tensors, one MFMA per product; F32: fp32 tensors in F32X3 arithmetic (hi * hi + hi * lo + lo * hi,
-// small terms first)
-template <int K, int CO, int EL>
+// small terms first).  ROWS (the compact canvas): `xv` is the feature row array and `cells` lists the feature row of every listed cell
+// (cells_fill_kernel's cell_row: the same position, so no further dependent load); a negative row reads as zeros.
+template <int K, int CO, int EL, bool ROWS>
 __global__ __launch_bounds__(256) void stem_taps_kernel(const void* __restrict__ xv, long xps, const int* __restrict__ cells,
                                                         const int* __restrict__ seg, const uint4* __restrict__ wp,
                                                         float* __restrict__ prod) {
@@ -200,7 +208,9 @@ __global__ __launch_bounds__(256) void stem_taps_kernel(const void* __restrict__
     uint4 ah[4], al[4];
     {
         const int p = row0 + r;
-        const size_t cell = (size_t)cells[p < end ? p : row0];
+        const int src = cells[p < end ? p : row0];
+        const bool none = ROWS && src < 0;
+        const size_t cell = (size_t)(none ? 0 : src);
 #pragma unroll
         for (int ks = 0; ks < 4; ks++) {
             if constexpr (H16) {
@@ -208,6 +218,9 @@ __global__ __launch_bounds__(256) void stem_taps_kernel(const void* __restrict__
                 al[ks] = ah[ks];
             } else {
                 split8((const float*)xv + cell * xps + ks * 16 + h * 8, ah[ks], al[ks]);
+            }
+            if constexpr (ROWS) {
+                if (none) { ah[ks] = make_uint4(0u, 0u, 0u, 0u); al[ks] = ah[ks]; }
             }
         }
     }
@@ -433,7 +446,7 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(const void* __restrict_
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct Layout {
-    size_t cnt4, off4, seg, bitmap, cells, cell_pos, prod, total;
+    size_t cnt4, off4, seg, bitmap, cells, cell_pos, cell_row, prod, total;
     int n_rows, words, cap;
 };
 
@@ -455,19 +468,22 @@ inline bool layout(int batch, int hi, int wi, int k, int co, int max_cells_per_s
     l->bitmap = o; o += align256((size_t)l->n_rows * l->words * 4);
     l->cells = o; o += align256((size_t)l->cap * 4);
     l->cell_pos = o; o += align256((size_t)batch * hi * wi * 4);
+    l->cell_row = o; o += align256((size_t)l->cap * 4);
     l->prod = o;
     if (with_products) o += align256((size_t)l->cap * sx * sx * co * 4);
     l->total = o;
     return true;
 }
 
-void cell_lists(const float* occupancy, int wi, const Layout& l, char* ws, int* overflow, hipStream_t st) {
+void cell_lists(const float* occupancy, int wi, const Layout& l, char* ws, int* overflow, hipStream_t st, const int* cell_map = nullptr,
+                int map_rows = 0) {
     int* cnt4 = (int*)(ws + l.cnt4);
     int* off4 = (int*)(ws + l.off4);
     int* seg = (int*)(ws + l.seg);
     cells_rows_kernel<<<l.n_rows, 64, 0, st>>>(occupancy, wi, l.words, l.n_rows, cnt4, (unsigned*)(ws + l.bitmap));
     cells_scan_kernel<<<1, 1024, 0, st>>>(cnt4, l.n_rows, l.cap, off4, seg, overflow);
-    cells_fill_kernel<<<l.n_rows, 64, 0, st>>>(occupancy, wi, l.n_rows, off4, seg, (int*)(ws + l.cells), (int*)(ws + l.cell_pos));
+    cells_fill_kernel<<<l.n_rows, 64, 0, st>>>(occupancy, wi, l.n_rows, off4, seg, (int*)(ws + l.cells), (int*)(ws + l.cell_pos),
+                                                cell_map, map_rows, (int*)(ws + l.cell_row));
 }
 
 }  // namespace
@@ -488,12 +504,13 @@ size_t liso_sparse_conv_workspace_bytes(int batch, int hi, int wi, int k, int co
     return layout(batch, hi, wi, k, co, max_cells_per_sample, !for_dgrad, &l) ? l.total : 0;
 }
 
-int liso_sparse_conv_forward(const void* x, long x_pix_stride, int is_bf16, const float* occupancy, const void* w_packed,
-                             const float* bias, int batch, int hi, int wi, int k, int co, int max_cells_per_sample, int relu, void* y,
-                             float* stats_partial, const float* stats_shift, int* overflow, void* workspace, size_t workspace_bytes,
-                             void* stream) {
+static int sparse_forward(const void* x, long x_pix_stride, int is_bf16, const int* cell_map, long map_rows, const float* occupancy,
+                          const void* w_packed, const float* bias, int batch, int hi, int wi, int k, int co, int max_cells_per_sample,
+                          int relu, void* y, float* stats_partial, const float* stats_shift, int* overflow, void* workspace,
+                          size_t workspace_bytes, void* stream) {
     Layout l;
     if (!x || !occupancy || !w_packed || !y || !workspace) return LISO_EINVAL;
+    if (cell_map && (map_rows < 1 || map_rows >= (1L << 31))) return LISO_EINVAL;
     if (is_bf16 != LISO_ELEM_F32 && is_bf16 != LISO_ELEM_BF16 && is_bf16 != LISO_ELEM_F16) return LISO_EINVAL;
     const int vec = is_bf16 ? 8 : 4;
     if (x_pix_stride < CI || (x_pix_stride % vec) || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_packed | (uintptr_t)workspace) & 15))
@@ -506,8 +523,9 @@ int liso_sparse_conv_forward(const void* x, long x_pix_stride, int is_bf16, cons
     if (groups <= 0) return LISO_EINVAL;
     char* ws = (char*)workspace;
     hipStream_t st = (hipStream_t)stream;
-    cell_lists(occupancy, wi, l, ws, overflow, st);
+    cell_lists(occupancy, wi, l, ws, overflow, st, cell_map, (int)map_rows);
     const int* cells = (const int*)(ws + l.cells);
+    const int* cell_row = (const int*)(ws + l.cell_row);
     const int* seg = (const int*)(ws + l.seg);
     const unsigned* bitmap = (const unsigned*)(ws + l.bitmap);
     const int* cell_pos = (const int*)(ws + l.cell_pos);
@@ -515,7 +533,8 @@ int liso_sparse_conv_forward(const void* x, long x_pix_stride, int is_bf16, cons
     const unsigned tb = (unsigned)(l.cap / 32), gb = (unsigned)((long)batch * ho * wo / ((long)ppb * groups));
 #define LISO_SPARSE_FWD(K, CO, BF)                                                                                                     \
     do {                                                                                                                                \
-        stem_taps_kernel<K, CO, BF><<<tb, 256, 0, st>>>(x, x_pix_stride, cells, seg, (const uint4*)w_packed, prod);                     \
+        if (cell_map) stem_taps_kernel<K, CO, BF, true><<<tb, 256, 0, st>>>(x, x_pix_stride, cell_row, seg, (const uint4*)w_packed, prod); \
+        else stem_taps_kernel<K, CO, BF, false><<<tb, 256, 0, st>>>(x, x_pix_stride, cells, seg, (const uint4*)w_packed, prod);          \
         stem_gather_kernel<K, CO, BF><<<gb, 256, 0, st>>>(bitmap, l.words, cell_pos, prod, bias, hi, wi, ho, wo, relu, groups, y, stats_partial, \
                                                          stats_shift);                                                                 \
     } while (0)
@@ -526,6 +545,23 @@ int liso_sparse_conv_forward(const void* x, long x_pix_stride, int is_bf16, cons
     else return LISO_EINVAL;
 #undef LISO_SPARSE_FWD
     return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH;
+}
+
+int liso_sparse_conv_forward(const void* x, long x_pix_stride, int is_bf16, const float* occupancy, const void* w_packed,
+                             const float* bias, int batch, int hi, int wi, int k, int co, int max_cells_per_sample, int relu, void* y,
+                             float* stats_partial, const float* stats_shift, int* overflow, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    return sparse_forward(x, x_pix_stride, is_bf16, nullptr, 0, occupancy, w_packed, bias, batch, hi, wi, k, co, max_cells_per_sample, relu,
+                          y, stats_partial, stats_shift, overflow, workspace, workspace_bytes, stream);
+}
+
+int liso_sparse_conv_forward_rows(const void* rows, long row_stride, int is_bf16, const int* cell_to_row, long n_rows,
+                                  const float* occupancy, const void* w_packed, const float* bias, int batch, int hi, int wi, int k, int co,
+                                  int max_cells_per_sample, int relu, void* y, float* stats_partial, const float* stats_shift,
+                                  int* overflow, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cell_to_row) return LISO_EINVAL;
+    return sparse_forward(rows, row_stride, is_bf16, cell_to_row, n_rows, occupancy, w_packed, bias, batch, hi, wi, k, co,
+                          max_cells_per_sample, relu, y, stats_partial, stats_shift, overflow, workspace, workspace_bytes, stream);
 }
 
 int liso_sparse_conv_dgrad(const void* dy, long dy_pix_stride, int is_bf16, const float* occupancy, const void* w_packed_dgrad, int batch,

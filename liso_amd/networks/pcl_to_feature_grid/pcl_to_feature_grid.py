@@ -95,6 +95,28 @@ def pillar_prep(points, offsets, pcfg):
     return pt_off, feat, voxel_cell, num_voxels, cell_to_voxel
 
 
+def _pfn_statistics(weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum, eps, prep):
+    """what both canvas forms share: the voxelisation products (`prep`, computed here unless given) and the BatchNorm1d statistics ->
+    (prep, weight fp32 contiguous, bn_out [4 * 64], moments [80]); runs on the current stream of the points' device"""
+    L.require_cuda(points, weight)
+    lib = L.lib()
+    dev = points.device
+    B = len(offsets) - 1
+    if prep is None:
+        prep = pillar_prep(points, offsets, pcfg)
+    pt_off, feat, _, num_voxels, _ = prep
+    weight = weight.contiguous().float()
+    with torch.cuda.device(dev):
+        bn_out = torch.empty(4 * 64, dtype=torch.float32, device=dev)
+        moments = torch.empty(80, dtype=torch.float64, device=dev)
+        partials = torch.empty(lib.liso_pfn_partials_bytes(), dtype=torch.uint8, device=dev)
+        L.check(lib.liso_pfn_bn_prepare_f32(L.ptr(feat), L.ptr(pt_off), ctypes.byref(pcfg), B, L.ptr(num_voxels),
+                                            L.ptr(weight), L.ptr(gamma), L.ptr(beta), L.ptr(running_mean),
+                                            L.ptr(running_var), float(momentum), float(eps), int(training),
+                                            L.ptr(bn_out), L.ptr(moments), L.ptr(partials), L.stream_ptr()), "pfn_bn_prepare")
+    return prep, weight, bn_out, moments
+
+
 class _PillarFeatureScatter(torch.autograd.Function):
     """voxelise (no grad) + fused PFN + scatter; differentiable w.r.t. linear.weight, norm.weight, norm.bias."""
 
@@ -102,23 +124,14 @@ class _PillarFeatureScatter(torch.autograd.Function):
     def forward(ctx, weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum, eps,
                 out_dtype, out=None, prep=None):
         code = L.elem_code(out_dtype)  # (TypeError before anything is allocated or launched: the canvas rows are sized by out_dtype)
-        L.require_cuda(points, weight)
         lib = L.lib()
         dev = points.device
         B = len(offsets) - 1
-        if prep is None:
-            prep = pillar_prep(points, offsets, pcfg)
+        prep, weight, bn_out, moments = _pfn_statistics(weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training,
+                                                        momentum, eps, prep)
         pt_off, feat, voxel_cell, num_voxels, cell_to_voxel = prep
-        weight = weight.contiguous().float()
         with torch.cuda.device(dev):
             st = L.stream_ptr()
-            bn_out = torch.empty(4 * 64, dtype=torch.float32, device=dev)
-            moments = torch.empty(80, dtype=torch.float64, device=dev)
-            partials = torch.empty(lib.liso_pfn_partials_bytes(), dtype=torch.uint8, device=dev)
-            L.check(lib.liso_pfn_bn_prepare_f32(L.ptr(feat), L.ptr(pt_off), ctypes.byref(pcfg), B, L.ptr(num_voxels),
-                                                L.ptr(weight), L.ptr(gamma), L.ptr(beta), L.ptr(running_mean),
-                                                L.ptr(running_var), float(momentum), float(eps), int(training),
-                                                L.ptr(bn_out), L.ptr(moments), L.ptr(partials), st), "pfn_bn_prepare")
             if out is not None:  # caller-owned destination (static graph inputs): [B, gx, gy, 64] rows + occupancy, both dense
                 canvas, occupancy = out
                 assert canvas.shape == (B, pcfg.gx, pcfg.gy, 64) and canvas.dtype == out_dtype and canvas.is_contiguous()
@@ -157,6 +170,41 @@ class _PillarFeatureScatter(torch.autograd.Function):
                                           int(ctx.training), L.ptr(g), L.elem_code(g.dtype), L.ptr(gw), L.ptr(gg),
                                           L.ptr(gb), L.ptr(partials), L.stream_ptr()), "pfn_backward")
         return gw, gg, gb, None, None, None, None, None, None, None, None, None, None, None
+
+
+@torch.no_grad()
+def pillar_rows(weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum, eps, out_dtype, out=None,
+                prep=None):
+    """The encoder's forward with a COMPACT canvas (mfma_conv.PillarCanvas; include/liso_pillars.h: liso_pfn_forward_rows): the same
+    statistics and the same rows as `_PillarFeatureScatter`, stored per pillar -- the dense canvas, zeros in all but 1-6 % of its
+    cells, is not written.  No autograd node: inference only.  `out`: the PillarCanvas (slice) to write into."""
+    from liso_amd.utils.mfma_conv import PillarCanvas
+
+    code = L.elem_code(out_dtype)
+    lib = L.lib()
+    dev = points.device
+    B = len(offsets) - 1
+    prep, weight, bn_out, _ = _pfn_statistics(weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum,
+                                              eps, prep)
+    pt_off, feat, voxel_cell, num_voxels, cell_to_voxel = prep
+    if out is None:
+        out = PillarCanvas.empty(B, (pcfg.gx, pcfg.gy), pcfg.max_voxels, out_dtype, dev)
+    R = B * pcfg.max_voxels
+    assert tuple(out.shape) == (B, 64, pcfg.gx, pcfg.gy) and out.dtype == out_dtype and out.max_voxels == pcfg.max_voxels
+    assert out.row_base + R <= out.rows.shape[0]
+    rows = out.rows[out.row_base:out.row_base + R]
+    with torch.cuda.device(dev):
+        st = L.stream_ptr()
+        cells = B * pcfg.gx * pcfg.gy
+        L.check(L.TIMER.launch("pfn_forward_scatter", lambda: lib.liso_pfn_forward_rows(
+            L.ptr(feat), L.ptr(pt_off), L.ptr(voxel_cell), ctypes.byref(pcfg), B, L.ptr(cell_to_voxel), L.ptr(weight),
+            L.ptr(bn_out), L.ptr(rows), code, out.row_base, L.ptr(out.cell_map), L.ptr(out.occupancy), st),
+            # bytes the launch moves, the terms known on the host: points read once, the voxeliser's map read, the caller's map and
+            # the occupancy written (12 B per cell); the pillars' rows are not counted -- their number is only known on the device
+            # (1-6 % of the cells: 1-2 MB per sweep at 512^2), so the figure is a lower bound of a few per cent
+            units=points.numel() * 4 + cells * 12),
+            "pfn_forward_rows")
+    return out
 
 
 class PointsPillarFeatureNetWrapper(nn.Module):
@@ -234,9 +282,10 @@ class PointsPillarFeatureNetWrapper(nn.Module):
         cat, offsets = self._cat(pts)
         return (cat, offsets, pillar_prep(cat, offsets, self._pcfg(cat.shape[1])))
 
-    def extract_pts_feat(self, pts, out=None, prep=None):
+    def extract_pts_feat(self, pts, out=None, prep=None, compact=False):
         """reference :86-102.  `out` (extension): (canvas rows [B, gx, gy, 64], occupancy [B, 1, gx, gy]) to write into;
-        `prep` (extension): the result of `prepare(pts)` for the same clouds"""
+        `prep` (extension): the result of `prepare(pts)` for the same clouds; `compact` (extension, inference only): the canvas as a
+        mfma_conv.PillarCanvas (`out`: one to write into) -> (PillarCanvas, its occupancy map)"""
         L.elem_code(self.out_dtype)  # an unsupported canvas dtype raises here, before any launch
         if prep is not None:
             cat, offsets, prep = prep
@@ -248,11 +297,16 @@ class PointsPillarFeatureNetWrapper(nn.Module):
         training = self.training and lyr.norm.training
         if training and lyr.norm.track_running_stats:
             lyr.norm.num_batches_tracked += 1
+        if compact:
+            assert not torch.is_grad_enabled(), "the compact canvas has no backward: inference only"
+            canvas = pillar_rows(lyr.linear.weight, lyr.norm.weight, lyr.norm.bias, lyr.norm.running_mean, lyr.norm.running_var, cat,
+                                 offsets, self._pcfg(C), training, lyr.norm.momentum, lyr.norm.eps, self.out_dtype, out, prep)
+            return canvas, canvas.occupancy
         x, occ = _PillarFeatureScatter.apply(lyr.linear.weight, lyr.norm.weight, lyr.norm.bias, lyr.norm.running_mean,
                                              lyr.norm.running_var, cat, offsets, self._pcfg(C), training,
                                              lyr.norm.momentum, lyr.norm.eps, self.out_dtype, out, prep)
         return x, occ
 
-    def forward(self, pcl_t0, img_t0=None, out=None, prep=None):
+    def forward(self, pcl_t0, img_t0=None, out=None, prep=None, compact=False):
         """reference :104-107"""
-        return self.extract_pts_feat(pcl_t0, out=out, prep=prep)
+        return self.extract_pts_feat(pcl_t0, out=out, prep=prep, compact=compact)

@@ -115,6 +115,10 @@ class SmallEncoder(nn.Module):
         if is_list:
             batch_dim = x[0].shape[0]
             x = torch.cat(x, dim=0)
+        if not torch.is_tensor(x):  # (extension) mfma_conv.PillarCanvas: the compact canvas, read through its map by the sparse stem
+            occupancy = x.occupancy if occupancy is None else occupancy
+            if not self._fold_inference(x):
+                x = x.dense()
         if self._fold_inference(x):
             # inference: every InstanceNorm + ReLU is applied by its consumer, residual tails are one kernel (mfma_conv.InFold)
             from liso_amd.utils import mfma_conv as MC

@@ -80,11 +80,39 @@ class RAFT(nn.Module):
         aux["fw_bw_batched"] = both  # per iteration [2B,H,W,8]: samples [:B] = forward flow, [B:] = backward flow
         return [p[:B] for p in both], [p[B:] for p in both], aux
 
-    def encode_pillars(self, pcl_t0, pcl_t1, out=None):
+    def compact_canvas_ok(self, device):
+        """host-side choice, before the encoder runs: can the inference take the pillar canvases in compact form
+        (mfma_conv.PillarCanvas)?  Both encoders' first convolution must run its sparse form on the canvas' geometry and dtype (F32X3
+        mode, not exact fp32) in the folded inference path; `mfma_conv.set_compact_canvas(False)` switches it off everywhere."""
+        from liso_amd.utils import mfma_conv as MC
+
+        if not MC.compact_canvas() or torch.is_grad_enabled() or torch.device(device).type != "cuda":
+            return False
+        pp = self.pp_layer
+        shape, dtype = (1, 64, *pp.grid), pp.out_dtype
+        if dtype != torch.float32:
+            return False
+        return all(getattr(e, "fold_inference", True) and MC._norm_kind(e.norm1) is not None and MC.sparse_stem_covers(shape, dtype, e.conv1)
+                   for e in (self.fnet, self.cnet))
+
+    def encode_pillars(self, pcl_t0, pcl_t1, out=None, compact=False):
         """the pillar canvases of both sweeps: (img_t0, occ_t0, img_t1, occ_t1); differentiable w.r.t. the pillar encoder's
         parameters when gradients are enabled.  `out` = (rows [2B, gx, gy, 64], occupancy [2B, 1, gx, gy]): both sweeps are
         written into these buffers (static hipGraph inputs: no copy, and the batch of both sweeps needs no concatenation);
-        the result then carries a fifth element, the stacked canvas [2B, 64, gx, gy]."""
+        the result then carries a fifth element, the stacked canvas [2B, 64, gx, gy].
+        `compact` (inference only): one mfma_conv.PillarCanvas of 2B samples (`out`: the one to write into) holds both sweeps -- rows,
+        cell -> row map, occupancy -- and the result is (its first B samples, occ_t0, its last B, occ_t1, the whole, occupancy [2B])."""
+        if compact:
+            from liso_amd.utils.mfma_conv import PillarCanvas
+
+            B = len(pcl_t0)
+            assert len(pcl_t1) == B
+            pp = self.pp_layer
+            both = out if out is not None else PillarCanvas.empty(2 * B, pp.grid, pp.max_voxels, pp.out_dtype, pcl_t0[0].device)
+            assert isinstance(both, PillarCanvas) and both.shape[0] == 2 * B and both.row_base == 0
+            a, _ = pp(pcl_t0, out=both[:B], compact=True)
+            b, _ = pp(pcl_t1, out=both[B:], compact=True)
+            return (a, a.occupancy, b, b.occupancy, both, both.occupancy)
         if out is None:
             return (*self.pp_layer(pcl_t0), *self.pp_layer(pcl_t1))
         rows, occ = out
@@ -97,7 +125,8 @@ class RAFT(nn.Module):
         """Inference for consumers of the t0 -> t1 flow only (the box miner): one direction, last iteration.
         -> ([B,H,W,8(+1)] network output, aux).  `canvases`: precomputed `encode_pillars` result (callers that replay the
         rest from a hipGraph keep the pillar encoder outside of it)."""
-        canvases = canvases if canvases is not None else self.encode_pillars(pcl_t0, pcl_t1)
+        if canvases is None:
+            canvases = self.encode_pillars(pcl_t0, pcl_t1, compact=self.compact_canvas_ok(pcl_t0[0].device))
         img_t0, occ_t0, img_t1, occ_t1 = canvases[:4]
         aux = {"t0": {"bev_net_input_dbg": occ_t0}, "t1": {"bev_net_input_dbg": occ_t1}}
         B = img_t0.shape[0]

@@ -896,20 +896,27 @@ class LisoLoopTrainer:
         pcls = (get_network_input_pcls(self.cfg, sample_t0, "ta", to_device=dev), get_network_input_pcls(self.cfg, sample_t1, "ta", to_device=dev))
         st = self._infer_graphs.lookup(sig)
         with torch.no_grad():  # pillar encoder eagerly (its rocPRIM sort memsets: liso_amd/utils/graph_safety.py) ...
+            # (compact canvases -- mfma_conv.PillarCanvas -- where the encoders' stems read them: the graph's static inputs are then
+            # the pillar rows, the cell -> row map and the occupancy map, ~25 MB per pair instead of the dense canvases' 134 MB)
+            compact = raft.compact_canvas_ok(dev) if st is None else st["compact"]
             if st is None:
-                canv = raft.encode_pillars(*pcls)
+                canv = raft.encode_pillars(*pcls, compact=compact)
             else:  # ... straight into the graph's input buffers: no copy, no concatenation of the two sweeps
-                raft.encode_pillars(*pcls, out=st["rows"])
+                raft.encode_pillars(*pcls, out=st["rows"], compact=compact)
             # a device scan (torch.cumsum): eagerly, its memset nodes do not survive in a graph (graph_safety.py)
             thr = self.slim.moving_dynamicness_threshold.value()
         if st is None:
             st = self._infer_graphs.insert(sig, {}, self.max_infer_graphs)  # (the least recently used graphs + their buffers go)
             st["in"] = TT.tree_map(ins, lambda t: t.to(dev).clone())
             B_ = canv[0].shape[0]
-            rows = torch.cat([canv[0], canv[2]], dim=0).permute(0, 2, 3, 1).contiguous()  # [2B, gx, gy, 64]
-            occ = torch.cat([canv[1], canv[3]], dim=0).contiguous()
-            st["rows"] = (rows, occ)
-            st["canv"] = (rows[:B_].permute(0, 3, 1, 2), occ[:B_], rows[B_:].permute(0, 3, 1, 2), occ[B_:], rows.permute(0, 3, 1, 2), occ)
+            st["compact"] = compact
+            if compact:  # (encode_pillars allocated the stacked canvas of both sweeps: it becomes the static input as it is)
+                st["rows"], st["canv"] = canv[4], canv
+            else:
+                rows = torch.cat([canv[0], canv[2]], dim=0).permute(0, 2, 3, 1).contiguous()  # [2B, gx, gy, 64]
+                occ = torch.cat([canv[1], canv[3]], dim=0).contiguous()
+                st["rows"] = (rows, occ)
+                st["canv"] = (rows[:B_].permute(0, 3, 1, 2), occ[:B_], rows[B_:].permute(0, 3, 1, 2), occ[B_:], rows.permute(0, 3, 1, 2), occ)
             st["thr"] = thr.clone()
             s0, s1 = st["in"]
             # In the pipeline the captured inference leaves compute units to the other streams (`infer_cus`, LISO_INFER_CUS=n; 0 = all;

@@ -972,8 +972,14 @@ def conv_in(x_raw, fold, conv, norm, relu=True, spec=None, occupancy=None):
     kw = {}
     if fold is not None:
         kw = dict(in_scale=fold.scale, in_shift=fold.shift, in_relu=fold.relu, affine_batch_stride=fold.stride)
+    compact = isinstance(x_raw, PillarCanvas)
+    if compact:
+        assert fold is None
+        occupancy = x_raw.occupancy if occupancy is None else occupancy
     if fold is None and occupancy is not None:
         res = _sparse_stem(x_raw, occupancy, conv.weight, conv.bias, spec, kind, relu)
+        if res is None and compact:  # (a geometry the sparse kernels do not cover: the dense kernels on the dense canvas)
+            x_raw = x_raw.dense()
         if res is not None:
             y, part, _ = res
             if kind == "none":
@@ -1044,6 +1050,68 @@ def _sparse_geometry(shape, dtype, weight, spec):
     return None
 
 
+_COMPACT_CANVAS = True
+
+
+def set_compact_canvas(on):
+    """off: the pillar encoder always materialises the dense canvas [B, gx, gy, 64] (the form the compact one is tested against, bit for
+    bit, and the fallback) -> the previous setting"""
+    global _COMPACT_CANVAS
+    prev, _COMPACT_CANVAS = _COMPACT_CANVAS, bool(on)
+    return prev
+
+
+def compact_canvas():
+    return _COMPACT_CANVAS
+
+
+class PillarCanvas:
+    """The pillar canvas in compact form: `rows` [R, 64] (one feature row per pillar, include/liso_pillars.h: liso_pfn_forward_rows),
+    `cell_map` int32 [B, gx, gy] (row + 1 of every cell, 0 = no pillar; indexes the WHOLE row array) and `occupancy` fp32 [B, 1, gx, gy].
+    The dense canvas -- zeros in the 94-99 % of the cells without a pillar -- is never written; the sparse stem convolutions read the rows
+    through the map (liso_sparse_conv_forward_rows).  Quacks like the logical [B, 64, gx, gy] tensor where only its shape / dtype / device
+    are asked for; `c[lo:hi]` is the canvas of samples lo..hi (same row array, `row_base` = where their pillars' rows start: the encoder
+    of one sweep writes there); `dense()` builds the tensor for consumers that have no compact form."""
+
+    def __init__(self, rows, cell_map, occupancy, max_voxels, row_base=0):
+        assert rows.dim() == 2 and rows.is_contiguous() and cell_map.dtype == torch.int32 and cell_map.is_contiguous()
+        assert occupancy.dim() == 4 and tuple(occupancy.shape[2:]) == tuple(cell_map.shape[1:]) and occupancy.is_contiguous()
+        self.rows, self.cell_map, self.occupancy, self.max_voxels, self.row_base = rows, cell_map, occupancy, int(max_voxels), int(row_base)
+
+    @staticmethod
+    def empty(batch, grid, max_voxels, dtype, device):
+        return PillarCanvas(torch.empty((batch * max_voxels, 64), dtype=dtype, device=device),
+                            torch.empty((batch, *grid), dtype=torch.int32, device=device),
+                            torch.empty((batch, 1, *grid), dtype=torch.float32, device=device), max_voxels)
+
+    shape = property(lambda self: torch.Size((self.cell_map.shape[0], self.rows.shape[1], *self.cell_map.shape[1:])))
+    dtype = property(lambda self: self.rows.dtype)
+    device = property(lambda self: self.rows.device)
+    is_cuda = property(lambda self: self.rows.is_cuda)
+
+    def dim(self):
+        return 4
+
+    def __getitem__(self, key):
+        assert isinstance(key, slice) and key.step in (None, 1), key
+        lo, _, _ = key.indices(self.cell_map.shape[0])
+        return PillarCanvas(self.rows, self.cell_map[key], self.occupancy[key], self.max_voxels, self.row_base + lo * self.max_voxels)
+
+    def dense(self):
+        """the logical [B, 64, gx, gy] tensor, channels-last storage, zeros where the map is 0 (framework indexing: not a hot path)"""
+        B, C, H, W = self.shape
+        idx = self.cell_map.reshape(-1).long()
+        got = self.rows[(idx - 1).clamp(min=0, max=self.rows.shape[0] - 1)]
+        keep = ((idx > 0) & (idx <= self.rows.shape[0]))[:, None]
+        return torch.where(keep, got, torch.zeros((), dtype=self.dtype, device=self.device)).view(B, H, W, C).permute(0, 3, 1, 2)
+
+
+def sparse_stem_covers(shape, dtype, conv):
+    """host-side: will `_sparse_stem` take the convolution `conv` on a canvas of this logical shape and dtype (then a compact canvas can
+    feed it)?"""
+    return _sparse_geometry(tuple(shape), dtype, conv.weight, ConvSpec.of(conv)) is not None
+
+
 def _sparse_flag(dev):
     idx = _dev_index(dev)
     flag = _SPARSE_OVERFLOW.get(idx)
@@ -1074,7 +1142,12 @@ def _sparse_stem(x_raw, occupancy, weight, bias, spec, kind, relu, stats_shift=N
     flag = _sparse_flag(dev)
     if occ is None or flag is None:
         return None
-    xv, xps = as_nhwc(x_raw, 8 if bf else 4)
+    compact = isinstance(x_raw, PillarCanvas)
+    if compact:
+        xv, xps = x_raw.rows, x_raw.rows.shape[1]
+        assert tuple(x_raw.cell_map.shape) == (B, H, W)
+    else:
+        xv, xps = as_nhwc(x_raw, 8 if bf else 4)
     lib = L.lib()
     cap = min(SPARSE_STEM_MAX_CELLS, H * W)
     nbytes = lib.liso_sparse_conv_workspace_bytes(B, H, W, k, co, cap, 0)
@@ -1089,12 +1162,18 @@ def _sparse_stem(x_raw, occupancy, weight, bias, spec, kind, relu, stats_shift=N
     if groups <= 0:
         return None
     part = torch.empty((B * ho * wo * co // (4096 * groups), 2, co), dtype=torch.float32, device=dev) if kind != "none" else None
-    with torch.cuda.device(dev):
-        L.check(L.TIMER.launch("conv_sparse_stem", lambda: lib.liso_sparse_conv_forward(
-            L.ptr(xv), xps, int(bf), L.ptr(occ), L.ptr(packed), L.ptr(bias) if bias is not None else None, B, H, W, k, co, cap,
+    tail = (L.ptr(occ), L.ptr(packed), L.ptr(bias) if bias is not None else None, B, H, W, k, co, cap,
             int(bool(relu) and kind == "none"), L.ptr(y), L.ptr(part) if part is not None else None,
-            L.ptr(stats_shift) if (stats_shift is not None and part is not None) else None, L.ptr(flag), L.ptr(ws), nbytes, L.stream_ptr()),
-            units=B * ho * wo * co * y.element_size() + B * H * W * 4), "sparse_conv_forward")  # (bytes: the dense output written once + the occupancy map)
+            L.ptr(stats_shift) if (stats_shift is not None and part is not None) else None, L.ptr(flag), L.ptr(ws), nbytes)
+    with torch.cuda.device(dev):
+        if compact:
+            L.check(L.TIMER.launch("conv_sparse_stem", lambda: lib.liso_sparse_conv_forward_rows(
+                L.ptr(xv), xps, int(bf), L.ptr(x_raw.cell_map), xv.shape[0], *tail, L.stream_ptr()),
+                units=B * ho * wo * co * y.element_size() + B * H * W * 4), "sparse_conv_forward_rows")
+        else:
+            L.check(L.TIMER.launch("conv_sparse_stem", lambda: lib.liso_sparse_conv_forward(
+                L.ptr(xv), xps, int(bf), *tail, L.stream_ptr()),
+                units=B * ho * wo * co * y.element_size() + B * H * W * 4), "sparse_conv_forward")  # (bytes: the dense output written once + the occupancy map)
     return y.permute(0, 3, 1, 2), part, ws
 
 
