@@ -106,6 +106,26 @@ typedef struct {
 } liso_conv_pack_job;
 int liso_conv_pack_weights_batched(const liso_conv_pack_job* jobs, int n_jobs, void* stream);
 
+/* The same for tensors PLACED inside a panel whose channel counts K / N may be larger than the tensor's own: element (k, n) of the
+ * tensor's panel orientation lands at (k + k_offset, n + n_offset) of the panel `dst` = liso_conv_packed_bytes(K, N, kh * kw, mode).
+ * Several filters thereby share one panel: the filters of parallel convolutions concatenated along the output channels, or each in
+ * its diagonal block of a block-diagonal filter.  A job writes exactly the 16-byte chunks that hold values of its tensor (a chunk
+ * that straddles the tensor's first or last k is written whole, zero outside the tensor: jobs of one panel must not share a chunk);
+ * everything else -- the K / N padding, the off-diagonal blocks -- is written only when `clear` != 0: every distinct panel is then
+ * zero-filled whole by a launch in front of the pack launch.  clear = 1 is the initial fill of freshly allocated panels, clear = 0 the
+ * repack from the current master weights.  Every job is checked before the first launch (LISO_EINVAL: null / unaligned pointer, a
+ * placement beyond the panel).  With K / N the tensor's own and offsets 0 the bytes are those of liso_conv_pack_weights.
+ * `jobs` is a HOST array read during the call.  These are also the panels liso_adamw_step_packed_f32 (include/liso_optim.h) keeps
+ * current from inside the parameter update. */
+typedef struct {
+    const float* src;
+    void* dst;
+    int d0, d1, kh, kw, transposed, for_dgrad, mode;
+    int K, N;               /* the panel's channel counts */
+    int k_offset, n_offset; /* where the tensor's (0, 0) lands */
+} liso_conv_pack_placed_job;
+int liso_conv_pack_weights_placed(const liso_conv_pack_placed_job* jobs, int n_jobs, int clear, void* stream);
+
 /* rows of the statistics buffer one forward launch writes: stats_partial is fp32 [rows][2][co_pad]
  * (sum and sum of squares of (stored value - stats_shift[c]) over the pixels of one block). */
 int liso_conv_stats_rows(const liso_conv_desc* d);

@@ -38,6 +38,8 @@ int liso_adamw_step_f32(float* param, const float* grad, float* exp_avg, float* 
 int liso_adamw_step_scaled_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
                                double beta2, double eps, double weight_decay, double grad_scale, long step, void* stream);
 
+/* liso_adamw_step_packed_f32, further down: the same update, whose launch also writes the convolutions' packed filter panels. */
+
 /* ---- dynamic loss scaling (fp16 training) ---------------------------------------------------------------------------------------
  * The state lives in device memory and never travels to the host inside a step: the backward pass is seeded with `scale` (read from
  * device memory, so a captured hipGraph replays with the current value), then
@@ -68,6 +70,48 @@ int liso_adamw_step_amp_f32(float* param, const float* grad, float* exp_avg, flo
                             double beta2, double eps, double weight_decay, double grad_scale, const liso_loss_scale_state* state,
                             void* stream);
 int liso_loss_scale_update(liso_loss_scale_state* state, double growth_factor, double backoff_factor, int growth_interval, void* stream);
+
+/* ---- the update that also writes what is derived from the parameters ------------------------------------------------------------------
+ * Between the update and the next step's first convolution a training step used to rebuild, from the fp32 master weights, the packed
+ * filter panels of every convolution (include/liso_conv.h: "Packed weights") and the merged filters of convolutions that run as one
+ * launch (concatenated / block-diagonal filters and their biases).  None of that is arithmetic the result needs: the weights are in
+ * registers once per step, inside the update.  liso_adamw_step_packed_f32 is liso_adamw_step_scaled_f32 -- every element of the flat
+ * buffers is updated exactly once by the same device function, bit for bit -- whose launch also writes, for each listed tensor
+ * [d0][d1][kh][kw] of the flat buffers:
+ *   - up to two panel destinations (forward / data gradient), with the geometry and the bytes of liso_conv_pack_weights(_placed): mode
+ *     LISO_CONV_BF16, LISO_CONV_F32X3 (hi / lo planes) or LISO_CONV_F32, the tensor placed at (k_offset, n_offset) of a panel whose K / N
+ *     may be larger than the tensor's -- so one filter fills its range of a merged convolution's panel or its diagonal block of a
+ *     block-diagonal one;
+ *   - one "mirror": the updated fp32 values stored a second time as d0 rows of d1 * kh * kw floats, `mirror_row_stride` floats apart
+ *     (the merged fp32 filter tensors and concatenated biases; a bias is d0 = 1, d1 = its length).
+ * Only chunks that hold values of a tensor are written: padding (k >= K, n >= N, off-diagonal blocks) is zero-filled once, when the
+ * panels are allocated (liso_conv_pack_weights_placed with clear = 1, which is also the repack whenever the parameters were changed by
+ * anything but this call).
+ * The table is checked and laid out on the host, once: liso_adamw_pack_table_plan -> its size and the launch's block count;
+ * liso_adamw_pack_table_fill -> the image, which the caller copies to device memory (16-byte aligned) and passes to every step.
+ * LISO_EINVAL (nothing is written or launched): a null or misaligned pointer (panels 16 bytes, mirrors 4), a tensor beyond `n`, not at
+ * a multiple of 4 elements or overlapping another, a placement beyond its panel, two destinations sharing a 16-byte chunk, panels /
+ * mirrors that overlap, a mode other than the three above, more than 64 taps.  Work items are 256-thread blocks: tiles of the listed
+ * tensors (the new values pass through <= 16.3 KiB of LDS on their way into the panels) and float4 ranges of everything else. */
+typedef struct {
+    void* dst;              /* the panel (liso_conv_packed_bytes(K, N, kh * kw, mode) bytes) */
+    int for_dgrad, mode;    /* as liso_conv_pack_weights, with the item's `transposed` */
+    int K, N;               /* the panel's channel counts */
+    int k_offset, n_offset; /* where the tensor's (0, 0) lands */
+} liso_adamw_pack_dest;
+typedef struct {
+    size_t offset;          /* first element in the flat buffers */
+    int d0, d1, kh, kw, transposed;
+    int n_dest;             /* 0 .. 2 */
+    liso_adamw_pack_dest dest[2];
+    float* mirror;          /* NULL: none */
+    size_t mirror_row_stride;
+} liso_adamw_pack_item;
+int liso_adamw_pack_table_plan(const liso_adamw_pack_item* items, int n_items, size_t n, size_t* bytes, int* blocks);
+int liso_adamw_pack_table_fill(const liso_adamw_pack_item* items, int n_items, size_t n, void* image, size_t bytes);
+int liso_adamw_step_packed_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, double lr, double beta1,
+                               double beta2, double eps, double weight_decay, double grad_scale, long step, const void* table,
+                               int blocks, void* stream);
 
 /* RMSprop over one flat fp32 buffer (SLIM's optimizer, liso/slim/experiment.py:200-219: torch.optim.RMSprop(lr) with its defaults
  * alpha 0.99, eps 1e-8, no momentum, not centered), the element-wise operations of torch's multi-tensor implementation:

@@ -223,6 +223,7 @@ SIGNATURES = {
     "liso_centerloss_bwd_f32": (_i, [_vp] * 21),
     "liso_render_center_targets_f32": (_i, [_vp] * 12),
     "liso_conv_pack_weights_batched": (_i, [_vp, _i, _vp]),
+    "liso_conv_pack_weights_placed": (_i, [_vp, _i, _i, _vp]),
     "liso_conv_in_finalize": (_i, [_vp, _i, _i, _i, _i, ctypes.c_long, _vp, _vp, _f, _vp, _vp]),
     "liso_residual_affine_relu_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, ctypes.c_long, _i, _vp]),
     # include/liso_box_mining.h
@@ -237,6 +238,9 @@ SIGNATURES = {
     # include/liso_optim.h
     "liso_adamw_step_f32": (_i, [_vp, _vp, _vp, _vp, _sz] + [ctypes.c_double] * 5 + [ctypes.c_long, _vp]),
     "liso_adamw_step_scaled_f32": (_i, [_vp, _vp, _vp, _vp, _sz] + [ctypes.c_double] * 6 + [ctypes.c_long, _vp]),
+    "liso_adamw_pack_table_plan": (_i, [_vp, _i, _sz, _vp, _vp]),
+    "liso_adamw_pack_table_fill": (_i, [_vp, _i, _sz, _vp, _sz]),
+    "liso_adamw_step_packed_f32": (_i, [_vp, _vp, _vp, _vp, _sz] + [ctypes.c_double] * 6 + [ctypes.c_long, _vp, _i, _vp]),
     "liso_grad_nonfinite_f32": (_i, [_vp, _sz, _vp, _vp]),
     "liso_adamw_step_amp_f32": (_i, [_vp, _vp, _vp, _vp, _sz] + [ctypes.c_double] * 6 + [_vp, _vp]),
     "liso_loss_scale_update": (_i, [_vp, ctypes.c_double, ctypes.c_double, _i, _vp]),
@@ -372,6 +376,23 @@ class ConvDesc(ctypes.Structure):
                 ("class_oox", _i * CONV_MAX_CLASSES), ("n_taps", _i), ("tap_dy", _i * CONV_MAX_TAPS), ("tap_dx", _i * CONV_MAX_TAPS),
                 ("tap_w", _i * CONV_MAX_TAPS), ("w_taps", _i), ("mode", _i), ("out_f32", _i), ("in_relu", _i), ("out_relu", _i),
                 ("in_affine_batch_stride", _i), ("wgrad_co", _i)]
+
+
+class ConvPackPlacedJob(ctypes.Structure):
+    """mirror of liso_conv_pack_placed_job (include/liso_conv.h)"""
+    _fields_ = [("src", _vp), ("dst", _vp), ("d0", _i), ("d1", _i), ("kh", _i), ("kw", _i), ("transposed", _i), ("for_dgrad", _i),
+                ("mode", _i), ("K", _i), ("N", _i), ("k_offset", _i), ("n_offset", _i)]
+
+
+class AdamwPackDest(ctypes.Structure):
+    """mirror of liso_adamw_pack_dest (include/liso_optim.h)"""
+    _fields_ = [("dst", _vp), ("for_dgrad", _i), ("mode", _i), ("K", _i), ("N", _i), ("k_offset", _i), ("n_offset", _i)]
+
+
+class AdamwPackItem(ctypes.Structure):
+    """mirror of liso_adamw_pack_item (include/liso_optim.h)"""
+    _fields_ = [("offset", _sz), ("d0", _i), ("d1", _i), ("kh", _i), ("kw", _i), ("transposed", _i), ("n_dest", _i),
+                ("dest", AdamwPackDest * 2), ("mirror", _vp), ("mirror_row_stride", _sz)]
 
 
 class ConvPackJob(ctypes.Structure):

@@ -31,6 +31,7 @@
 #include "conv_plan.h"
 #include "dev_common.h"
 #include "elem16.h"
+#include "pack_chunk.h"
 #include "per_device.h"
 
 namespace {
@@ -47,13 +48,10 @@ __device__ __forceinline__ int xcd_remap(int bid, int total) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    const __bf16 x = (__bf16)a, y = (__bf16)b;
-    return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
-}
+using liso_pack::pack_bf16;  // (pack_chunk.h: shared with the AdamW pass that writes panels)
+using liso_pack::round_bf16;
 __device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ float round_bf16(float v) { return (float)(__bf16)v; }
 
 __device__ __forceinline__ bf8 as_bf8(const uint4& v) { return __builtin_bit_cast(bf8, v); }
 
@@ -1476,16 +1474,30 @@ __global__ __launch_bounds__(kThreads, 2) void conv_taps_kernel(const liso_conv_
 }
 
 // ---- weight packing ---------------------------------------------------------------------------------------------------------
+// (formats, chunk counts and the chunk itself: pack_chunk.h)
+using liso_pack::kPackBf16;
+using liso_pack::kPackF16;
+using liso_pack::kPackF32;
+using liso_pack::pack_chunks;
+using liso_pack::pack_format;
+
+// chunk q of a whole panel from src[ia][ib][tap]; the panel's k / n are the tensor's, zero beyond K / N
 __device__ __forceinline__ void pack_chunk(const float* __restrict__ src, int d1, int taps, int swap_ab, int K, int N, int Kp, int Np,
-                                           int fmt, unsigned short* __restrict__ dst, long q);
-
-// panel formats: 16-bit planes of bf16 (BF16, F32X3 hi / lo), exact fp32, one fp16 plane
-constexpr int kPackBf16 = 0, kPackF32 = 1, kPackF16 = 2;
-__host__ __device__ inline int pack_format(int mode) { return mode == LISO_CONV_F32 ? kPackF32 : mode == LISO_CONV_F16 ? kPackF16 : kPackBf16; }
-
-// 16-B chunks of the packed weights: 16-bit planes x taps x Kp/8 x Np; exact fp32 (one plane of 4-float groups): taps x Kp/4 x Np
-__host__ __device__ inline long pack_chunks(int planes, int taps, int Kp, int Np, int fmt) {
-    return fmt == kPackF32 ? (long)taps * (Kp / 4) * Np : (long)planes * taps * (Kp / 8) * Np;
+                                           int fmt, unsigned short* __restrict__ dst, long q) {
+    const int n = (int)(q % Np);
+    long t = q / Np;
+    const int kcs = Kp / liso_pack::pack_chunk_k(fmt);
+    const int kc = (int)(t % kcs);
+    t /= kcs;
+    const int tap = (int)(t % taps);
+    const int plane = (int)(t / taps);  // (exact fp32: one plane)
+    liso_pack::pack_chunk_at(
+        [&](int k, int nn, int tp) {
+            if (k >= K || nn >= N) return 0.0f;
+            const int ia = swap_ab ? k : nn, ib = swap_ab ? nn : k;  // src[ia][ib][tap]
+            return src[((long)ia * d1 + ib) * taps + tp];
+        },
+        fmt, plane, tap, kc, n, taps, Kp, Np, dst);
 }
 
 __global__ void pack_weights_kernel(const float* __restrict__ src, int d0, int d1, int taps, int swap_ab, int K, int N, int Kp,
@@ -1518,52 +1530,55 @@ __global__ void pack_weights_batched_kernel(const PackTable t) {
     pack_chunk(b.src, b.d1, b.taps, b.swap_ab, b.K, b.N, b.Kp, b.Np, b.fmt, b.dst, q - (j ? t.end[j - 1] : 0));
 }
 
-__device__ __forceinline__ void pack_chunk(const float* __restrict__ src, int d1, int taps, int swap_ab, int K, int N, int Kp, int Np,
-                                           int fmt, unsigned short* __restrict__ dst, long q) {
-    const int n = (int)(q % Np);
-    long t = q / Np;
-    if (fmt == kPackF32) {  // [tap][Kp / 4][Np][4] fp32, unrounded
-        const int k4 = (int)(t % (Kp / 4));
-        const int tap = (int)(t / (Kp / 4));
-        float f[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int k = k4 * 4 + e;
-            f[e] = 0.0f;
-            if (k < K && n < N) {
-                const int ia = swap_ab ? k : n, ib = swap_ab ? n : k;
-                f[e] = src[((long)ia * d1 + ib) * taps + tap];
-            }
-        }
-        *reinterpret_cast<float4*>(dst + q * 8) = make_float4(f[0], f[1], f[2], f[3]);
-        return;
-    }
-    const int k8 = (int)(t % (Kp / 8));
-    t /= (Kp / 8);
-    const int tap = (int)(t % taps);
-    const int plane = (int)(t / taps);
-    unsigned w[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        float f[2];
-#pragma unroll
-        for (int z = 0; z < 2; z++) {
-            const int k = k8 * 8 + 2 * e + z;
-            float v = 0.0f;
-            if (k < K && n < N) {
-                const int ia = swap_ab ? k : n, ib = swap_ab ? n : k;  // src[ia][ib][tap]
-                v = src[((long)ia * d1 + ib) * taps + tap];
-            }
-            if (fmt == kPackF16) {
-                f[z] = v;
-            } else {
-                const float hi = round_bf16(v);
-                f[z] = plane == 0 ? hi : (v - hi);
-            }
-        }
-        w[e] = fmt == kPackF16 ? liso_e16::F16::pack(f[0], f[1]) : pack_bf16(f[0], f[1]);
-    }
-    *reinterpret_cast<uint4*>(dst + q * 8) = make_uint4(w[0], w[1], w[2], w[3]);
+// a tensor placed at (k_off, n_off) inside a panel of larger K / N (include/liso_conv.h: liso_conv_pack_weights_placed): only the
+// chunks that hold values of the tensor are written -- per (plane, tap): chunks kc0 .. kc0 + nkc of the columns n_off .. n_off + N
+constexpr int kPlacedJobs = 32;
+struct PlacedJob {
+    const float* src;
+    unsigned short* dst;
+    int d1, taps, swap_ab, K, N, Kp, Np, fmt, planes, k_off, n_off, kc0, nkc;
+};
+struct PlacedTable {
+    PlacedJob job[kPlacedJobs];
+    long end[kPlacedJobs];
+    int n;
+};
+
+__global__ void pack_weights_placed_kernel(const PlacedTable t) {
+    long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= t.end[t.n - 1]) return;
+    int j = 0;
+    while (q >= t.end[j]) j++;
+    const PlacedJob& b = t.job[j];
+    q -= j ? t.end[j - 1] : 0;
+    const int n = (int)(q % b.N);
+    q /= b.N;
+    const int kc = b.kc0 + (int)(q % b.nkc);
+    q /= b.nkc;
+    const int tap = (int)(q % b.taps);
+    const int plane = (int)(q / b.taps);
+    const float* __restrict__ src = b.src;
+    liso_pack::pack_chunk_at(
+        [&](int kp, int, int tp) {
+            const int k = kp - b.k_off;
+            if (k < 0 || k >= b.K) return 0.0f;
+            const int ia = b.swap_ab ? k : n, ib = b.swap_ab ? n : k;
+            return src[((long)ia * b.d1 + ib) * b.taps + tp];
+        },
+        b.fmt, plane, tap, kc, n + b.n_off, b.taps, b.Kp, b.Np, b.dst);
+}
+
+struct ZeroTable {
+    uint4* dst[kPlacedJobs];
+    long end[kPlacedJobs];  // exclusive prefix of 16-B counts
+    int n;
+};
+__global__ void zero_panels_kernel(const ZeroTable t) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= t.end[t.n - 1]) return;
+    int j = 0;
+    while (q >= t.end[j]) j++;
+    t.dst[j][q - (j ? t.end[j - 1] : 0)] = make_uint4(0, 0, 0, 0);
 }
 
 // ---- BatchNorm statistics from the per-block partial sums ---------------------------------------------------------------------
@@ -1771,6 +1786,57 @@ int liso_conv_pack_weights_batched(const liso_conv_pack_job* jobs, int n_jobs, v
             t.end[i] = run;
         }
         pack_weights_batched_kernel<<<(unsigned)((run + 255) / 256), 256, 0, (hipStream_t)stream>>>(t);
+    }
+    return check_launch();
+}
+
+int liso_conv_pack_weights_placed(const liso_conv_pack_placed_job* jobs, int n_jobs, int clear, void* stream) {
+    if (n_jobs == 0) return LISO_OK;
+    if (!jobs || n_jobs < 0) return LISO_EINVAL;
+    for (int i = 0; i < n_jobs; i++) {  // every job is checked before the first launch
+        const liso_conv_pack_placed_job& j = jobs[i];
+        if (!j.src || !j.dst || ((uintptr_t)j.dst & 15) || j.d0 <= 0 || j.d1 <= 0 || j.kh <= 0 || j.kw <= 0) return LISO_EINVAL;
+        if (j.mode != LISO_CONV_BF16 && j.mode != LISO_CONV_F32X3 && j.mode != LISO_CONV_F32 && j.mode != LISO_CONV_F16) return LISO_EINVAL;
+        const bool same = (j.transposed != 0) == (j.for_dgrad != 0);
+        const int K = same ? j.d1 : j.d0, N = same ? j.d0 : j.d1;
+        if (j.K <= 0 || j.N <= 0 || j.k_offset < 0 || j.n_offset < 0) return LISO_EINVAL;
+        if ((long)j.k_offset + K > j.K || (long)j.n_offset + N > j.N) return LISO_EINVAL;
+    }
+    if (clear) {  // every distinct panel once, whole (padding and the parts no job fills stay zero from here on)
+        for (int base = 0; base < n_jobs;) {
+            ZeroTable z;
+            z.n = 0;
+            long run = 0;
+            int i = base;
+            for (; i < n_jobs && z.n < kPlacedJobs; i++) {
+                bool seen = false;
+                for (int k = 0; k < i && !seen; k++) seen = jobs[k].dst == jobs[i].dst;
+                if (seen) continue;
+                const liso_conv_pack_placed_job& j = jobs[i];
+                run += (long)(liso_conv_packed_bytes(j.K, j.N, j.kh * j.kw, j.mode) / 16);
+                z.dst[z.n] = (uint4*)j.dst;
+                z.end[z.n++] = run;
+            }
+            base = i;
+            if (z.n) zero_panels_kernel<<<(unsigned)((run + 255) / 256), 256, 0, (hipStream_t)stream>>>(z);
+        }
+    }
+    for (int base = 0; base < n_jobs; base += kPlacedJobs) {
+        PlacedTable t;
+        t.n = n_jobs - base < kPlacedJobs ? n_jobs - base : kPlacedJobs;
+        long run = 0;
+        for (int i = 0; i < t.n; i++) {
+            const liso_conv_pack_placed_job& j = jobs[base + i];
+            const bool same = (j.transposed != 0) == (j.for_dgrad != 0);
+            const int K = same ? j.d1 : j.d0, N = same ? j.d0 : j.d1;
+            const int fmt = pack_format(j.mode), planes = liso_pack::pack_planes(j.mode), kck = liso_pack::pack_chunk_k(fmt);
+            const int kc0 = j.k_offset / kck, nkc = (j.k_offset + K + kck - 1) / kck - kc0;
+            t.job[i] = PlacedJob{j.src, (unsigned short*)j.dst, j.d1, j.kh * j.kw, same ? 0 : 1, K, N, round_up(j.K, 16), round_up(j.N, 64),
+                                 fmt, planes, j.k_offset, j.n_offset, kc0, nkc};
+            run += (long)planes * (j.kh * j.kw) * nkc * N;
+            t.end[i] = run;
+        }
+        pack_weights_placed_kernel<<<(unsigned)((run + 255) / 256), 256, 0, (hipStream_t)stream>>>(t);
     }
     return check_launch();
 }

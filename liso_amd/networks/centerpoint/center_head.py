@@ -17,10 +17,14 @@ class _BlockDiagonalFilters(torch.autograd.Function):
     (launch-bound: 9 + 21 + 28 us per head at B = 4).  Backward: the diagonal blocks of the dense weight gradient."""
 
     @staticmethod
-    def forward(ctx, n, *wb):
+    def forward(ctx, n, static, *wb):
+        """`static`: (W, bias) that an optimizer table keeps current (mfma_conv.merged_static) -- then nothing is launched -- or None"""
         ws, bs = wb[:n], wb[n:]
         co = [w.shape[0] for w in ws]
         ci = [w.shape[1] for w in ws]
+        if static is not None:
+            ctx.co, ctx.ci, ctx.device_blocks = co, ci, True
+            return static[0].detach(), static[1].detach()
         W = ws[0].new_zeros((sum(co), sum(ci)) + tuple(ws[0].shape[2:]))
         ctx.co, ctx.ci = co, ci
         ctx.device_blocks = W.is_cuda and W.dtype == torch.float32
@@ -53,12 +57,12 @@ class _BlockDiagonalFilters(torch.autograd.Function):
                 gbs.append(gb[o:o + a] if gb is not None else None)
                 o, c = o + a, c + b
             L.copy_blocks(jobs)
-            return (None, *gws, *gbs)
+            return (None, None, *gws, *gbs)
         for a, b in zip(ctx.co, ctx.ci):
             gws.append(gW[o:o + a, c:c + b].contiguous() if gW is not None else None)
             gbs.append(gb[o:o + a] if gb is not None else None)
             o, c = o + a, c + b
-        return (None, *gws, *gbs)
+        return (None, None, *gws, *gbs)
 
 
 class SepHead(nn.Module):
@@ -97,7 +101,10 @@ class SepHead(nn.Module):
             # every head reads its channels of the result (a split: its backward is one concatenation of the heads' gradients)
             import types
 
-            W, b = _BlockDiagonalFilters.apply(len(lasts), *[l.weight for l in lasts], *[l.bias for l in lasts])
+            static = MC.merged_static("blockdiag", [l.weight for l in lasts])
+            W, b = _BlockDiagonalFilters.apply(len(lasts), static, *[l.weight for l in lasts], *[l.bias for l in lasts])
+            if static is None:
+                MC.note_merged_filter("blockdiag", W, [l.weight for l in lasts], [l.bias for l in lasts])
             y, _ = MC.fused_conv(hid, hfold, types.SimpleNamespace(weight=W, bias=b), out_dtype=torch.float32, spec=MC.ConvSpec.of(lasts[0]))
             return dict(zip(self.heads, torch.split(y, [l.out_channels for l in lasts], dim=1)))
         # (split, not four slices: the backward of split is ONE concatenation of the heads' input gradients, the backward of each

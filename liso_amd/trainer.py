@@ -148,8 +148,18 @@ def _captured_training_pass(tr, canvases, second_half=False):
         # gradient -- a 134-MB fill and a 400-MB accumulation into zeros per detector step at B = 4 otherwise)
         for c in canvases:
             c.grad = None
-        tr._step_packs = MC.batched_pack(tr._pack_jobs) if tr._pack_jobs else None
-    MC.set_step_packs(tr._step_packs)
+        opt_packs = getattr(tr, "_opt_packs", None) if MC.optimizer_packs_enabled() else None
+        if opt_packs is not None:
+            # panels and merged filters that the AdamW launch keeps current: no pack launch, no filter-building copy in this step
+            # (requests the table does not cover are packed as before)
+            tr._step_packs = dict(opt_packs.panels)
+            if opt_packs.leftover_jobs:
+                tr._step_packs.update(MC.batched_pack(opt_packs.leftover_jobs))
+            tr._step_merged = opt_packs.merged
+        else:
+            tr._step_packs = MC.batched_pack(tr._pack_jobs) if tr._pack_jobs else None
+            tr._step_merged = None
+    MC.set_step_packs(tr._step_packs, getattr(tr, "_step_merged", None))
     gathered = tr._gather_params or []
     for p_, _ in gathered:  # (autograd then KEEPS the gradient tensor it is handed instead of adding it into the zeroed slice)
         p_.grad = None
@@ -187,6 +197,7 @@ class DetectorTrainer:
         _prepare_device(device, exact)
         self.use_graph = bool(use_graph) and device.type == "cuda"
         self._graph, self._graph2, self._graph_sig = None, None, None
+        self._opt_packs = None
         self.fused_loss = (fused_centerpoint.supports(cfg) and device.type == "cuda") if fused_loss is None else fused_loss
         self.net = BoxLearner(cfg).to(device)
         self.net.model.set_compute_dtype(compute_dtype)
@@ -400,18 +411,38 @@ class DetectorTrainer:
                 self._gather_params = [(p_, p_.grad) for p_ in self.net.parameters()
                                        if p_.requires_grad and p_.grad is not None and id(p_) not in in_place and id(p_) not in outside]
 
+            if self._opt_packs is not None:
+                self._opt_packs.ensure_current()  # (the warm-up passes of a re-capture read the table's panels)
             GC.warm_up(body, side, pack_jobs=self._pack_jobs, after_first=after_first_pass, restore=restore)
+            self._attach_optimizer_packs(MC.recorded_merged_jobs())
             if cut is None:
                 self._graph, self._static_loss = GC.capture(body, side)
             else:  # two graphs sharing one memory pool: the second one reads the leaf gradient and the saved tensors of the first
                 self._graph, self._static_loss = GC.capture(lambda: body(1), side)
                 self._graph2, _ = GC.capture(lambda: body(2), side, pool=self._graph.pool())
 
+    def _attach_optimizer_packs(self, merged_jobs):
+        """after the warm-up of the first capture: the panels / merged filters its pack requests asked for become outputs of the AdamW
+        launch (liso_amd/utils/optimizer_packs.py).  Built once: a re-capture for another input signature asks for the same panels."""
+        from liso_amd.utils import mfma_conv as MC
+        from liso_amd.utils.flat_adamw import FlatAdamW
+
+        if self._opt_packs is not None or not MC.optimizer_packs_enabled() or not self._pack_jobs:
+            return
+        if not isinstance(self.optimizer, FlatAdamW) or self.optimizer.loss_scale is not None:
+            return  # (the fp16 loss-scaled update keeps its own launches)
+        from liso_amd.utils.optimizer_packs import OptimizerPacks
+
+        self._opt_packs = OptimizerPacks(self.optimizer, self._pack_jobs, merged_jobs)
+        self.optimizer.attach_packs(self._opt_packs)
+
     def _graph_step(self, pcls, targets, prep=None):
         # what the graph consumes: the [B, 64, gx, gy] canvas (batch size; grid and dtype are fixed per trainer) and the target maps.
         # The clouds themselves never enter it (the pillar encoder runs eagerly in front): their point counts are not part of the key.
         tsig = targets.shapes() if isinstance(targets, _BatchedTargets) else tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(targets.items()))
-        sig = (len(pcls), tsig)
+        from liso_amd.utils import mfma_conv as MC
+
+        sig = (len(pcls), tsig, MC.optimizer_packs_enabled())
         if self._graph is None or sig != self._graph_sig:
             self._graph = None
             self._capture(pcls, targets)
@@ -431,6 +462,9 @@ class DetectorTrainer:
                 for k, v in targets.items():
                     stage.append((self._static_targets[k], v))
             L.multi_copy(stage)
+        if self._opt_packs is not None and sig[2]:
+            # the captured step reads panels the optimizer wrote: repack (one launch) if anything else has touched a parameter since
+            self._opt_packs.ensure_current()
         self._graph.replay()
 
         def rest_of_backward():

@@ -52,6 +52,13 @@ class FlatAdamW(torch.optim.Optimizer):
                 g.copy_(p.grad)
             p.grad = g
             self.state[p] = {"step": torch.tensor(0.0), "exp_avg": view(self.flat_exp_avg), "exp_avg_sq": view(self.flat_exp_avg_sq)}
+        # an OptimizerPacks (liso_amd/utils/optimizer_packs.py): the update launch then also writes the convolutions' packed panels and
+        # merged filters (liso_adamw_step_packed_f32).  None, a loss scale, or mfma_conv.set_optimizer_packs(False): the plain update.
+        self.packs = None
+
+    def attach_packs(self, packs):
+        """`packs`: built for THIS optimizer's flat buffers; allocated once, outside any graph's pool.  None detaches."""
+        self.packs = packs
 
     def zero_grad(self, set_to_none=False):
         """one memset; the .grad views stay (set_to_none is ignored: autograd accumulates into the flat buffer)"""
@@ -69,13 +76,26 @@ class FlatAdamW(torch.optim.Optimizer):
             torch.autograd.graph.increment_version(g["params"])
             return
         self._step += 1
+        packs = self.packs
+        if packs is not None:
+            from liso_amd.utils import mfma_conv as MC
+
+            packs = packs if MC.optimizer_packs_enabled() else None
+        scalars = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                   float(self.grad_scale), self._step)
         with torch.cuda.device(self.flat_param.device):
-            L.check(L.TIMER.launch("adamw_flat", lambda: L.lib().liso_adamw_step_scaled_f32(
-                L.ptr(self.flat_param), L.ptr(self.flat_grad), L.ptr(self.flat_exp_avg), L.ptr(self.flat_exp_avg_sq), self.numel,
-                float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                float(self.grad_scale), self._step, L.stream_ptr()), units=28 * self.numel), "adamw_step")
+            if packs is not None:  # the same update, and the panels / merged filters of the new parameters from the same launch
+                L.check(L.TIMER.launch("adamw_pack", lambda: L.lib().liso_adamw_step_packed_f32(
+                    L.ptr(self.flat_param), L.ptr(self.flat_grad), L.ptr(self.flat_exp_avg), L.ptr(self.flat_exp_avg_sq), self.numel,
+                    *scalars, L.ptr(packs.table), packs.blocks, L.stream_ptr()), units=28 * self.numel), "adamw_step_packed")
+            else:
+                L.check(L.TIMER.launch("adamw_flat", lambda: L.lib().liso_adamw_step_scaled_f32(
+                    L.ptr(self.flat_param), L.ptr(self.flat_grad), L.ptr(self.flat_exp_avg), L.ptr(self.flat_exp_avg_sq), self.numel,
+                    *scalars, L.stream_ptr()), units=28 * self.numel), "adamw_step")
         # the kernel wrote through a raw pointer: tell autograd / the packed-weight cache that every parameter changed
         torch.autograd.graph.increment_version(g["params"])
+        if packs is not None:
+            packs.stamp()
 
     def state_dict(self):
         if self.loss_scale is not None:  # (the applied-step counter lives on the device)
