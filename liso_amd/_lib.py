@@ -343,6 +343,9 @@ SIGNATURES = {
     "liso_select_tracks": (_i, [_i] * 5 + [_vp] * 7 + [_i, _f, _d, _d, _i, _d, _d, _i, _d] + [_vp] * 13 + [_vp, _sz, _vp]),
     "liso_refine_tracks_apply": (_i, [_i] * 3 + [_vp] * 12 + [_i, _i, _d] + [_vp] * 7 + [_vp]),
     "liso_export_tracks": (_i, [_i] * 6 + [_vp] * 11 + [_i] + [_vp] * 13 + [_vp, _sz, _vp]),
+    # include/liso_frame_prep.h
+    "liso_frame_prep_workspace_bytes": (_sz, [_vp]),
+    "liso_prepare_tracker_frames": (_i, [_vp] * 27 + [_sz, _vp]),
 }
 
 
@@ -444,6 +447,13 @@ class SlimNpLossCfg(ctypes.Structure):
 class BoxPtsCfg(ctypes.Structure):
     """mirror of liso_boxpts_cfg (include/liso_tracking.h)"""
     _fields_ = [("batch", _i), ("n", ctypes.c_long), ("k", _i), ("point_stride", _i), ("precision", _i), ("dims_bloat", _f)]
+
+
+class FramePrepCfg(ctypes.Structure):
+    """mirror of liso_frame_prep_cfg (include/liso_frame_prep.h)"""
+    _fields_ = [("n_seq", _i), ("max_frames", _i), ("max_box", _i), ("cap", _i), ("n_points", ctypes.c_long), ("point_stride", _i),
+                ("n_fov_points", ctypes.c_long), ("fov_stride", _i), ("bev_range_x", _f), ("bev_range_y", _f), ("drop_on_bev_boundaries", _i),
+                ("min_points_in_box", _i), ("fov_min_points", _i), ("align", _i), ("no_align_below_m", _d), ("full_align_above_m", _d)]
 
 
 class GruCfg(ctypes.Structure):

@@ -16,6 +16,7 @@
 
 #include "../../include/liso_iou3d.h"
 #include "../../include/liso_tracking.h"
+#include "box_inside.h"
 
 namespace {
 
@@ -23,35 +24,9 @@ constexpr int kThreads = 256;  // one point per thread
 constexpr int kTile = 128;     // boxes per block (LDS tile)
 constexpr double kFixedScale = 16777216.0;  // 2^24 per metre
 
-// One box in LDS, 64 B: rows x and y of inv(sensor_T_box) = [Rz(yaw)^T | -Rz^T pos] are (c, s, 0, m03) and (-s, c, 0, m13),
-// row z is (0, 0, 1, tz); the zero entries are not stored (adding 0 * z changes nothing for finite z; non-finite points
-// are excluded before the test).
-struct BoxRow {
-    double c, s, m03, m13, tz;
-    float hx, hy, hz;  // 0.5 * bloat * dims
-    float pad;
-};
-struct PreRow {
-    float x, y, r2;  // conservative circle around the box footprint: fp32 reject before the exact test
-    int count;
-};
-
-template <int PREC>
-__device__ __forceinline__ bool inside(const BoxRow& r, float px, float py, float pz) {
-    float bx, by, bz;
-    if (PREC == 0) {  // fp64 product, rounded to fp32 (torch_dataset_commons.py:1914-1918)
-        const double dx = px, dy = py, dz = pz;
-        bx = (float)(r.c * dx + r.s * dy + r.m03);
-        by = (float)(r.c * dy - r.s * dx + r.m13);
-        bz = (float)(dz + r.tz);
-    } else {          // inverse rounded to fp32, fp32 product (shape_utils.py:514-518)
-        const float c = (float)r.c, s = (float)r.s;
-        bx = fmaf(s, py, c * px) + (float)r.m03;
-        by = fmaf(c, py, -s * px) + (float)r.m13;
-        bz = pz + (float)r.tz;
-    }
-    return fabsf(bx) < r.hx && fabsf(by) < r.hy && fabsf(bz) < r.hz;
-}
+using liso_box::BoxRow;  // the inverse pose of a box as an LDS row, its reject circle and the exact test: box_inside.h
+using liso_box::PreRow;
+using liso_box::inside;
 
 template <int PREC>
 __global__ __launch_bounds__(kThreads) void points_in_boxes_kernel(liso_boxpts_cfg c, const float* __restrict__ boxes,
@@ -65,20 +40,7 @@ __global__ __launch_bounds__(kThreads) void points_in_boxes_kernel(liso_boxpts_c
     const int b = blockIdx.z, tile0 = blockIdx.y * kTile, tk = min(kTile, c.k - tile0);
     if ((int)threadIdx.x < tk) {
         const int j = threadIdx.x;
-        const float* box = boxes + ((size_t)b * c.k + tile0 + j) * 7;
-        // Shape.get_poses: sensor_T_box = [Rz(yaw) | pos] in fp64 (shape_utils.py:271-319)
-        const double x = box[0], y = box[1], z = box[2], yaw = box[6];
-        const double cs = cos(yaw), sn = sin(yaw);
-        BoxRow r;
-        r.c = cs; r.s = sn; r.m03 = -(cs * x + sn * y); r.m13 = sn * x - cs * y; r.tz = -z;
-        r.hx = 0.5f * (c.dims_bloat * box[3]); r.hy = 0.5f * (c.dims_bloat * box[4]); r.hz = 0.5f * (c.dims_bloat * box[5]);
-        r.pad = 0.f;
-        rows[j] = r;
-        // inside => bx^2 + by^2 < hx^2 + hy^2; the margin covers the fp32 rounding of the squared distance at |xy| <= 1e4 m
-        const float r2 = r.hx * r.hx + r.hy * r.hy;
-        pre[j].x = box[0]; pre[j].y = box[1];
-        pre[j].r2 = r2 * 1.001f + 0.05f;  // NaN boxes: every comparison below is false -> never inside
-        pre[j].count = 0;
+        liso_box::make_box_row(boxes + ((size_t)b * c.k + tile0 + j) * 7, c.dims_bloat, rows[j], pre[j]);
         fs[j][0] = fs[j][1] = fs[j][2] = 0;
     }
     __syncthreads();

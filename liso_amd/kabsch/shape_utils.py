@@ -261,3 +261,27 @@ def extract_motion_in_pred_box_coordinates(pred_boxes_a, fg_kabsch_trafos, bg_ka
     """reference :563-580"""
     return torch_decompose_matrix(
         extract_box_motion_transform_without_sensor_odometry(pred_boxes_a, fg_kabsch_trafos, bg_kabsch_trafo, check=check))
+
+
+def soft_align_box_flip_orientation_with_motion_trafo(boxes, fg_kabsch_trafos, bg_kabsch_trafo, no_align_for_displacement_below_m=0.1,
+                                                      full_align_for_displacement_above_m=0.3, check=True):
+    """reference :608-644, in place on `boxes` like the reference: a box that moves more than `no_align_for_displacement_below_m`
+    against its heading is turned by pi, every box is turned towards its direction of motion by the share of the angle that grows
+    linearly between the two displacements, and `velo` becomes (displacement, 0, 0).  The heading comes out as float64 (float32 rot
+    + float64 ratio * angle).  `check=False` (extension): see extract_box_motion_transform_without_sensor_odometry."""
+    assert no_align_for_displacement_below_m < full_align_for_displacement_above_m, (no_align_for_displacement_below_m,
+                                                                                     full_align_for_displacement_above_m)
+    box_translation, _ = extract_motion_in_pred_box_coordinates(boxes, fg_kabsch_trafos, bg_kabsch_trafo, check=check)
+    box_displacement_m = torch.linalg.norm(box_translation[..., :2], dim=-1)
+    box_needs_flip = (box_translation[..., 0] < 0.0) & (box_displacement_m > no_align_for_displacement_below_m)
+    box_translation[..., :2] = torch.where(box_needs_flip[..., None], -box_translation[..., :2], box_translation[..., :2])
+    assert boxes.rot.shape[-1] == 1, boxes.rot.shape
+    boxes.rot = torch.where(box_needs_flip[..., None], boxes.rot + np.pi, boxes.rot)
+    alignment_ratio = (box_displacement_m - no_align_for_displacement_below_m) / (full_align_for_displacement_above_m
+                                                                                  - no_align_for_displacement_below_m)
+    alignment_ratio = torch.clip(alignment_ratio, min=0.0, max=1.0)[..., None]
+    boxes.rot = boxes.rot + alignment_ratio * torch.atan2(box_translation[..., [1]], box_translation[..., [0]])
+    box_velo = torch.zeros_like(box_translation)
+    box_velo[..., 0] = box_displacement_m
+    boxes.velo = box_velo
+    return boxes
