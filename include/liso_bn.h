@@ -59,6 +59,40 @@ int liso_bn_relu_bwd_chained(const void* dy, long dy_stride, const void* x, long
                              const float* stats, int training, int relu, void* dx, long dx_stride, float* grad_gamma, float* grad_beta,
                              void* workspace, size_t workspace_bytes, const liso_wgrad_reduce_job* job, void* stream);
 
+/* ---- grouped backward with one or two upstream gradients --------------------------------------------------------------------
+ * One raw channels-last tensor x (rows of x_stride elements) carries up to LISO_BN_MAX_GROUPS BatchNorms over ascending, disjoint
+ * channel ranges [c_off, c_off + c), c <= 256, c_off on a 16-byte boundary (the deblocks' 3 x 128-channel concatenation), and receives
+ * one or two gradients dy_a / dy_b (dy_b == NULL: one) -- a map with two consumers, each handing back dL/d(relu(bn(x))) for its own
+ * use of it.  x, dy_a, dy_b and dx address channel 0 of their rows, each with its own row stride.  The call is three launches:
+ *   reduce    grid (row blocks, groups): per (group, gradient) the geometry, row order and LDS summation order of
+ *             liso_bn_relu_bwd_strided on that group's channels alone -> the same partial sums, bit for bit; x and the ReLU mask are
+ *             read once per row for both gradients.
+ *   finalize  one block per channel segment of every group (the segments and merge order of the single call), both gradients in turn;
+ *             the parameter gradients written are fl(fl(sum_a) + fl(sum_b)) -- what adding the second single call's result onto the
+ *             first one's gives in fp32 -- and the dx coefficients stay per gradient.  Behind these blocks ride the slab reductions of
+ *             up to two deferred weight gradients (job_a / job_b, NULL: none), as in liso_bn_relu_bwd_chained.
+ *   dx        per element dx_a and dx_b as the single calls compute them, each rounded to the element type, then
+ *             round(float(dx_a) + float(dx_b)): the elementwise sum of the two stored maps.  One gradient: dx_a.
+ * No atomics, no flags between blocks; every group's grad_gamma / grad_beta [c] fp32 are overwritten.  `training` / `relu` hold for
+ * all groups of the call. */
+#define LISO_BN_MAX_GROUPS 4
+typedef struct liso_bn_group {
+    int c_off, c;
+    const float* gamma;
+    const float* stats; /* [4 * c] = scale | shift | mean | invstd of this group */
+    float* grad_gamma;
+    float* grad_beta;
+} liso_bn_group;
+size_t liso_bn_multi_workspace_bytes(const liso_bn_group* groups, int n_groups, int n_grads);
+int liso_bn_relu_bwd_multi(const void* dy_a, long dy_a_stride, const void* dy_b, long dy_b_stride, const void* x, long x_stride, int elem,
+                           long m, const liso_bn_group* groups, int n_groups, int training, int relu, void* dx, long dx_stride,
+                           void* workspace, size_t workspace_bytes, const liso_wgrad_reduce_job* job_a, const liso_wgrad_reduce_job* job_b,
+                           void* stream);
+/* host only: LISO_OK where liso_bn_relu_bwd_multi accepts this table and these strides (-> the finalize launch's segment blocks),
+ * LISO_EINVAL otherwise (more than 4 groups, a group wider than 256 channels, overlapping or unaligned ranges, a range past a row) */
+int liso_bn_relu_bwd_multi_check(const liso_bn_group* groups, int n_groups, int n_grads, int elem, long m, long x_stride,
+                                 long dy_a_stride, long dy_b_stride, long dx_stride, int* n_finalize_blocks);
+
 /* ---- InstanceNorm2d(+ReLU), training: the same passes with one set of statistics per sample ---------------------------------
  * Replaces `nn.InstanceNorm2d(affine=True)` + `ReLU` of the SLIM encoders in training (liso/slim/model/extractor.py:24-38,
  * 219-230; norm_fn "instance" / "instance_affine"), which PyTorch runs through the BatchNorm kernels on a [1, B*C, H, W] view

@@ -213,6 +213,14 @@ int liso_conv_wgrad_reduce(const liso_wgrad_reduce_job* job, void* stream);
 int liso_conv_bn_finalize(const float* stats_partial, int rows, int co, int co_pad, long n, const float* stats_shift,
                           const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
                           float eps, float* stats, void* stream);
+/* The same launch, which also writes the four values of every channel into `merged` (NULL: exactly liso_conv_bn_finalize): fp32
+ * [4 * merged_c] = scale | shift | mean | invstd over ALL channels of a concatenation of separately normalised maps, this BatchNorm's
+ * channels starting at `merged_off` -- the values are in registers; a consumer of the concatenation (its prologue, its BatchNorm
+ * backward) reads one buffer instead of concatenating the groups' vectors.  `merged_gamma` (NULL: not wanted): fp32 [merged_c], receives
+ * gamma at the same offset, the concatenated gammas such a backward multiplies by. */
+int liso_conv_bn_finalize_merged(const float* stats_partial, int rows, int co, int co_pad, long n, const float* stats_shift,
+                                 const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
+                                 float eps, float* stats, float* merged, float* merged_gamma, int merged_c, int merged_off, void* stream);
 
 /* InstanceNorm2d statistics from the partial sums of a forward launch of a one-class (gather) descriptor, whose rows are ordered
  * sample-major: per sample b and channel c over the ho * wo pixels of that sample

@@ -257,6 +257,10 @@ SIGNATURES = {
     "liso_bn_relu_bwd": (_i, [_vp, _vp, _i, ctypes.c_long, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_bn_relu_bwd_strided": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _vp, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp, _vp, _sz, _vp]),
     "liso_bn_relu_bwd_chained": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _i, ctypes.c_long, _i, _vp, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "liso_bn_multi_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "liso_bn_relu_bwd_multi": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _i, ctypes.c_long, _vp, _i, _i, _i, _vp, ctypes.c_long,
+                                    _vp, _sz, _vp, _vp, _vp]),
+    "liso_bn_relu_bwd_multi_check": (_i, [_vp, _i, _i, _i, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_long, _vp]),
     "liso_knn_workspace_bytes": (_sz, [_vp, _i]),
     "liso_knn_build_f32": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
     "liso_knn_sorted_ids": (_i, [_vp, _vp, _i, _vp, _vp]),
@@ -287,6 +291,7 @@ SIGNATURES = {
     "liso_sparse_stem_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "liso_sparse_stem_forward_f32": (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_conv_bn_finalize": (_i, [_vp, _i, _i, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp]),
+    "liso_conv_bn_finalize_merged": (_i, [_vp, _i, _i, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _i, _vp]),
     # include/liso_tracking.h
     "liso_points_in_boxes_workspace_bytes": (_sz, [_vp]),
     "liso_points_in_boxes_f32": (_i, [_vp] * 9 + [_sz, _vp]),
@@ -408,6 +413,14 @@ class WgradReduceJob(ctypes.Structure):
     """mirror of liso_wgrad_reduce_job (include/liso_conv.h)"""
     _fields_ = [("slab", _vp), ("bias_slab", _vp), ("dw", _vp), ("dbias", _vp), ("cip", ctypes.c_long), ("cop", ctypes.c_long),
                 ("splits", _i), ("bias_rows", _i), ("taps", _i), ("ci", _i), ("co", _i), ("transposed", _i)]
+
+
+BN_MAX_GROUPS = 4  # include/liso_bn.h: LISO_BN_MAX_GROUPS
+
+
+class BnGroup(ctypes.Structure):
+    """mirror of liso_bn_group (include/liso_bn.h)"""
+    _fields_ = [("c_off", _i), ("c", _i), ("gamma", _vp), ("stats", _vp), ("grad_gamma", _vp), ("grad_beta", _vp)]
 
 
 class KnnGrid(ctypes.Structure):

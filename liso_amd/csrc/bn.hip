@@ -421,6 +421,176 @@ inline int stream_grid(long m, const Geom& g) {
     return (int)(nb < 8192 ? (nb > 0 ? nb : 1) : 8192);
 }
 
+// ---- grouped backward with one or two upstream gradients (include/liso_bn.h: liso_bn_relu_bwd_multi) -----------------------------
+// Up to four BatchNorms over channel ranges of ONE raw tensor, and up to two gradients arriving at it (a map with two consumers), in the
+// three launches of a single call.  Every (group, gradient) pair keeps the geometry, the per-thread row order and the LDS summation
+// order of bn_bwd_reduce_kernel / bn_bwd_finalize_segment on that group's channels alone, so its sums are the bits of the separate
+// call; x and the ReLU mask are read once per row for both gradients.
+struct MultiGroup {
+    int c_off, c;          // channel range inside a row of x / dy / dx
+    int cg, rl;            // Geom of this group's channel count
+    int cw, seg0;          // finalize: channels per segment, first block of this group's segments
+    const float* gamma;
+    const float* stats;
+    float *grad_gamma, *grad_beta;
+    float* partial[2];     // per gradient: [nblk][2 * c]
+    float* coef[2];        // per gradient: [3 * c]
+    float* pgrad[2];       // two gradients: this gradient's grad_gamma | grad_beta [2 * c], added by the block that wrote both
+};
+struct MultiArgs {
+    MultiGroup g[LISO_BN_MAX_GROUPS];
+    int n_groups, nblk, training;
+    long m, rows_per_block;
+    long xs, gs[2], ds;
+};
+
+// the value a store of T keeps, widened back (fp32: the value itself, made opaque so that the product in front of it is rounded
+// before the sum of the two gradients' dx is formed -- never a fused multiply-add of one into the other)
+template <typename T> __device__ __forceinline__ float stored(float v);
+template <> __device__ __forceinline__ float stored<float>(float v) { asm volatile("" : "+v"(v)); return v; }
+template <> __device__ __forceinline__ float stored<__hip_bfloat16>(float v) { return __bfloat162float(__float2bfloat16(v)); }
+template <> __device__ __forceinline__ float stored<_Float16>(float v) { return liso_e16::F16::round(v); }
+
+template <typename T, bool RELU, int NG>
+__global__ __launch_bounds__(kThreads) void bn_bwd_multi_reduce_kernel(const T* __restrict__ dy_a, const T* __restrict__ dy_b,
+                                                                       const T* __restrict__ x, MultiArgs A) {
+    constexpr int V = Vec<T>::V;
+    __shared__ float s_a[kThreads][V + 1];
+    __shared__ float s_b[kThreads][V + 1];
+    const MultiGroup& G = A.g[blockIdx.y];
+    const int c = G.c, cg = G.cg, rl = G.rl;
+    const float* __restrict__ stats = G.stats;
+    const long m = A.m, xs = A.xs;
+    const T* dy[2] = {dy_a + G.c_off, NG == 2 ? dy_b + G.c_off : nullptr};
+    x += G.c_off;
+    const int tid = threadIdx.x;
+    const int col = tid % cg, rlane = tid / cg;
+    float sc[V], sh[V], mu[V], is[V], a[NG][V], b[NG][V];
+#pragma unroll
+    for (int j = 0; j < V; j++) {
+        sc[j] = stats[col * V + j]; sh[j] = stats[c + col * V + j];
+        mu[j] = stats[2 * c + col * V + j]; is[j] = stats[3 * c + col * V + j];
+#pragma unroll
+        for (int n = 0; n < NG; n++) { a[n][j] = 0.f; b[n][j] = 0.f; }
+    }
+    const long r0 = (long)blockIdx.x * A.rows_per_block;
+    const long r1 = r0 + A.rows_per_block < m ? r0 + A.rows_per_block : m;
+#pragma unroll 4
+    for (long r = rlane < rl ? r0 + rlane : r1; r < r1; r += rl) {
+        float vx[V], vg[NG][V];
+        Vec<T>::load(x + r * xs + col * V, vx);
+#pragma unroll
+        for (int n = 0; n < NG; n++) Vec<T>::load(dy[n] + r * A.gs[n] + col * V, vg[n]);
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+            const bool off = RELU && !(fmaf(vx[j], sc[j], sh[j]) > 0.f);  // ReLU mask recomputed from x, once for both gradients
+            const float xh = (vx[j] - mu[j]) * is[j];
+#pragma unroll
+            for (int n = 0; n < NG; n++) {
+                const float dz = off ? 0.f : vg[n][j];
+                a[n][j] += dz;
+                b[n][j] = fmaf(dz, xh, b[n][j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int n = 0; n < NG; n++) {
+        if (n) __syncthreads();  // (the previous gradient's reads of s_a / s_b)
+#pragma unroll
+        for (int j = 0; j < V; j++) { s_a[tid][j] = a[n][j]; s_b[tid][j] = b[n][j]; }
+        __syncthreads();
+        if (tid < c) {
+            const int col2 = tid / V, j2 = tid % V;
+            float sa = 0.f, sb = 0.f;
+            for (int q = 0; q < rl; q++) { sa += s_a[q * cg + col2][j2]; sb += s_b[q * cg + col2][j2]; }
+            float* p = G.partial[n] + (size_t)blockIdx.x * 2 * c;
+            p[tid] = sa;
+            p[c + tid] = sb;
+        }
+    }
+}
+
+// blocks [0, n_fin): one channel segment of one group each -- bn_bwd_finalize_segment per gradient; with two gradients each writes its
+// parameter gradients to scratch and the thread that wrote both adds them (fp32: what autograd's add of the second contribution onto
+// the first gives).  Behind them the blocks of up to two riding weight-gradient slab reductions, as in bn_bwd_finalize_reduce_kernel.
+template <int NG>
+__global__ __launch_bounds__(1024) void bn_bwd_multi_finalize_kernel(MultiArgs A, int n_fin, liso_wgrad_reduce_job j0, long n_red0,
+                                                                     liso_wgrad_reduce_job j1, long n_red1) {
+    __shared__ double sh[2048];
+    if ((int)blockIdx.x < n_fin) {
+        int k = 0;
+        while (k + 1 < A.n_groups && (int)blockIdx.x >= A.g[k + 1].seg0) k++;
+        const MultiGroup& G = A.g[k];
+        const int seg = (int)blockIdx.x - G.seg0;
+#pragma unroll
+        for (int n = 0; n < NG; n++) {
+            if (n) __syncthreads();  // (the previous gradient's reads of sh)
+            const liso_chain::BnBwdFinalizeArgs f{G.partial[n], A.nblk, A.m, G.c, G.cw, G.gamma, G.stats, A.training,
+                                                  NG == 2 ? G.pgrad[n] : G.grad_gamma, NG == 2 ? G.pgrad[n] + G.c : G.grad_beta, G.coef[n]};
+            liso_chain::bn_bwd_finalize_segment(f, 0, seg, sh, sh + 1024);
+        }
+        if (NG == 2 && (int)threadIdx.x < G.cw) {  // (this thread's own stores above)
+            const int ch = seg * G.cw + threadIdx.x;
+            G.grad_gamma[ch] = G.pgrad[0][ch] + G.pgrad[1][ch];
+            G.grad_beta[ch] = G.pgrad[0][G.c + ch] + G.pgrad[1][G.c + ch];
+        }
+        return;
+    }
+    const int quarter = threadIdx.x >> 8;
+    long bid = (long)(blockIdx.x - n_fin) * 4 + quarter;
+    float4(*red)[16] = reinterpret_cast<float4(*)[16]>(sh) + quarter * 16;
+    const long wg0 = (n_red0 + 3) / 4 * 4;  // (job 0's workgroups are whole: a workgroup serves one job, its barriers stay uniform)
+    if (bid < wg0) {
+        if (j0.splits > 16) liso_chain::wgrad_reduce_block<16>(j0, bid, threadIdx.x & 255, red, bid < n_red0);
+        else liso_chain::wgrad_reduce_block<1>(j0, bid, threadIdx.x & 255, red, bid < n_red0);
+    } else {
+        bid -= wg0;
+        if (j1.splits > 16) liso_chain::wgrad_reduce_block<16>(j1, bid, threadIdx.x & 255, red, bid < n_red1);
+        else liso_chain::wgrad_reduce_block<1>(j1, bid, threadIdx.x & 255, red, bid < n_red1);
+    }
+}
+
+template <typename T, bool RELU, int NG>
+__global__ __launch_bounds__(kThreads) void bn_bwd_multi_dx_kernel(const T* __restrict__ dy_a, const T* __restrict__ dy_b,
+                                                                   const T* __restrict__ x, MultiArgs A, T* __restrict__ dx) {
+    constexpr int V = Vec<T>::V;
+    const MultiGroup& G = A.g[blockIdx.y];
+    const int c = G.c, cg = G.cg, rl = G.rl;
+    const float* __restrict__ stats = G.stats;
+    const long m = A.m, xs = A.xs, ds = A.ds;
+    const T* dy[2] = {dy_a + G.c_off, NG == 2 ? dy_b + G.c_off : nullptr};
+    x += G.c_off; dx += G.c_off;
+    const int col = threadIdx.x % cg, rlane = threadIdx.x / cg;
+    float sc[V], sh[V], mu[V], is[V], Ac[NG][V], Bc[NG][V], Cc[NG][V];
+#pragma unroll
+    for (int j = 0; j < V; j++) {
+        const int ch = col * V + j;
+        sc[j] = stats[ch]; sh[j] = stats[c + ch]; mu[j] = stats[2 * c + ch]; is[j] = stats[3 * c + ch];
+#pragma unroll
+        for (int n = 0; n < NG; n++) { Ac[n][j] = G.coef[n][ch]; Bc[n][j] = G.coef[n][c + ch]; Cc[n][j] = G.coef[n][2 * c + ch]; }
+    }
+    const long stride = (long)gridDim.x * rl;
+    for (long r = rlane < rl ? (long)blockIdx.x * rl + rlane : m; r < m; r += stride) {
+        float vx[V], vg[NG][V];
+        Vec<T>::load(x + r * xs + col * V, vx);
+#pragma unroll
+        for (int n = 0; n < NG; n++) Vec<T>::load(dy[n] + r * A.gs[n] + col * V, vg[n]);
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+            const bool off = RELU && !(fmaf(vx[j], sc[j], sh[j]) > 0.f);
+#pragma unroll
+            for (int n = 0; n < NG; n++) {
+                const float dz = off ? 0.f : vg[n][j];
+                vg[n][j] = Ac[n][j] * (dz - Bc[n][j] - (vx[j] - mu[j]) * is[j] * Cc[n][j]);
+            }
+            // two gradients: each dx rounded to T as its own store would, then their sum rounded once more (the elementwise add of the
+            // two stored maps)
+            if (NG == 2) vg[0][j] = stored<T>(vg[0][j]) + stored<T>(vg[1][j]);
+        }
+        Vec<T>::store(dx + r * ds + col * V, vg[0]);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -529,6 +699,113 @@ int liso_bn_relu_bwd_chained(const void* dy, long dy_stride, const void* x, long
     if (job && !liso_chain::wgrad_reduce_job_ok(job)) return LISO_EINVAL;
     return bn_relu_bwd(dy, x, is_bf16, m, c, gamma, stats, training, relu, dx, grad_gamma, grad_beta, workspace, workspace_bytes,
                        stream, dy_stride, x_stride, dx_stride, job);
+}
+
+// floats of workspace per (group, gradient): partial sums | dx coefficients | this gradient's parameter gradients
+static inline size_t multi_pair_floats(int c) { return (size_t)kMaxBlocks * 2 * c + 5 * (size_t)c; }
+
+size_t liso_bn_multi_workspace_bytes(const liso_bn_group* groups, int n_groups, int n_grads) {
+    if (!groups || n_groups < 1 || n_groups > LISO_BN_MAX_GROUPS || n_grads < 1 || n_grads > 2) return 0;
+    size_t n = 0;
+    for (int k = 0; k < n_groups; k++) {
+        if (groups[k].c <= 0 || groups[k].c > kThreads) return 0;
+        n += (size_t)n_grads * multi_pair_floats(groups[k].c);
+    }
+    return n * sizeof(float);
+}
+
+// the table of a grouped call: geometry per group, finalize segments in group order.  Host only; liso_bn_relu_bwd_multi_check exposes
+// its refusals.
+static int multi_table(const liso_bn_group* groups, int n_groups, int n_grads, int elem, long m, long x_stride, long dy_a_stride,
+                       long dy_b_stride, long dx_stride, MultiArgs* A, int* n_fin, int* grid_dx) {
+    if (!elem_ok(elem) || m <= 0 || !groups || n_groups < 1 || n_groups > LISO_BN_MAX_GROUPS || n_grads < 1 || n_grads > 2)
+        return LISO_EINVAL;
+    const int v = elem ? 8 : 4;
+    const long strides[4] = {x_stride, dy_a_stride, dx_stride, n_grads == 2 ? dy_b_stride : dy_a_stride};
+    for (long s : strides)
+        if (s <= 0 || s % v) return LISO_EINVAL;
+    int seg = 0, gdx = 1, end = 0;
+    for (int k = 0; k < n_groups; k++) {
+        const liso_bn_group& g = groups[k];
+        Geom ge;
+        int nblk;
+        if (!geom(g.c, v, m, &ge, &nblk)) return LISO_EINVAL;  // (c <= 256, whole 16-B lanes)
+        if (g.c_off < end || g.c_off % v) return LISO_EINVAL;   // ascending, disjoint channel ranges on 16-B boundaries
+        end = g.c_off + g.c;
+        for (long s : strides)
+            if (end > s) return LISO_EINVAL;
+        if (!g.gamma || !g.stats || !g.grad_gamma || !g.grad_beta) return LISO_EINVAL;
+        MultiGroup& G = A->g[k];
+        G.c_off = g.c_off; G.c = g.c; G.cg = ge.cg; G.rl = ge.rl;
+        G.cw = finalize_segment(g.c, nblk); G.seg0 = seg;
+        G.gamma = g.gamma; G.stats = g.stats; G.grad_gamma = g.grad_gamma; G.grad_beta = g.grad_beta;
+        seg += g.c / G.cw;
+        const int sg = stream_grid(m, ge);
+        if (sg > gdx) gdx = sg;
+        A->nblk = nblk; A->rows_per_block = ge.rows_per_block;  // (functions of m alone: the same for every group)
+    }
+    A->n_groups = n_groups; A->m = m;
+    A->xs = x_stride; A->gs[0] = dy_a_stride; A->gs[1] = n_grads == 2 ? dy_b_stride : 0; A->ds = dx_stride;
+    *n_fin = seg; *grid_dx = gdx;
+    return LISO_OK;
+}
+
+int liso_bn_relu_bwd_multi_check(const liso_bn_group* groups, int n_groups, int n_grads, int elem, long m, long x_stride,
+                                 long dy_a_stride, long dy_b_stride, long dx_stride, int* n_finalize_blocks) {
+    MultiArgs A{};
+    int n_fin = 0, gdx = 0;
+    const int rc = multi_table(groups, n_groups, n_grads, elem, m, x_stride, dy_a_stride, dy_b_stride, dx_stride, &A, &n_fin, &gdx);
+    if (rc == LISO_OK && n_finalize_blocks) *n_finalize_blocks = n_fin;
+    return rc;
+}
+
+int liso_bn_relu_bwd_multi(const void* dy_a, long dy_a_stride, const void* dy_b, long dy_b_stride, const void* x, long x_stride, int elem,
+                           long m, const liso_bn_group* groups, int n_groups, int training, int relu, void* dx, long dx_stride,
+                           void* workspace, size_t workspace_bytes, const liso_wgrad_reduce_job* job_a, const liso_wgrad_reduce_job* job_b,
+                           void* stream) {
+    const int ng = dy_b ? 2 : 1;
+    MultiArgs A{};
+    int n_fin = 0, gdx = 0;
+    const int rc = multi_table(groups, n_groups, ng, elem, m, x_stride, dy_a_stride, dy_b_stride, dx_stride, &A, &n_fin, &gdx);
+    if (rc != LISO_OK) return rc;
+    if (!dy_a || !x || !dx || !workspace) return LISO_EINVAL;
+    if ((((uintptr_t)dy_a | (uintptr_t)dy_b | (uintptr_t)x | (uintptr_t)dx) & 15) != 0) return LISO_EINVAL;
+    if (!job_a && job_b) { job_a = job_b; job_b = nullptr; }
+    if ((job_a && !liso_chain::wgrad_reduce_job_ok(job_a)) || (job_b && !liso_chain::wgrad_reduce_job_ok(job_b))) return LISO_EINVAL;
+    if (workspace_bytes < liso_bn_multi_workspace_bytes(groups, n_groups, ng)) return LISO_EWORKSPACE;
+    float* w = (float*)workspace;
+    for (int k = 0; k < n_groups; k++)
+        for (int n = 0; n < ng; n++) {
+            MultiGroup& G = A.g[k];
+            G.partial[n] = w;
+            G.coef[n] = w + (size_t)kMaxBlocks * 2 * G.c;
+            G.pgrad[n] = G.coef[n] + 3 * (size_t)G.c;
+            w += multi_pair_floats(G.c);
+        }
+    A.training = training;
+    hipStream_t st = (hipStream_t)stream;
+    const liso_wgrad_reduce_job none{};
+    const long n_red0 = job_a ? liso_chain::wgrad_reduce_blocks(*job_a) : 0, n_red1 = job_b ? liso_chain::wgrad_reduce_blocks(*job_b) : 0;
+    const unsigned grid_f = (unsigned)(n_fin + (n_red0 + 3) / 4 + (n_red1 + 3) / 4);
+    const dim3 grid_r((unsigned)A.nblk, (unsigned)n_groups), grid_d((unsigned)gdx, (unsigned)n_groups);
+#define LISO_BWD(T, R, N)                                                                                                            \
+    do {                                                                                                                             \
+        bn_bwd_multi_reduce_kernel<T, R, N><<<grid_r, kThreads, 0, st>>>((const T*)dy_a, (const T*)dy_b, (const T*)x, A);            \
+        bn_bwd_multi_finalize_kernel<N><<<grid_f, 1024, 0, st>>>(A, n_fin, job_a ? *job_a : none, n_red0, job_b ? *job_b : none,     \
+                                                                 n_red1);                                                            \
+        bn_bwd_multi_dx_kernel<T, R, N><<<grid_d, kThreads, 0, st>>>((const T*)dy_a, (const T*)dy_b, (const T*)x, A, (T*)dx);        \
+    } while (0)
+#define LISO_BWD_T(T)                                                                                                                \
+    do {                                                                                                                             \
+        if (relu) { if (ng == 2) LISO_BWD(T, true, 2); else LISO_BWD(T, true, 1); }                                                  \
+        else { if (ng == 2) LISO_BWD(T, false, 2); else LISO_BWD(T, false, 1); }                                                     \
+    } while (0)
+    if (elem == LISO_ELEM_F16) LISO_BWD_T(_Float16);
+    else if (elem) LISO_BWD_T(__hip_bfloat16);
+    else LISO_BWD_T(float);
+#undef LISO_BWD_T
+#undef LISO_BWD
+    return check_launch();
 }
 
 size_t liso_in_workspace_bytes(int groups, int c) {

@@ -1587,7 +1587,9 @@ __global__ __launch_bounds__(1024) void conv_bn_finalize_kernel(const float* __r
                                                                 long n, const float* __restrict__ stats_shift,
                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                 float* __restrict__ running_mean, float* __restrict__ running_var,
-                                                                float momentum, float eps, float* __restrict__ stats) {
+                                                                float momentum, float eps, float* __restrict__ stats,
+                                                                float* __restrict__ merged, float* __restrict__ merged_gamma, int merged_c,
+                                                                int merged_off) {
     // 8 channels per block; 64 row groups walk the per-block partial sums (1024-2048 rows of 8 B at a 512-B stride: latency-bound --
     // with 16 groups the kernel took 7-11 us, a fifth of the convolution in front of it), fp64 merge in a fixed order
     __shared__ double red[kFinGroups][16];
@@ -1650,6 +1652,13 @@ __global__ __launch_bounds__(1024) void conv_bn_finalize_kernel(const float* __r
             stats[co + cc] = (float)((beta ? (double)beta[cc] : 0.0) - mean * sc);
             stats[2 * co + cc] = (float)mean;
             stats[3 * co + cc] = (float)invstd;
+            if (merged) {  // the same four values at this BatchNorm's place in the statistics of a channel concatenation
+                merged[merged_off + cc] = (float)sc;
+                merged[merged_c + merged_off + cc] = (float)((beta ? (double)beta[cc] : 0.0) - mean * sc);
+                merged[2 * merged_c + merged_off + cc] = (float)mean;
+                merged[3 * merged_c + merged_off + cc] = (float)invstd;
+                if (merged_gamma) merged_gamma[merged_off + cc] = gamma ? gamma[cc] : 1.0f;
+            }
             if (running_mean) {
                 const double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
                 running_mean[cc] = (float)((1.0 - momentum) * running_mean[cc] + momentum * mean);
@@ -1969,7 +1978,20 @@ int liso_conv_bn_finalize(const float* stats_partial, int rows, int co, int co_p
     if (!stats_partial || !gamma || !beta || !stats || rows <= 0 || co <= 0 || co_pad < co || n <= 0) return LISO_EINVAL;
     if ((running_mean == nullptr) != (running_var == nullptr)) return LISO_EINVAL;
     conv_bn_finalize_kernel<<<(co + 7) / 8, 1024, 0, (hipStream_t)stream>>>(stats_partial, rows, co, co_pad, n, stats_shift, gamma,
-                                                                          beta, running_mean, running_var, momentum, eps, stats);
+                                                                          beta, running_mean, running_var, momentum, eps, stats,
+                                                                          nullptr, nullptr, 0, 0);
+    return check_launch();
+}
+
+int liso_conv_bn_finalize_merged(const float* stats_partial, int rows, int co, int co_pad, long n, const float* stats_shift,
+                                 const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
+                                 float eps, float* stats, float* merged, float* merged_gamma, int merged_c, int merged_off, void* stream) {
+    if (!stats_partial || !gamma || !beta || !stats || rows <= 0 || co <= 0 || co_pad < co || n <= 0) return LISO_EINVAL;
+    if ((running_mean == nullptr) != (running_var == nullptr)) return LISO_EINVAL;
+    if ((merged && (merged_off < 0 || merged_c < merged_off + co)) || (merged_gamma && !merged)) return LISO_EINVAL;
+    conv_bn_finalize_kernel<<<(co + 7) / 8, 1024, 0, (hipStream_t)stream>>>(stats_partial, rows, co, co_pad, n, stats_shift, gamma,
+                                                                          beta, running_mean, running_var, momentum, eps, stats,
+                                                                          merged, merged_gamma, merged_c, merged_off);
     return check_launch();
 }
 
@@ -1979,7 +2001,7 @@ int liso_conv_in_finalize(const float* stats_partial, int rows_per_sample, int b
     if ((gamma == nullptr) != (beta == nullptr)) return LISO_EINVAL;
     conv_bn_finalize_kernel<<<dim3((co + 7) / 8, batch), 1024, 0, (hipStream_t)stream>>>(stats_partial, rows_per_sample, co, co_pad,
                                                                                      n_per_sample, nullptr, gamma, beta, nullptr,
-                                                                                     nullptr, 0.0f, eps, stats);
+                                                                                     nullptr, 0.0f, eps, stats, nullptr, nullptr, 0, 0);
     return check_launch();
 }
 

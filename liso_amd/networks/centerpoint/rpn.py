@@ -124,10 +124,17 @@ class RPN(nn.Module):
             for j in range(4, len(mods), 3):
                 x, fold = MC.fused_conv(x, fold, mods[j], out_bn=mods[j + 1])
             cut = getattr(self, "grad_cut", None)
+            x_tap = x
             if cut is not None and i == 0:  # (extension) behind block 0, in front of its two consumers: see mfma_conv.GradCut
-                x = cut.split(x)
+                x_tap = x = cut.split(x)
+            elif i - self._upsample_start_idx >= 0 and i + 1 < len(self.blocks):
+                # two consumers (the next block and this block's deblock): the pending BatchNorm's backward runs once, on both of
+                # their gradients (mfma_conv.shared_fold), not once per consumer
+                shared = MC.shared_fold(x, fold, 2)
+                if shared is not None:
+                    (x, x_tap), fold = shared
             if i - self._upsample_start_idx >= 0:
-                taps.append((x, fold, self.deblocks[i - self._upsample_start_idx]))
+                taps.append((x_tap, fold, self.deblocks[i - self._upsample_start_idx]))
         if len(taps) == 0:
             return x, fold
         if len(taps) == 1:
@@ -143,12 +150,19 @@ class RPN(nn.Module):
         if len(set(sizes)) == 1 and all(c % 8 == 0 for c in chans) and sum(chans) % vec == 0:
             (ho, wo), B = sizes[0], x.shape[0]
             buf = torch.empty((B, ho, wo, sum(chans)), dtype=x.dtype, device=x.device)
+            # (and their finalize launches write the statistics of the concatenation next to their own: see BnFold.use_merged)
+            merged = torch.empty(5 * sum(chans), dtype=torch.float32, device=x.device) if MC.merged_stats_wanted(taps) else None
             off = 0
             for (xi, fi, d), c in zip(taps, chans):
-                ups.append(MC.fused_conv(xi, fi, d[0], out_bn=d[1], out=(buf, off)))
+                ups.append(MC.fused_conv(xi, fi, d[0], out_bn=d[1], out=(buf, off),
+                                         merged_stats=(merged, sum(chans), off) if merged is not None else None))
                 off += c
             raw = MC.slice_cat(buf.permute(0, 3, 1, 2), [u[0] for u in ups])
         else:
+            merged = None
             ups = [MC.fused_conv(xi, fi, d[0], out_bn=d[1]) for xi, fi, d in taps]
             raw = torch.cat([u[0] for u in ups], dim=1)
-        return raw, MC.BnFold.cat([u[1] for u in ups])
+        fold = MC.BnFold.cat([u[1] for u in ups])
+        if merged is not None:
+            fold.use_merged(merged, sum(chans))
+        return raw, fold

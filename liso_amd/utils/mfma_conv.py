@@ -702,6 +702,8 @@ class BnFold:
     def __init__(self, groups, relu=True, training=True):
         self.groups, self.relu, self.training = list(groups), bool(relu), bool(training)
         self._ss = None
+        self.deferred = None  # (shared_fold: the node that runs this fold's backward for all consumers of the raw map)
+        self.merged = None  # (use_merged: (buffer, channels) of the groups' statistics and gammas laid out over all channels)
 
     @property
     def channels(self):
@@ -717,6 +719,13 @@ class BnFold:
                             torch.cat([g["stats"][g["gamma"].shape[0]:2 * g["gamma"].shape[0]] for g in self.groups]).contiguous())
         return self._ss
 
+    def use_merged(self, buf, total):
+        """`buf` fp32 [5 * total] = scale | shift | mean | invstd | gamma over all channels of the groups, which their finalize launches
+        wrote next to the groups' own statistics (finalize_bn(..., merged=)): nothing is concatenated, forward or backward"""
+        assert total == self.channels and buf.numel() == 5 * total
+        self.merged = (buf, total)
+        self._ss = (buf[:total], buf[total:2 * total])
+
     def group(self, k):
         return BnFold([self.groups[k]], self.relu, self.training)
 
@@ -729,10 +738,17 @@ class BnFold:
         return [t for g in self.groups for t in (g["gamma"], g["beta"])]
 
 
-def finalize_bn(stats_partial, n_pixels, bn, stats_shift=None, channel_offset=0):
+def merged_stats_wanted(taps):
+    """do the BatchNorms behind the convolutions of `taps` [(x, fold, (conv, bn)), ...] take batch statistics in finalize launches that
+    can write a merged buffer (training mode, the joint backward switched on)?"""
+    return _JOINT_BN_BACKWARD and all(d[1].training or not d[1].track_running_stats for _, _, d in taps)
+
+
+def finalize_bn(stats_partial, n_pixels, bn, stats_shift=None, channel_offset=0, merged=None):
     """per-block partial sums of a conv_forward(..., want_stats=True) -> BnFold of `bn` in training mode (batch statistics,
     running statistics updated with the module's momentum, like torch.nn.BatchNorm2d.forward).  `channel_offset`: first
-    channel of this BatchNorm inside the convolution's output (several BatchNorms behind one merged convolution)."""
+    channel of this BatchNorm inside the convolution's output (several BatchNorms behind one merged convolution).  `merged`:
+    (buffer fp32 [5 * total], total, offset) -- the launch also writes this BatchNorm's part of BnFold.use_merged's buffer."""
     C = bn.num_features
     stats = torch.empty(4 * C, dtype=torch.float32, device=stats_partial.device)
     rows, _, cop = stats_partial.shape
@@ -740,10 +756,15 @@ def finalize_bn(stats_partial, n_pixels, bn, stats_shift=None, channel_offset=0)
     track = bn.track_running_stats and bn.training
     part = ctypes.c_void_p(stats_partial.data_ptr() + 4 * channel_offset)
     with torch.cuda.device(stats_partial.device):
-        L.check(L.lib().liso_conv_bn_finalize(
-            part, rows, C, cop, int(n_pixels), L.ptr(stats_shift) if stats_shift is not None else None,
-            L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean) if track else None, L.ptr(bn.running_var) if track else None,
-            float(mom), float(bn.eps), L.ptr(stats), L.stream_ptr()), "conv_bn_finalize")
+        args = (part, rows, C, cop, int(n_pixels), L.ptr(stats_shift) if stats_shift is not None else None,
+                L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean) if track else None, L.ptr(bn.running_var) if track else None,
+                float(mom), float(bn.eps), L.ptr(stats))
+        if merged is not None:
+            buf, total, off = merged
+            L.check(L.lib().liso_conv_bn_finalize_merged(*args, L.ptr(buf), ctypes.c_void_p(buf.data_ptr() + 16 * total), total, off,
+                                                         L.stream_ptr()), "conv_bn_finalize_merged")
+        else:
+            L.check(L.lib().liso_conv_bn_finalize(*args, L.stream_ptr()), "conv_bn_finalize")
     return BnFold([{"stats": stats, "gamma": bn.weight, "beta": bn.bias}], True, True)
 
 
@@ -835,6 +856,132 @@ def _bn_backward_group(g, x_raw, grp, relu, training, out=None, job=None):
     return dxv.permute(0, 3, 1, 2), (None if direct else gg), (None if direct else gb)
 
 
+_JOINT_BN_BACKWARD = True
+
+
+def set_joint_bn_backward(on):
+    """on (default): a raw map with two consumers runs ONE BatchNorm backward on both gradients (`shared_fold`), and a fold of more
+    than 256 channels runs its groups in one grouped call (include/liso_bn.h: liso_bn_relu_bwd_multi); multi-group folds read their
+    concatenated statistics from the buffer the groups' finalize launches wrote (BnFold.use_merged).  off: one backward per consumer
+    and per group, their results added by autograd, statistics concatenated by torch.cat -- the form the joint one is tested against,
+    bit for bit -> the previous setting"""
+    global _JOINT_BN_BACKWARD
+    prev, _JOINT_BN_BACKWARD = _JOINT_BN_BACKWARD, bool(on)
+    return prev
+
+
+def bn_group_table(Cs, vec):
+    """channel offsets of a fold's groups in a grouped call -> [(c_off, c), ...], or None where the call does not take them: more than
+    four groups, a group wider than 256 channels or one that does not start and end on a 16-byte lane boundary"""
+    if not 1 <= len(Cs) <= L.BN_MAX_GROUPS:
+        return None
+    table, off = [], 0
+    for c in Cs:
+        if c <= 0 or c > 256 or c % vec:
+            return None
+        table.append((off, c))
+        off += c
+    return table
+
+
+def _bn_backward_multi(gs, x_raw, fold, jobs=()):
+    """gradient through relu?(bn(x_raw)) of ALL groups of `fold` given one or two gradients `gs` of its output (two consumers of one
+    raw map): ONE grouped call, three launches -> (dx_raw logical NCHW = the sum over the gradients, [dgamma0, dbeta0, ...]), or None
+    where a layout is not regular rows or the groups do not fit the call (the caller takes the per-group path).  `jobs`: up to two
+    WgradReduceJobs that ride in the finalize launch."""
+    vec = 8 if L.is_half(x_raw.dtype) else 4
+    Cs = [grp["gamma"].shape[0] for grp in fold.groups]
+    table = bn_group_table(Cs, vec)
+    xv, xs = _rows_view(x_raw, vec)
+    if table is None or xv is None or x_raw.shape[1] != sum(Cs) or not 1 <= len(gs) <= 2:
+        return None
+    views = []
+    for g in gs:
+        if g.dtype != xv.dtype:
+            g = g.to(xv.dtype)
+        gv, s = _rows_view(g, vec)
+        if gv is None or gv.shape != xv.shape:
+            return None
+        views.append((gv, s))
+    B, H, W, Ct = xv.shape
+    M = B * H * W
+    lib = L.lib()
+    dxv = torch.empty((B, H, W, Ct), dtype=xv.dtype, device=xv.device)
+    tab = (L.BnGroup * len(Cs))()
+    grads, keep = [], []
+    for k, (grp, (off, C)) in enumerate(zip(fold.groups, table)):
+        tg, tb = _direct_target(grp["gamma"]), _direct_target(grp["beta"])
+        direct = tg is not None and tb is not None
+        gg = tg if direct else torch.empty(C, dtype=torch.float32, device=xv.device)
+        gb = tb if direct else torch.empty(C, dtype=torch.float32, device=xv.device)
+        keep += [gg, gb]
+        tab[k].c_off, tab[k].c = off, C
+        tab[k].gamma, tab[k].stats, tab[k].grad_gamma, tab[k].grad_beta = (grp["gamma"].data_ptr(), grp["stats"].data_ptr(), gg.data_ptr(),
+                                                                            gb.data_ptr())
+        grads += [None if direct else gg, None if direct else gb]
+    nbytes = lib.liso_bn_multi_workspace_bytes(tab, len(Cs), len(views))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=xv.device)
+    riding = [j for j in jobs if j is not None and not j.done][:2]
+    (ga, gsa), (gb_, gsb) = views[0], (views[1] if len(views) == 2 else (None, 0))
+    units = (3 + 2 * len(views)) * M * Ct * xv.element_size()
+    with torch.cuda.device(xv.device):
+        L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd_multi(
+            L.ptr(ga), gsa, L.ptr(gb_) if gb_ is not None else None, gsb, L.ptr(xv), xs, L.elem_code(xv.dtype), M, tab, len(Cs),
+            int(fold.training), int(fold.relu), L.ptr(dxv), Ct, L.ptr(ws), nbytes, riding[0].ride() if len(riding) > 0 else None,
+            riding[1].ride() if len(riding) > 1 else None, L.stream_ptr()), units=units), "bn_relu_bwd_multi")
+    return dxv.permute(0, 3, 1, 2), grads
+
+
+class _SharedFold(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x_raw, node, n, *fold_params):
+        """node: dict(fold, jobs); `fold_params`: the fold's gamma / beta tensors, passed so that autograd routes their gradients"""
+        ctx.node, ctx.n, ctx.n_fold_params = node, n, len(fold_params)
+        ctx.save_for_backward(x_raw)
+        return tuple(torch.ops.aten.alias(x_raw) for _ in range(n))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        (x_raw,) = ctx.saved_tensors
+        fold, jobs = ctx.node["fold"], ctx.node["jobs"]
+        gs = [g for g in gs if g is not None]
+        try:
+            if not gs:
+                return (None, None, None) + (None,) * ctx.n_fold_params
+            res = _bn_backward_multi(gs, x_raw, fold, jobs) if len(gs) <= 2 else None
+            if res is None:  # (a layout the grouped call does not read in place: one backward per gradient, added)
+                dx, grads = None, [None] * ctx.n_fold_params
+                for g in gs:
+                    d, gr = _bn_backward(g, x_raw, fold, next((j for j in jobs if not j.done), None))
+                    dx = d if dx is None else dx + d
+                    grads = [b if a is None else (a if b is None else a + b) for a, b in zip(grads, gr)]
+                res = dx, grads
+        finally:
+            for j in jobs:
+                j.flush()  # (no finalize launch took it: the plain reduction)
+            jobs.clear()
+        return (res[0], None, None, *res[1])
+
+
+def shared_fold(x_raw, fold, n=2):
+    """A raw map with `n` consumers (a block's output feeding the next block and its deblock): -> ([n aliases of x_raw], the fold to hand
+    each consumer with its alias), no launch.  The BatchNorm(+ReLU) pending on x_raw is still applied in every consumer's prologue, but
+    its BACKWARD runs once, here, on the consumers' data gradients together (liso_bn_relu_bwd_multi: x_raw read once per pass, one dx
+    map written) instead of once per consumer with autograd adding the results; the consumers' deferred weight-gradient reductions ride
+    in its finalize launch.  None where the joint backward does not apply (switched off, no gradient wanted, an eval-mode fold, a layout
+    the kernels do not read in place): the caller hands x_raw and fold to every consumer as before."""
+    vec = 8 if L.is_half(x_raw.dtype) else 4
+    if (not _JOINT_BN_BACKWARD or fold is None or not fold.training or fold.deferred is not None or not torch.is_grad_enabled()
+            or not x_raw.requires_grad or not x_raw.is_cuda or _rows_view(x_raw, vec)[0] is None
+            or bn_group_table([g["gamma"].shape[0] for g in fold.groups], vec) is None):
+        return None
+    node = {"fold": fold, "jobs": []}
+    outs = _SharedFold.apply(x_raw, node, int(n), *fold.params())
+    held = BnFold(fold.groups, fold.relu, fold.training)
+    held._ss, held.merged, held.deferred = fold.scale_shift(), fold.merged, node
+    return list(outs), held
+
+
 def _bn_backward(g, x_raw, fold, job=None):
     """-> (dx_raw logical NCHW, [dgamma0, dbeta0, dgamma1, dbeta1, ...]); `job`: see _bn_backward_group (the first group's call takes it)"""
     if len(fold.groups) == 1:
@@ -847,7 +994,10 @@ def _bn_backward(g, x_raw, fold, job=None):
     Cs = [grp["gamma"].shape[0] for grp in fold.groups]
     if sum(Cs) > 256:  # (the BatchNorm kernels take up to 256 channels per call: e.g. the deblocks' 3 x 128-channel concatenation)
         # every group reads its channel slice of g / x_raw in place and writes its slice of ONE input-gradient tensor: no slice
-        # copies, no concatenation
+        # copies, no concatenation -- in one grouped call (three launches for all groups) where the layouts allow
+        res = _bn_backward_multi([g], x_raw, fold, [job]) if _JOINT_BN_BACKWARD else None
+        if res is not None:
+            return res
         B, _, H, W = x_raw.shape
         dx_full = torch.empty((B, H, W, sum(Cs)), dtype=x_raw.dtype, device=x_raw.device).permute(0, 3, 1, 2)
         grads, a = [], 0
@@ -859,8 +1009,12 @@ def _bn_backward(g, x_raw, fold, job=None):
             grads += [gg, gb]
             a += C
         return dx_full, grads
-    gam = torch.cat([grp["gamma"].detach() for grp in fold.groups])
-    stats = torch.cat([grp["stats"][k * c:(k + 1) * c] for k in range(4) for grp, c in zip(fold.groups, Cs)])  # scale | shift | mean | invstd
+    if fold.merged is not None:  # (written by the groups' finalize launches in the forward pass)
+        buf, total = fold.merged
+        gam, stats = buf[4 * total:], buf[:4 * total]
+    else:
+        gam = torch.cat([grp["gamma"].detach() for grp in fold.groups])
+        stats = torch.cat([grp["stats"][k * c:(k + 1) * c] for k in range(4) for grp, c in zip(fold.groups, Cs)])  # scale | shift | mean | invstd
     dx, gg, gb = _bn_backward_group(g, x_raw, {"gamma": gam, "beta": None, "stats": stats}, fold.relu, fold.training, job=job)
     grads, a = [], 0
     for c in Cs:
@@ -945,7 +1099,16 @@ class _FusedConv(torch.autograd.Function):
                     g = _sparse_dgrad(dy, ctx.meta["occupancy"], weight, spec, tuple(x_raw.shape), x_raw.dtype, lists=ctx.meta.get("sparse_ws"))
                 if g is None:
                     g = conv_dgrad(dy, weight, spec, tuple(x_raw.shape))
-                if fold is not None:
+                if fold is not None and fold.deferred is not None:
+                    # a shared fold: its backward runs once for all consumers, in the node in front of them (shared_fold), which
+                    # also takes over the slab reduction -- and with it the workspace the job keeps alive -- where the weight
+                    # gradient is written in place (a trainer's flat buffer: nothing reads it before that node has run).  A dw
+                    # handed back to autograd is accumulated as soon as this function returns: it is reduced here (`finally`).
+                    dx = g
+                    if job is not None and dw is None:
+                        fold.deferred["jobs"].append(job)
+                        job = None
+                elif fold is not None:
                     dx, fold_grads = _bn_backward(g, x_raw, fold, job)
                 else:
                     dx = g
@@ -959,12 +1122,13 @@ class _FusedConv(torch.autograd.Function):
         return (dx, dw, db, None, *fold_grads)
 
 
-def fused_conv(x_raw, fold, conv, out_bn=None, out_dtype=None, out_relu=False, spec=None, occupancy=None, out=None):
+def fused_conv(x_raw, fold, conv, out_bn=None, out_dtype=None, out_relu=False, spec=None, occupancy=None, out=None, merged_stats=None):
     """y_raw = conv(relu?(bn(x_raw))) (+ bias).  `fold`: BnFold pending on x_raw or None.  `conv`: one nn.Conv2d /
     nn.ConvTranspose2d, or a list of nn.Conv2d with the same geometry and input (run as ONE convolution with the filters
     concatenated along the output channels).  `out_bn`: the BatchNorm2d (list: one per convolution of the list) that follows
     -> returns (y_raw, BnFold) (training: batch statistics from the convolution's epilogue; eval: running statistics);
-    without it returns (y_raw, None)."""
+    without it returns (y_raw, None).  `merged_stats`: see finalize_bn's `merged` (a single `out_bn` whose map is one part of a channel
+    concatenation); several BatchNorms behind one merged convolution get a buffer of their own."""
     convs = list(conv) if isinstance(conv, (list, tuple)) else [conv]
     bns = (list(out_bn) if isinstance(out_bn, (list, tuple)) else [out_bn]) if out_bn is not None else None
     spec = spec or ConvSpec.of(convs[0])
@@ -995,7 +1159,7 @@ def fused_conv(x_raw, fold, conv, out_bn=None, out_dtype=None, out_relu=False, s
         # any per-channel constant close to the mean keeps the sums well conditioned: the running mean.  (The finalize kernel
         # reads stats_shift[c] before the same thread updates running_mean[c]: passing the live buffer is safe.)
         meta["stats_shift"] = bns[0].running_mean
-    params = fold.params() if fold is not None else []
+    params = fold.params() if fold is not None and fold.deferred is None else []  # (a shared fold's node routes them)
     y = _FusedConv.apply(x_raw, weight, bias, meta, *params)
     if bns is None:
         return y, None
@@ -1003,12 +1167,18 @@ def fused_conv(x_raw, fold, conv, out_bn=None, out_dtype=None, out_relu=False, s
         return y, BnFold.cat([eval_bn_fold(b, relu=True) for b in bns])
     n = y.shape[0] * y.shape[2] * y.shape[3]
     folds, off = [], 0
+    total = sum(b.num_features for b in bns)
+    own = torch.empty(5 * total, dtype=torch.float32, device=y.device) if len(bns) > 1 and _JOINT_BN_BACKWARD else None
     for b in bns:
         if b.training and b.track_running_stats and not getattr(b, "_liso_counter_deferred", False):
             b.num_batches_tracked += 1
-        folds.append(finalize_bn(meta["stats_partial"], n, b, meta.get("stats_shift"), channel_offset=off))
+        merged = (own, total, off) if own is not None else (merged_stats if len(bns) == 1 else None)
+        folds.append(finalize_bn(meta["stats_partial"], n, b, meta.get("stats_shift"), channel_offset=off, merged=merged))
         off += b.num_features
-    return y, BnFold.cat(folds)
+    out_fold = BnFold.cat(folds)
+    if own is not None:
+        out_fold.use_merged(own, total)
+    return y, out_fold
 
 
 # ---- InstanceNorm folding (inference) ----------------------------------------------------------------------------------------
