@@ -49,11 +49,12 @@ int liso_bn_relu_bwd_strided(const void* dy, long dy_stride, const void* x, long
                              const float* stats, int training, int relu, void* dx, long dx_stride, float* grad_gamma, float* grad_beta,
                              void* workspace, size_t workspace_bytes, void* stream);
 
-/* liso_bn_relu_bwd / liso_bn_relu_bwd_strided (dy_stride = x_stride = dx_stride = 0: dense rows) whose finalize launch also carries the
- * blocks of a deferred weight-gradient slab reduction (include/liso_conv.h: liso_conv_wgrad_deferred): grid = the finalize's blocks
- * first, then the reduction's.  The two roles share the launch and nothing else -- no flag, fence or atomic between them; every block
- * runs the instructions of the separate launches on the same data, so all results are the same bits.  The finalize (latency-bound, a
- * few blocks) runs in the shadow of the reduction (bandwidth-bound), one launch less on the backward pass's dependent chain per layer.
+/* The superset of the two entries above, and the one the Python side calls: the three strides are all zero (dense rows, liso_bn_relu_bwd)
+ * or all non-zero (liso_bn_relu_bwd_strided), and with job != NULL the finalize launch also carries the blocks of a deferred
+ * weight-gradient slab reduction (include/liso_conv.h: liso_conv_wgrad_deferred): grid = the finalize's blocks first, then the
+ * reduction's.  The two roles share the launch and nothing else -- no flag, fence or atomic between them; every block runs the
+ * instructions of the separate launches on the same data, so all results are the same bits.  The finalize (latency-bound, a few blocks)
+ * runs in the shadow of the reduction (bandwidth-bound), one launch less on the backward pass's dependent chain per layer.
  * job == NULL: exactly liso_bn_relu_bwd(_strided). */
 int liso_bn_relu_bwd_chained(const void* dy, long dy_stride, const void* x, long x_stride, int is_bf16, long m, int c, const float* gamma,
                              const float* stats, int training, int relu, void* dx, long dx_stride, float* grad_gamma, float* grad_beta,
@@ -64,14 +65,14 @@ int liso_bn_relu_bwd_chained(const void* dy, long dy_stride, const void* x, long
  * channel ranges [c_off, c_off + c), c <= 256, c_off on a 16-byte boundary (the deblocks' 3 x 128-channel concatenation), and receives
  * one or two gradients dy_a / dy_b (dy_b == NULL: one) -- a map with two consumers, each handing back dL/d(relu(bn(x))) for its own
  * use of it.  x, dy_a, dy_b and dx address channel 0 of their rows, each with its own row stride.  The call is three launches:
- *   reduce    grid (row blocks, groups): per (group, gradient) the geometry, row order and LDS summation order of
- *             liso_bn_relu_bwd_strided on that group's channels alone -> the same partial sums, bit for bit; x and the ReLU mask are
- *             read once per row for both gradients.
+ *   reduce    grid (row blocks, groups): per (group, gradient) the device function that is liso_bn_relu_bwd_strided's reduce pass, on
+ *             that group's channels alone (its geometry, row order and LDS summation order) -> the same partial sums, bit for bit; x
+ *             and the ReLU mask are read once per row for both gradients.
  *   finalize  one block per channel segment of every group (the segments and merge order of the single call), both gradients in turn;
  *             the parameter gradients written are fl(fl(sum_a) + fl(sum_b)) -- what adding the second single call's result onto the
  *             first one's gives in fp32 -- and the dx coefficients stay per gradient.  Behind these blocks ride the slab reductions of
  *             up to two deferred weight gradients (job_a / job_b, NULL: none), as in liso_bn_relu_bwd_chained.
- *   dx        per element dx_a and dx_b as the single calls compute them, each rounded to the element type, then
+ *   dx        per element dx_a and dx_b by the single calls' own dx device function, each rounded to the element type, then
  *             round(float(dx_a) + float(dx_b)): the elementwise sum of the two stored maps.  One gradient: dx_a.
  * No atomics, no flags between blocks; every group's grad_gamma / grad_beta [c] fp32 are overwritten.  `training` / `relu` hold for
  * all groups of the call. */

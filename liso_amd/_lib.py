@@ -372,6 +372,11 @@ def elem_code(dtype):
 def is_half(dtype):
     """a 16-bit storage type of the detector path (bf16 or fp16): 8 channels per lane, one MFMA per product"""
     return elem_code(dtype) != ELEM_F32
+
+
+def lane_channels(dtype):
+    """channels in a lane's 16-byte access of the channels-last passes: 8 in bf16 / fp16, 4 in fp32"""
+    return 8 if is_half(dtype) else 4
 CONV_OPT_SHARED_GPU = 1
 CONV_OPT_ROLES_CUS = 2
 

@@ -11,6 +11,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/liso_bn.h"
 #include "../../include/liso_iou3d.h"
 #include "chain_bodies.h"
@@ -249,6 +251,108 @@ __global__ __launch_bounds__(kThreads) void bn_apply_kernel(const T* __restrict_
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------
+// One copy of each pass's body, as in chain_bodies.h: the single calls (liso_bn_relu_bwd*, the InstanceNorm backward) and the grouped
+// call (liso_bn_relu_bwd_multi) wrap the SAME reduce and dx bodies, so a (group, gradient) pair of the grouped call has the geometry,
+// the per-thread row order, the LDS summation order and the instructions of the single call on that group's channels alone -- its
+// results are the bits of the separate calls by construction.  NG = upstream gradients (1, or 2 for a map with two consumers: x and the
+// ReLU mask are read once per row for both).  The kernels only find their block's pointers.
+
+// rows [r0, r1) of one group: per gradient n, sum(dz) and sum(dz * xhat) per channel -> partial[n] = sums a [c] | sums b [c]
+template <typename T, bool RELU, int NG>
+__device__ __forceinline__ void bn_bwd_reduce_body(const T* __restrict__ x, const T* const (&dy)[NG], long xs, const long (&gs)[NG], int c,
+                                                   int cg, int rl, const float* __restrict__ stats, long r0, long r1,
+                                                   float (*s_a)[Vec<T>::V + 1], float (*s_b)[Vec<T>::V + 1], float* const (&partial)[NG]) {
+    constexpr int V = Vec<T>::V;
+    const int tid = threadIdx.x;
+    const int col = tid % cg, rlane = tid / cg;
+    float sc[V], sh[V], mu[V], is[V], a[NG][V], b[NG][V];
+#pragma unroll
+    for (int j = 0; j < V; j++) {
+        sc[j] = stats[col * V + j]; sh[j] = stats[c + col * V + j];
+        mu[j] = stats[2 * c + col * V + j]; is[j] = stats[3 * c + col * V + j];
+#pragma unroll
+        for (int n = 0; n < NG; n++) { a[n][j] = 0.f; b[n][j] = 0.f; }
+    }
+#pragma unroll 4
+    for (long r = rlane < rl ? r0 + rlane : r1; r < r1; r += rl) {  // (rlane >= rl: C / V does not divide the block, idle lanes)
+        float vx[V], vg[NG][V];
+        Vec<T>::load(x + r * xs + col * V, vx);
+#pragma unroll
+        for (int n = 0; n < NG; n++) Vec<T>::load(dy[n] + r * gs[n] + col * V, vg[n]);
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+            const bool off = RELU && !(fmaf(vx[j], sc[j], sh[j]) > 0.f);  // ReLU mask recomputed from x
+            const float xh = (vx[j] - mu[j]) * is[j];
+#pragma unroll
+            for (int n = 0; n < NG; n++) {
+                const float dz = off ? 0.f : vg[n][j];
+                a[n][j] += dz;
+                b[n][j] = fmaf(dz, xh, b[n][j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int n = 0; n < NG; n++) {
+        if (n) __syncthreads();  // (the previous gradient's reads of s_a / s_b)
+#pragma unroll
+        for (int j = 0; j < V; j++) { s_a[tid][j] = a[n][j]; s_b[tid][j] = b[n][j]; }
+        __syncthreads();
+        if (tid < c) {  // one thread per channel finishes the block: tid -> (col2, j2)
+            const int col2 = tid / V, j2 = tid % V;
+            float sa = 0.f, sb = 0.f;
+            for (int q = 0; q < rl; q++) { sa += s_a[q * cg + col2][j2]; sb += s_b[q * cg + col2][j2]; }
+            partial[n][tid] = sa;
+            partial[n][c + tid] = sb;
+        }
+    }
+}
+
+// the value a store of T keeps, widened back (fp32: the value itself, made opaque so that the product in front of it is rounded
+// before the sum of the two gradients' dx is formed -- never a fused multiply-add of one into the other)
+template <typename T> __device__ __forceinline__ float stored(float v);
+template <> __device__ __forceinline__ float stored<float>(float v) { asm volatile("" : "+v"(v)); return v; }
+template <> __device__ __forceinline__ float stored<__hip_bfloat16>(float v) { return __bfloat162float(__float2bfloat16(v)); }
+template <> __device__ __forceinline__ float stored<_Float16>(float v) { return liso_e16::F16::round(v); }
+
+// rows blockIdx.x * rl + rlane, + gridDim.x * rl, ... < m of one group: dx = A * (dz - B - xhat * C) per gradient (coef[n] = A | B | C).
+// Two gradients: each dx rounded to T as its own store would, then their sum rounded once more (the elementwise add of the two stored
+// maps).
+template <typename T, bool RELU, int NG>
+__device__ __forceinline__ void bn_bwd_dx_body(const T* __restrict__ x, const T* const (&dy)[NG], long xs, const long (&gs)[NG], long m, int c,
+                                               int cg, int rl, const float* __restrict__ stats, const float* const (&coef)[NG],
+                                               T* __restrict__ dx, long ds) {
+    constexpr int V = Vec<T>::V;
+    const int col = threadIdx.x % cg, rlane = threadIdx.x / cg;
+    float sc[V], sh[V], mu[V], is[V], A[NG][V], Bc[NG][V], Cc[NG][V];
+#pragma unroll
+    for (int j = 0; j < V; j++) {
+        const int ch = col * V + j;
+        sc[j] = stats[ch]; sh[j] = stats[c + ch]; mu[j] = stats[2 * c + ch]; is[j] = stats[3 * c + ch];
+#pragma unroll
+        for (int n = 0; n < NG; n++) { A[n][j] = coef[n][ch]; Bc[n][j] = coef[n][c + ch]; Cc[n][j] = coef[n][2 * c + ch]; }
+    }
+    const long stride = (long)gridDim.x * rl;
+    for (long r = rlane < rl ? (long)blockIdx.x * rl + rlane : m; r < m; r += stride) {
+        float vx[V], vg[NG][V];
+        Vec<T>::load(x + r * xs + col * V, vx);
+#pragma unroll
+        for (int n = 0; n < NG; n++) Vec<T>::load(dy[n] + r * gs[n] + col * V, vg[n]);
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+#pragma unroll
+            for (int n = 0; n < NG; n++) {
+                float dz = vg[n][j];
+                // (the test is spelled per gradient: hoisted out of this loop, the bf16 / ReLU / NG = 1 kernels get 88 registers for 80)
+                if (RELU && !(fmaf(vx[j], sc[j], sh[j]) > 0.f)) dz = 0.f;
+                vg[n][j] = A[n][j] * (dz - Bc[n][j] - (vx[j] - mu[j]) * is[j] * Cc[n][j]);
+            }
+            if constexpr (NG == 2) vg[0][j] = stored<T>(vg[0][j]) + stored<T>(vg[1][j]);
+        }
+        Vec<T>::store(dx + r * ds + col * V, vg[0]);
+    }
+}
+
+// one BatchNorm (blockIdx.y = 0) or one InstanceNorm sample per blockIdx.y, one gradient
 template <typename T, bool RELU>
 __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restrict__ x, long m,
                                                                  int c, Geom g, const float* __restrict__ stats,
@@ -256,43 +360,24 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
     constexpr int V = Vec<T>::V;
     __shared__ float s_a[kThreads][V + 1];
     __shared__ float s_b[kThreads][V + 1];
-    x += (size_t)blockIdx.y * m * g.xs; dy += (size_t)blockIdx.y * m * g.gs; stats += (size_t)blockIdx.y * 4 * c;
-    partial += (size_t)blockIdx.y * gridDim.x * 2 * c;
-    const int tid = threadIdx.x;
-    const int col = tid % g.cg, rlane = tid / g.cg;
-    float sc[V], sh[V], mu[V], is[V], a[V], b[V];
-#pragma unroll
-    for (int j = 0; j < V; j++) {
-        sc[j] = stats[col * V + j]; sh[j] = stats[c + col * V + j];
-        mu[j] = stats[2 * c + col * V + j]; is[j] = stats[3 * c + col * V + j];
-        a[j] = 0.f; b[j] = 0.f;
-    }
+    const T* const dys[1] = {dy + (size_t)blockIdx.y * m * g.gs};
+    const long gs[1] = {g.gs};
+    float* const parts[1] = {partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * c};
     const long r0 = (long)blockIdx.x * g.rows_per_block;
     const long r1 = r0 + g.rows_per_block < m ? r0 + g.rows_per_block : m;
-#pragma unroll 4
-    for (long r = rlane < g.rl ? r0 + rlane : r1; r < r1; r += g.rl) {
-        float vx[V], vg[V];
-        Vec<T>::load(x + r * g.xs + col * V, vx);
-        Vec<T>::load(dy + r * g.gs + col * V, vg);
-#pragma unroll
-        for (int j = 0; j < V; j++) {
-            float dz = vg[j];
-            if (RELU && !(fmaf(vx[j], sc[j], sh[j]) > 0.f)) dz = 0.f;  // ReLU mask recomputed from x
-            a[j] += dz;
-            b[j] = fmaf(dz, (vx[j] - mu[j]) * is[j], b[j]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < V; j++) { s_a[tid][j] = a[j]; s_b[tid][j] = b[j]; }
-    __syncthreads();
-    if (tid < c) {
-        const int col2 = tid / V, j2 = tid % V;
-        float sa = 0.f, sb = 0.f;
-        for (int q = 0; q < g.rl; q++) { sa += s_a[q * g.cg + col2][j2]; sb += s_b[q * g.cg + col2][j2]; }
-        float* p = partial + (size_t)blockIdx.x * 2 * c;
-        p[tid] = sa;
-        p[c + tid] = sb;
-    }
+    bn_bwd_reduce_body<T, RELU, 1>(x + (size_t)blockIdx.y * m * g.xs, dys, g.xs, gs, c, g.cg, g.rl, stats + (size_t)blockIdx.y * 4 * c, r0, r1,
+                                   s_a, s_b, parts);
+}
+
+template <typename T, bool RELU>
+__global__ __launch_bounds__(kThreads) void bn_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__ x, long m, int c,
+                                                             Geom g, const float* __restrict__ stats,
+                                                             const float* __restrict__ coef, T* __restrict__ dx) {
+    const T* const dys[1] = {dy + (size_t)blockIdx.y * m * g.gs};
+    const long gs[1] = {g.gs};
+    const float* const coefs[1] = {coef + (size_t)blockIdx.y * 3 * c};
+    bn_bwd_dx_body<T, RELU, 1>(x + (size_t)blockIdx.y * m * g.xs, dys, g.xs, gs, m, c, g.cg, g.rl, stats + (size_t)blockIdx.y * 4 * c, coefs,
+                               dx + (size_t)blockIdx.y * m * g.ds, g.ds);
 }
 
 // sums -> grad_beta, grad_gamma and the three dx coefficients per channel (chain_bodies.h: bn_bwd_finalize_segment)
@@ -302,23 +387,28 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(liso_chain::BnBwd
     liso_chain::bn_bwd_finalize_segment(f, blockIdx.x, blockIdx.y, sh_a, sh_b);
 }
 
-// The finalize of ONE BatchNorm (blocks [0, n_fin): the channel segments) and the slab reduction of a deferred weight gradient (the
-// blocks behind them, four of the reduction's 256-thread blocks per workgroup) in one launch.  Nothing reads the weight gradient before
-// the optimizer, but as a launch of its own the reduction (~8 us, bandwidth-bound) sat on the backward pass's dependent chain in front
-// of the layer's data gradient; here the finalize (~5 us of dependent latency in a few blocks, dispatched first) runs in its shadow.
-// The roles share the launch and nothing else: no flag, fence or atomic, and a block's role depends on blockIdx only.
+// A finalize launch's workgroups behind its segment blocks: the slab reduction of a deferred weight gradient, four of the reduction's
+// 256-thread blocks per workgroup (`first`: this workgroup's first block of job j).  Nothing reads the weight gradient before the
+// optimizer, but as a launch of its own the reduction (~8 us, bandwidth-bound) sat on the backward pass's dependent chain in front of
+// the layer's data gradient; here the finalize (~5 us of dependent latency in a few blocks, dispatched first) runs in its shadow.  The
+// roles share the launch and its 16 KB of LDS (finalize: 2 x 1024 doubles; reduction: 4 x (16 x 16 float4)) and nothing else: no flag,
+// fence or atomic, and a block's role depends on blockIdx only.  PARTS: 16 / 1 as the launch was instantiated, 0: from the job's splits.
+template <int PARTS>
+__device__ __forceinline__ void ride_wgrad_reduce(const liso_wgrad_reduce_job& j, long first, long n_red, double* sh) {
+    const int quarter = threadIdx.x >> 8;
+    const long bid = first + quarter;
+    float4(*red)[16] = reinterpret_cast<float4(*)[16]>(sh) + quarter * 16;
+    if (PARTS == 16 || (PARTS == 0 && j.splits > 16)) liso_chain::wgrad_reduce_block<16>(j, bid, threadIdx.x & 255, red, bid < n_red);
+    else liso_chain::wgrad_reduce_block<1>(j, bid, threadIdx.x & 255, red, bid < n_red);
+}
+
+// the finalize of ONE BatchNorm (blocks [0, n_fin): the channel segments) with one riding reduction
 template <int PARTS>
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_reduce_kernel(liso_chain::BnBwdFinalizeArgs f, int n_fin,
                                                                       liso_wgrad_reduce_job j, long n_red) {
-    __shared__ double sh[2048];  // finalize: 2 x 1024 doubles; reduction: 4 x (16 x 16 float4) -- 16 KB either way
-    if ((int)blockIdx.x < n_fin) {
-        liso_chain::bn_bwd_finalize_segment(f, 0, blockIdx.x, sh, sh + 1024);
-        return;
-    }
-    const int quarter = threadIdx.x >> 8;
-    const long bid = (long)(blockIdx.x - n_fin) * 4 + quarter;
-    float4(*red)[16] = reinterpret_cast<float4(*)[16]>(sh) + quarter * 16;
-    liso_chain::wgrad_reduce_block<PARTS>(j, bid, threadIdx.x & 255, red, bid < n_red);
+    __shared__ double sh[2048];
+    if ((int)blockIdx.x < n_fin) liso_chain::bn_bwd_finalize_segment(f, 0, blockIdx.x, sh, sh + 1024);
+    else ride_wgrad_reduce<PARTS>(j, (long)(blockIdx.x - n_fin) * 4, n_red, sh);
 }
 
 // channel segment of the finalize launch: 32 where the channel count allows and there are enough partial sums to spread
@@ -369,36 +459,6 @@ __global__ __launch_bounds__(1024) void in_bwd_finalize_sum_kernel(const float* 
     if (tid < c) { grad_beta[tid] = (float)sum_a; grad_gamma[tid] = (float)sum_b; }
 }
 
-template <typename T, bool RELU>
-__global__ __launch_bounds__(kThreads) void bn_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__ x, long m, int c,
-                                                             Geom g, const float* __restrict__ stats,
-                                                             const float* __restrict__ coef, T* __restrict__ dx) {
-    constexpr int V = Vec<T>::V;
-    const int col = threadIdx.x % g.cg, rlane = threadIdx.x / g.cg;
-    x += (size_t)blockIdx.y * m * g.xs; dy += (size_t)blockIdx.y * m * g.gs; dx += (size_t)blockIdx.y * m * g.ds;
-    stats += (size_t)blockIdx.y * 4 * c; coef += (size_t)blockIdx.y * 3 * c;
-    float sc[V], sh[V], mu[V], is[V], A[V], Bc[V], Cc[V];
-#pragma unroll
-    for (int j = 0; j < V; j++) {
-        const int ch = col * V + j;
-        sc[j] = stats[ch]; sh[j] = stats[c + ch]; mu[j] = stats[2 * c + ch]; is[j] = stats[3 * c + ch];
-        A[j] = coef[ch]; Bc[j] = coef[c + ch]; Cc[j] = coef[2 * c + ch];
-    }
-    const long stride = (long)gridDim.x * g.rl;
-    for (long r = rlane < g.rl ? (long)blockIdx.x * g.rl + rlane : m; r < m; r += stride) {
-        float vx[V], vg[V];
-        Vec<T>::load(x + r * g.xs + col * V, vx);
-        Vec<T>::load(dy + r * g.gs + col * V, vg);
-#pragma unroll
-        for (int j = 0; j < V; j++) {
-            float dz = vg[j];
-            if (RELU && !(fmaf(vx[j], sc[j], sh[j]) > 0.f)) dz = 0.f;
-            vg[j] = A[j] * (dz - Bc[j] - (vx[j] - mu[j]) * is[j] * Cc[j]);
-        }
-        Vec<T>::store(dx + r * g.ds + col * V, vg);
-    }
-}
-
 inline bool geom(int c, int v, long m, Geom* g, int* nblk) {
     if (c <= 0 || c % v != 0 || c > kThreads) return false;
     const int cg = c / v;
@@ -423,9 +483,7 @@ inline int stream_grid(long m, const Geom& g) {
 
 // ---- grouped backward with one or two upstream gradients (include/liso_bn.h: liso_bn_relu_bwd_multi) -----------------------------
 // Up to four BatchNorms over channel ranges of ONE raw tensor, and up to two gradients arriving at it (a map with two consumers), in the
-// three launches of a single call.  Every (group, gradient) pair keeps the geometry, the per-thread row order and the LDS summation
-// order of bn_bwd_reduce_kernel / bn_bwd_finalize_segment on that group's channels alone, so its sums are the bits of the separate
-// call; x and the ReLU mask are read once per row for both gradients.
+// three launches of a single call: blockIdx.y = group, whose geometry and pointers come from the table.
 struct MultiGroup {
     int c_off, c;          // channel range inside a row of x / dy / dx
     int cg, rl;            // Geom of this group's channel count
@@ -444,13 +502,6 @@ struct MultiArgs {
     long xs, gs[2], ds;
 };
 
-// the value a store of T keeps, widened back (fp32: the value itself, made opaque so that the product in front of it is rounded
-// before the sum of the two gradients' dx is formed -- never a fused multiply-add of one into the other)
-template <typename T> __device__ __forceinline__ float stored(float v);
-template <> __device__ __forceinline__ float stored<float>(float v) { asm volatile("" : "+v"(v)); return v; }
-template <> __device__ __forceinline__ float stored<__hip_bfloat16>(float v) { return __bfloat162float(__float2bfloat16(v)); }
-template <> __device__ __forceinline__ float stored<_Float16>(float v) { return liso_e16::F16::round(v); }
-
 template <typename T, bool RELU, int NG>
 __global__ __launch_bounds__(kThreads) void bn_bwd_multi_reduce_kernel(const T* __restrict__ dy_a, const T* __restrict__ dy_b,
                                                                        const T* __restrict__ x, MultiArgs A) {
@@ -458,61 +509,22 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_multi_reduce_kernel(const T* 
     __shared__ float s_a[kThreads][V + 1];
     __shared__ float s_b[kThreads][V + 1];
     const MultiGroup& G = A.g[blockIdx.y];
-    const int c = G.c, cg = G.cg, rl = G.rl;
-    const float* __restrict__ stats = G.stats;
-    const long m = A.m, xs = A.xs;
-    const T* dy[2] = {dy_a + G.c_off, NG == 2 ? dy_b + G.c_off : nullptr};
-    x += G.c_off;
-    const int tid = threadIdx.x;
-    const int col = tid % cg, rlane = tid / cg;
-    float sc[V], sh[V], mu[V], is[V], a[NG][V], b[NG][V];
-#pragma unroll
-    for (int j = 0; j < V; j++) {
-        sc[j] = stats[col * V + j]; sh[j] = stats[c + col * V + j];
-        mu[j] = stats[2 * c + col * V + j]; is[j] = stats[3 * c + col * V + j];
-#pragma unroll
-        for (int n = 0; n < NG; n++) { a[n][j] = 0.f; b[n][j] = 0.f; }
-    }
-    const long r0 = (long)blockIdx.x * A.rows_per_block;
-    const long r1 = r0 + A.rows_per_block < m ? r0 + A.rows_per_block : m;
-#pragma unroll 4
-    for (long r = rlane < rl ? r0 + rlane : r1; r < r1; r += rl) {
-        float vx[V], vg[NG][V];
-        Vec<T>::load(x + r * xs + col * V, vx);
-#pragma unroll
-        for (int n = 0; n < NG; n++) Vec<T>::load(dy[n] + r * A.gs[n] + col * V, vg[n]);
-#pragma unroll
-        for (int j = 0; j < V; j++) {
-            const bool off = RELU && !(fmaf(vx[j], sc[j], sh[j]) > 0.f);  // ReLU mask recomputed from x, once for both gradients
-            const float xh = (vx[j] - mu[j]) * is[j];
-#pragma unroll
-            for (int n = 0; n < NG; n++) {
-                const float dz = off ? 0.f : vg[n][j];
-                a[n][j] += dz;
-                b[n][j] = fmaf(dz, xh, b[n][j]);
-            }
-        }
-    }
+    const T* dys[NG];
+    long gs[NG];
+    float* parts[NG];
 #pragma unroll
     for (int n = 0; n < NG; n++) {
-        if (n) __syncthreads();  // (the previous gradient's reads of s_a / s_b)
-#pragma unroll
-        for (int j = 0; j < V; j++) { s_a[tid][j] = a[n][j]; s_b[tid][j] = b[n][j]; }
-        __syncthreads();
-        if (tid < c) {
-            const int col2 = tid / V, j2 = tid % V;
-            float sa = 0.f, sb = 0.f;
-            for (int q = 0; q < rl; q++) { sa += s_a[q * cg + col2][j2]; sb += s_b[q * cg + col2][j2]; }
-            float* p = G.partial[n] + (size_t)blockIdx.x * 2 * c;
-            p[tid] = sa;
-            p[c + tid] = sb;
-        }
+        dys[n] = (n ? dy_b : dy_a) + G.c_off; gs[n] = A.gs[n];
+        parts[n] = G.partial[n] + (size_t)blockIdx.x * 2 * G.c;
     }
+    const long r0 = (long)blockIdx.x * A.rows_per_block;
+    const long r1 = r0 + A.rows_per_block < A.m ? r0 + A.rows_per_block : A.m;
+    bn_bwd_reduce_body<T, RELU, NG>(x + G.c_off, dys, A.xs, gs, G.c, G.cg, G.rl, G.stats, r0, r1, s_a, s_b, parts);
 }
 
 // blocks [0, n_fin): one channel segment of one group each -- bn_bwd_finalize_segment per gradient; with two gradients each writes its
 // parameter gradients to scratch and the thread that wrote both adds them (fp32: what autograd's add of the second contribution onto
-// the first gives).  Behind them the blocks of up to two riding weight-gradient slab reductions, as in bn_bwd_finalize_reduce_kernel.
+// the first gives).  Behind them the workgroups of up to two riding reductions, job 0's first.
 template <int NG>
 __global__ __launch_bounds__(1024) void bn_bwd_multi_finalize_kernel(MultiArgs A, int n_fin, liso_wgrad_reduce_job j0, long n_red0,
                                                                      liso_wgrad_reduce_job j1, long n_red1) {
@@ -536,59 +548,31 @@ __global__ __launch_bounds__(1024) void bn_bwd_multi_finalize_kernel(MultiArgs A
         }
         return;
     }
-    const int quarter = threadIdx.x >> 8;
-    long bid = (long)(blockIdx.x - n_fin) * 4 + quarter;
-    float4(*red)[16] = reinterpret_cast<float4(*)[16]>(sh) + quarter * 16;
-    const long wg0 = (n_red0 + 3) / 4 * 4;  // (job 0's workgroups are whole: a workgroup serves one job, its barriers stay uniform)
-    if (bid < wg0) {
-        if (j0.splits > 16) liso_chain::wgrad_reduce_block<16>(j0, bid, threadIdx.x & 255, red, bid < n_red0);
-        else liso_chain::wgrad_reduce_block<1>(j0, bid, threadIdx.x & 255, red, bid < n_red0);
-    } else {
-        bid -= wg0;
-        if (j1.splits > 16) liso_chain::wgrad_reduce_block<16>(j1, bid, threadIdx.x & 255, red, bid < n_red1);
-        else liso_chain::wgrad_reduce_block<1>(j1, bid, threadIdx.x & 255, red, bid < n_red1);
-    }
+    // (job 0's workgroups are whole: a workgroup serves one job, its barriers stay uniform)
+    const long wg = (long)(blockIdx.x - n_fin), wg0 = (n_red0 + 3) / 4;
+    if (wg < wg0) ride_wgrad_reduce<0>(j0, wg * 4, n_red0, sh);
+    else ride_wgrad_reduce<0>(j1, (wg - wg0) * 4, n_red1, sh);
 }
 
 template <typename T, bool RELU, int NG>
 __global__ __launch_bounds__(kThreads) void bn_bwd_multi_dx_kernel(const T* __restrict__ dy_a, const T* __restrict__ dy_b,
                                                                    const T* __restrict__ x, MultiArgs A, T* __restrict__ dx) {
-    constexpr int V = Vec<T>::V;
     const MultiGroup& G = A.g[blockIdx.y];
-    const int c = G.c, cg = G.cg, rl = G.rl;
-    const float* __restrict__ stats = G.stats;
-    const long m = A.m, xs = A.xs, ds = A.ds;
-    const T* dy[2] = {dy_a + G.c_off, NG == 2 ? dy_b + G.c_off : nullptr};
-    x += G.c_off; dx += G.c_off;
-    const int col = threadIdx.x % cg, rlane = threadIdx.x / cg;
-    float sc[V], sh[V], mu[V], is[V], Ac[NG][V], Bc[NG][V], Cc[NG][V];
+    const T* dys[NG];
+    long gs[NG];
+    const float* coefs[NG];
 #pragma unroll
-    for (int j = 0; j < V; j++) {
-        const int ch = col * V + j;
-        sc[j] = stats[ch]; sh[j] = stats[c + ch]; mu[j] = stats[2 * c + ch]; is[j] = stats[3 * c + ch];
-#pragma unroll
-        for (int n = 0; n < NG; n++) { Ac[n][j] = G.coef[n][ch]; Bc[n][j] = G.coef[n][c + ch]; Cc[n][j] = G.coef[n][2 * c + ch]; }
-    }
-    const long stride = (long)gridDim.x * rl;
-    for (long r = rlane < rl ? (long)blockIdx.x * rl + rlane : m; r < m; r += stride) {
-        float vx[V], vg[NG][V];
-        Vec<T>::load(x + r * xs + col * V, vx);
-#pragma unroll
-        for (int n = 0; n < NG; n++) Vec<T>::load(dy[n] + r * A.gs[n] + col * V, vg[n]);
-#pragma unroll
-        for (int j = 0; j < V; j++) {
-            const bool off = RELU && !(fmaf(vx[j], sc[j], sh[j]) > 0.f);
-#pragma unroll
-            for (int n = 0; n < NG; n++) {
-                const float dz = off ? 0.f : vg[n][j];
-                vg[n][j] = Ac[n][j] * (dz - Bc[n][j] - (vx[j] - mu[j]) * is[j] * Cc[n][j]);
-            }
-            // two gradients: each dx rounded to T as its own store would, then their sum rounded once more (the elementwise add of the
-            // two stored maps)
-            if (NG == 2) vg[0][j] = stored<T>(vg[0][j]) + stored<T>(vg[1][j]);
-        }
-        Vec<T>::store(dx + r * ds + col * V, vg[0]);
-    }
+    for (int n = 0; n < NG; n++) { dys[n] = (n ? dy_b : dy_a) + G.c_off; gs[n] = A.gs[n]; coefs[n] = G.coef[n]; }
+    bn_bwd_dx_body<T, RELU, NG>(x + G.c_off, dys, A.xs, gs, A.m, G.c, G.cg, G.rl, G.stats, coefs, dx + G.c_off, A.ds);
+}
+
+// the three kernel templates of an entry point are instantiated per element type and ReLU flag: f(T{}, std::bool_constant<RELU>{})
+template <typename F>
+inline void with_elem_relu(int elem, int relu, F&& f) {
+    auto r = [&](auto t) { if (relu) f(t, std::true_type{}); else f(t, std::false_type{}); };
+    if (elem == LISO_ELEM_F16) r(_Float16{});
+    else if (elem) r(__hip_bfloat16{});
+    else r(float{});
 }
 
 }  // namespace
@@ -625,11 +609,10 @@ int liso_bn_relu_fwd(const void* x, int is_bf16, long m, int c, const float* gam
     }
     if (m > 0) {
         const int grid = stream_grid(m, g);
-#define LISO_APPLY(T, R) bn_apply_kernel<T, R><<<grid, kThreads, 0, st>>>((const T*)x, m, c, g, stats, (T*)y)
-        if (is_bf16 == LISO_ELEM_F16) { if (relu) LISO_APPLY(_Float16, true); else LISO_APPLY(_Float16, false); }
-        else if (is_bf16) { if (relu) LISO_APPLY(__hip_bfloat16, true); else LISO_APPLY(__hip_bfloat16, false); }
-        else { if (relu) LISO_APPLY(float, true); else LISO_APPLY(float, false); }
-#undef LISO_APPLY
+        with_elem_relu(is_bf16, relu, [&](auto t, auto r) {
+            using T = decltype(t);
+            bn_apply_kernel<T, decltype(r)::value><<<grid, kThreads, 0, st>>>((const T*)x, m, c, g, stats, (T*)y);
+        });
     }
     return check_launch();
 }
@@ -658,21 +641,18 @@ static int bn_relu_bwd(const void* dy, const void* x, int is_bf16, long m, int c
     const int n_fin = c / cw;
     const long n_red = job ? liso_chain::wgrad_reduce_blocks(*job) : 0;
     const unsigned grid_fr = (unsigned)(n_fin + (n_red + 3) / 4);
-#define LISO_BWD(T, R)                                                                                                     \
-    do {                                                                                                                   \
-        bn_bwd_reduce_kernel<T, R><<<nblk, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial);          \
-        if (job && job->splits > 16)                                                                                       \
-            bn_bwd_finalize_reduce_kernel<16><<<grid_fr, 1024, 0, st>>>(fa, n_fin, *job, n_red);                           \
-        else if (job)                                                                                                      \
-            bn_bwd_finalize_reduce_kernel<1><<<grid_fr, 1024, 0, st>>>(fa, n_fin, *job, n_red);                            \
-        else                                                                                                               \
-            bn_bwd_finalize_kernel<<<dim3(1, c / cw), 1024, 0, st>>>(fa);                                                  \
-        bn_bwd_dx_kernel<T, R><<<grid, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, coef, (T*)dx);          \
-    } while (0)
-    if (is_bf16 == LISO_ELEM_F16) { if (relu) LISO_BWD(_Float16, true); else LISO_BWD(_Float16, false); }
-    else if (is_bf16) { if (relu) LISO_BWD(__hip_bfloat16, true); else LISO_BWD(__hip_bfloat16, false); }
-    else { if (relu) LISO_BWD(float, true); else LISO_BWD(float, false); }
-#undef LISO_BWD
+    with_elem_relu(is_bf16, relu, [&](auto t, auto r) {
+        using T = decltype(t);
+        constexpr bool R = decltype(r)::value;
+        bn_bwd_reduce_kernel<T, R><<<nblk, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial);
+        if (job && job->splits > 16)
+            bn_bwd_finalize_reduce_kernel<16><<<grid_fr, 1024, 0, st>>>(fa, n_fin, *job, n_red);
+        else if (job)
+            bn_bwd_finalize_reduce_kernel<1><<<grid_fr, 1024, 0, st>>>(fa, n_fin, *job, n_red);
+        else
+            bn_bwd_finalize_kernel<<<dim3(1, c / cw), 1024, 0, st>>>(fa);
+        bn_bwd_dx_kernel<T, R><<<grid, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, coef, (T*)dx);
+    });
     return check_launch();
 }
 
@@ -788,23 +768,18 @@ int liso_bn_relu_bwd_multi(const void* dy_a, long dy_a_stride, const void* dy_b,
     const long n_red0 = job_a ? liso_chain::wgrad_reduce_blocks(*job_a) : 0, n_red1 = job_b ? liso_chain::wgrad_reduce_blocks(*job_b) : 0;
     const unsigned grid_f = (unsigned)(n_fin + (n_red0 + 3) / 4 + (n_red1 + 3) / 4);
     const dim3 grid_r((unsigned)A.nblk, (unsigned)n_groups), grid_d((unsigned)gdx, (unsigned)n_groups);
-#define LISO_BWD(T, R, N)                                                                                                            \
-    do {                                                                                                                             \
-        bn_bwd_multi_reduce_kernel<T, R, N><<<grid_r, kThreads, 0, st>>>((const T*)dy_a, (const T*)dy_b, (const T*)x, A);            \
-        bn_bwd_multi_finalize_kernel<N><<<grid_f, 1024, 0, st>>>(A, n_fin, job_a ? *job_a : none, n_red0, job_b ? *job_b : none,     \
-                                                                 n_red1);                                                            \
-        bn_bwd_multi_dx_kernel<T, R, N><<<grid_d, kThreads, 0, st>>>((const T*)dy_a, (const T*)dy_b, (const T*)x, A, (T*)dx);        \
-    } while (0)
-#define LISO_BWD_T(T)                                                                                                                \
-    do {                                                                                                                             \
-        if (relu) { if (ng == 2) LISO_BWD(T, true, 2); else LISO_BWD(T, true, 1); }                                                  \
-        else { if (ng == 2) LISO_BWD(T, false, 2); else LISO_BWD(T, false, 1); }                                                     \
-    } while (0)
-    if (elem == LISO_ELEM_F16) LISO_BWD_T(_Float16);
-    else if (elem) LISO_BWD_T(__hip_bfloat16);
-    else LISO_BWD_T(float);
-#undef LISO_BWD_T
-#undef LISO_BWD
+    with_elem_relu(elem, relu, [&](auto t, auto r) {
+        using T = decltype(t);
+        constexpr bool R = decltype(r)::value;
+        auto launch = [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            bn_bwd_multi_reduce_kernel<T, R, N><<<grid_r, kThreads, 0, st>>>((const T*)dy_a, (const T*)dy_b, (const T*)x, A);
+            bn_bwd_multi_finalize_kernel<N><<<grid_f, 1024, 0, st>>>(A, n_fin, job_a ? *job_a : none, n_red0, job_b ? *job_b : none, n_red1);
+            bn_bwd_multi_dx_kernel<T, R, N><<<grid_d, kThreads, 0, st>>>((const T*)dy_a, (const T*)dy_b, (const T*)x, A, (T*)dx);
+        };
+        if (ng == 2) launch(std::integral_constant<int, 2>{});
+        else launch(std::integral_constant<int, 1>{});
+    });
     return check_launch();
 }
 
@@ -829,10 +804,10 @@ int liso_in_relu_fwd(const void* x, int is_bf16, int groups, long m, int c, cons
     else
         bn_stats_kernel<float><<<gs, kThreads, 0, st>>>((const float*)x, m, c, g, partial);
     bn_finalize_kernel<<<groups, 1024, 0, st>>>(partial, nblk, m, c, g.rows_per_block, gamma, beta, nullptr, nullptr, 0.f, eps, stats);
-#define LISO_APPLY(T, R) bn_apply_kernel<T, R><<<ga, kThreads, 0, st>>>((const T*)x, m, c, g, stats, (T*)y)
-    if (is_bf16) { if (relu) LISO_APPLY(__hip_bfloat16, true); else LISO_APPLY(__hip_bfloat16, false); }
-    else { if (relu) LISO_APPLY(float, true); else LISO_APPLY(float, false); }
-#undef LISO_APPLY
+    with_elem_relu(is_bf16, relu, [&](auto t, auto r) {  // (fp32 / bf16: checked above)
+        using T = decltype(t);
+        bn_apply_kernel<T, decltype(r)::value><<<ga, kThreads, 0, st>>>((const T*)x, m, c, g, stats, (T*)y);
+    });
     return check_launch();
 }
 
@@ -850,18 +825,16 @@ static int in_relu_bwd(const void* dy, const void* x, int is_bf16, int groups, l
     const dim3 gs((unsigned)nblk, (unsigned)groups), ga((unsigned)stream_grid(m, g), (unsigned)groups);
     const int cw = finalize_segment(c, nblk);
     const liso_chain::BnBwdFinalizeArgs fa{partial, nblk, m, c, cw, gamma, stats, 1, grad_gamma, grad_beta, coef};
-#define LISO_BWD(T, R)                                                                                                     \
-    do {                                                                                                                   \
-        bn_bwd_reduce_kernel<T, R><<<gs, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial); \
-        if (summed)                                                                                                        \
-            in_bwd_finalize_sum_kernel<<<1, 1024, 0, st>>>(partial, groups, nblk, m, c, gamma, stats, grad_gamma, grad_beta, coef); \
-        else                                                                                                               \
-            bn_bwd_finalize_kernel<<<dim3(groups, c / cw), 1024, 0, st>>>(fa);                                             \
-        bn_bwd_dx_kernel<T, R><<<ga, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, coef, (T*)dx);            \
-    } while (0)
-    if (is_bf16) { if (relu) LISO_BWD(__hip_bfloat16, true); else LISO_BWD(__hip_bfloat16, false); }
-    else { if (relu) LISO_BWD(float, true); else LISO_BWD(float, false); }
-#undef LISO_BWD
+    with_elem_relu(is_bf16, relu, [&](auto t, auto r) {  // (fp32 / bf16: checked above)
+        using T = decltype(t);
+        constexpr bool R = decltype(r)::value;
+        bn_bwd_reduce_kernel<T, R><<<gs, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, partial);
+        if (summed)
+            in_bwd_finalize_sum_kernel<<<1, 1024, 0, st>>>(partial, groups, nblk, m, c, gamma, stats, grad_gamma, grad_beta, coef);
+        else
+            bn_bwd_finalize_kernel<<<dim3(groups, c / cw), 1024, 0, st>>>(fa);
+        bn_bwd_dx_kernel<T, R><<<ga, kThreads, 0, st>>>((const T*)dy, (const T*)x, m, c, g, stats, coef, (T*)dx);
+    });
     return check_launch();
 }
 

@@ -681,7 +681,7 @@ def supported(x, weight, spec):
     """can the own kernels run this convolution (forward, data and weight gradient)?"""
     if not x.is_cuda or x.dtype not in (torch.bfloat16, torch.float16, torch.float32):
         return False
-    vec = 8 if L.is_half(x.dtype) else 4
+    vec = L.lane_channels(x.dtype)
     ci = x.shape[1]
     co = weight.shape[1] if spec.transposed else weight.shape[0]
     if ci % vec or spec.kh * spec.kw > L.CONV_MAX_TAPS:
@@ -810,49 +810,59 @@ def _direct_target(p):
     return g
 
 
+def _bn_backward_prelude(gs, x_raw, groups, table=None):
+    """What the single and the grouped BatchNorm-backward call share.  `gs`: the gradients of relu?(bn(x_raw)), logical NCHW like x_raw,
+    cast to its dtype; `groups`: the BatchNorms' dicts; `table`: bn_group_table's offsets for the grouped call, which reads every layout
+    in place -> None where one is not regular rows (the single call reads a contiguous copy there).
+    -> (physical [B, H, W, C] views and row strides [(xv, xs), (gv, gs), ...], [(dgamma, dbeta, direct) per group], group table of the
+    grouped call, workspace).  direct: both vectors are the parameters' own .grad buffers (`_direct_target`: both or neither, and never
+    for a gamma that is not a Parameter, like the merged statistics'), autograd is told None."""
+    vec, views = L.lane_channels(x_raw.dtype), []
+    for t in (x_raw, *gs):
+        if t.dtype != x_raw.dtype:
+            t = t.to(x_raw.dtype)
+        v, s = _rows_view(t, vec)
+        if table is not None and (v is None or (views and v.shape != views[0][0].shape)):
+            return None
+        views.append((v, s) if v is not None else (t.permute(0, 2, 3, 1).contiguous(), t.shape[1]))
+    dev, lib = x_raw.device, L.lib()
+    targets = []
+    for grp in groups:
+        C = grp["gamma"].shape[0]
+        tg, tb = _direct_target(grp["gamma"]), _direct_target(grp["beta"])
+        direct = tg is not None and tb is not None
+        targets.append((tg if direct else torch.empty(C, dtype=torch.float32, device=dev),
+                        tb if direct else torch.empty(C, dtype=torch.float32, device=dev), direct))
+    if table is None:
+        tab, nbytes = None, lib.liso_bn_workspace_bytes(groups[0]["gamma"].shape[0])
+    else:
+        tab = (L.BnGroup * len(groups))()
+        for row, grp, (off, c), (gg, gb, _) in zip(tab, groups, table, targets):
+            row.c_off, row.c = off, c
+            row.gamma, row.stats, row.grad_gamma, row.grad_beta = grp["gamma"].data_ptr(), grp["stats"].data_ptr(), gg.data_ptr(), gb.data_ptr()
+        nbytes = lib.liso_bn_multi_workspace_bytes(tab, len(groups), len(gs))
+    return views, targets, tab, torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
 def _bn_backward_group(g, x_raw, grp, relu, training, out=None, job=None):
     """gradient through relu?(bn(x_raw)) of ONE BatchNorm given g = dL/d(output): -> (dx_raw, dgamma, dbeta); g, x_raw logical NCHW.
-    Channel slices of wider channels-last tensors are read in place (liso_bn_relu_bwd_strided); `out`: a logical-NCHW tensor (e.g. the
-    group's channel slice of the concatenated input gradient) to write dx_raw into.  `job`: a WgradReduceJob whose slab reduction rides
-    in this call's finalize launch (liso_bn_relu_bwd_chained)."""
+    One entry point, liso_bn_relu_bwd_chained: channel slices of wider channels-last tensors are read in place (the three row strides;
+    all zero for dense rows), `out`: a logical-NCHW tensor (e.g. the group's channel slice of the concatenated input gradient) to write
+    dx_raw into, `job`: a WgradReduceJob whose slab reduction rides in this call's finalize launch (None or done already: none rides)."""
     C = grp["gamma"].shape[0]
-    vec = 8 if L.is_half(x_raw.dtype) else 4
-    xv, xs = _rows_view(x_raw, vec)
-    if xv is None:
-        xv, xs = x_raw.permute(0, 2, 3, 1).contiguous(), C
-    if g.dtype != xv.dtype:
-        g = g.to(xv.dtype)
-    gv, gs = _rows_view(g, vec)
-    if gv is None:
-        gv, gs = g.permute(0, 2, 3, 1).contiguous(), C
+    ((xv, xs), (gv, gs)), ((gg, gb, direct),), _, ws = _bn_backward_prelude([g], x_raw, [grp])
     M = xv.numel() // C
-    lib = L.lib()
-    dxv, ds = _rows_view(out, vec) if out is not None else (None, 0)
+    dxv, ds = _rows_view(out, L.lane_channels(xv.dtype)) if out is not None else (None, 0)
     if dxv is None:
         dxv, ds = torch.empty(xv.shape, dtype=xv.dtype, device=xv.device), C
-    tg, tb = _direct_target(grp["gamma"]), _direct_target(grp["beta"])
-    direct = tg is not None and tb is not None
-    gg = tg if direct else torch.empty(C, dtype=torch.float32, device=xv.device)
-    gb = tb if direct else torch.empty(C, dtype=torch.float32, device=xv.device)
-    nbytes = lib.liso_bn_workspace_bytes(C)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=xv.device)
-    bf = L.elem_code(xv.dtype)
-    units = 5 * M * C * xv.element_size()
+    if (xs, gs, ds) == (C, C, C):
+        xs = gs = ds = 0  # (the entry's rule: all three zero -- dense rows -- or all three non-zero)
+    riding = job is not None and not job.done
     with torch.cuda.device(xv.device):
-        if job is not None and not job.done:
-            dense = (xs, gs, ds) == (C, C, C)
-            L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd_chained(
-                L.ptr(gv), 0 if dense else gs, L.ptr(xv), 0 if dense else xs, bf, M, C, L.ptr(grp["gamma"]), L.ptr(grp["stats"]), int(training),
-                int(relu), L.ptr(dxv), 0 if dense else ds, L.ptr(gg), L.ptr(gb), L.ptr(ws), nbytes, job.ride(), L.stream_ptr()), units=units),
-                "bn_relu_bwd_chained")
-        elif (xs, gs, ds) != (C, C, C):
-            L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd_strided(
-                L.ptr(gv), gs, L.ptr(xv), xs, bf, M, C, L.ptr(grp["gamma"]), L.ptr(grp["stats"]), int(training), int(relu), L.ptr(dxv), ds,
-                L.ptr(gg), L.ptr(gb), L.ptr(ws), nbytes, L.stream_ptr()), units=units), "bn_relu_bwd_strided")
-        else:
-            args = (L.ptr(gv), L.ptr(xv), bf, M, C, L.ptr(grp["gamma"]), L.ptr(grp["stats"]), int(training), int(relu), L.ptr(dxv), L.ptr(gg),
-                    L.ptr(gb), L.ptr(ws), nbytes)
-            L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd(*args, L.stream_ptr()), units=units), "bn_relu_bwd")
+        L.check(L.TIMER.launch("bn_bwd", lambda: L.lib().liso_bn_relu_bwd_chained(
+            L.ptr(gv), gs, L.ptr(xv), xs, L.elem_code(xv.dtype), M, C, L.ptr(grp["gamma"]), L.ptr(grp["stats"]), int(training), int(relu),
+            L.ptr(dxv), ds, L.ptr(gg), L.ptr(gb), L.ptr(ws), ws.numel(), job.ride() if riding else None, L.stream_ptr()),
+            units=5 * M * C * xv.element_size()), "bn_relu_bwd_chained")
     return dxv.permute(0, 3, 1, 2), (None if direct else gg), (None if direct else gb)
 
 
@@ -884,52 +894,82 @@ def bn_group_table(Cs, vec):
     return table
 
 
-def _bn_backward_multi(gs, x_raw, fold, jobs=()):
+def _bn_backward_grouped(gs, x_raw, fold, jobs=()):
     """gradient through relu?(bn(x_raw)) of ALL groups of `fold` given one or two gradients `gs` of its output (two consumers of one
-    raw map): ONE grouped call, three launches -> (dx_raw logical NCHW = the sum over the gradients, [dgamma0, dbeta0, ...]), or None
-    where a layout is not regular rows or the groups do not fit the call (the caller takes the per-group path).  `jobs`: up to two
-    WgradReduceJobs that ride in the finalize launch."""
-    vec = 8 if L.is_half(x_raw.dtype) else 4
+    raw map): ONE grouped call (liso_bn_relu_bwd_multi), three launches -> (dx_raw logical NCHW = the sum over the gradients, [dgamma0,
+    dbeta0, ...]), or None where a layout is not regular rows or the groups do not fit the call.  `jobs`: WgradReduceJobs, the first two
+    that are not done ride in the finalize launch."""
     Cs = [grp["gamma"].shape[0] for grp in fold.groups]
-    table = bn_group_table(Cs, vec)
-    xv, xs = _rows_view(x_raw, vec)
-    if table is None or xv is None or x_raw.shape[1] != sum(Cs) or not 1 <= len(gs) <= 2:
+    table = bn_group_table(Cs, L.lane_channels(x_raw.dtype))
+    if table is None or x_raw.shape[1] != sum(Cs) or not 1 <= len(gs) <= 2:
         return None
-    views = []
-    for g in gs:
-        if g.dtype != xv.dtype:
-            g = g.to(xv.dtype)
-        gv, s = _rows_view(g, vec)
-        if gv is None or gv.shape != xv.shape:
-            return None
-        views.append((gv, s))
-    B, H, W, Ct = xv.shape
-    M = B * H * W
-    lib = L.lib()
-    dxv = torch.empty((B, H, W, Ct), dtype=xv.dtype, device=xv.device)
-    tab = (L.BnGroup * len(Cs))()
-    grads, keep = [], []
-    for k, (grp, (off, C)) in enumerate(zip(fold.groups, table)):
-        tg, tb = _direct_target(grp["gamma"]), _direct_target(grp["beta"])
-        direct = tg is not None and tb is not None
-        gg = tg if direct else torch.empty(C, dtype=torch.float32, device=xv.device)
-        gb = tb if direct else torch.empty(C, dtype=torch.float32, device=xv.device)
-        keep += [gg, gb]
-        tab[k].c_off, tab[k].c = off, C
-        tab[k].gamma, tab[k].stats, tab[k].grad_gamma, tab[k].grad_beta = (grp["gamma"].data_ptr(), grp["stats"].data_ptr(), gg.data_ptr(),
-                                                                            gb.data_ptr())
-        grads += [None if direct else gg, None if direct else gb]
-    nbytes = lib.liso_bn_multi_workspace_bytes(tab, len(Cs), len(views))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=xv.device)
-    riding = [j for j in jobs if j is not None and not j.done][:2]
-    (ga, gsa), (gb_, gsb) = views[0], (views[1] if len(views) == 2 else (None, 0))
-    units = (3 + 2 * len(views)) * M * Ct * xv.element_size()
+    pre = _bn_backward_prelude(gs, x_raw, fold.groups, table)
+    if pre is None:
+        return None
+    ((xv, xs), (ga, gsa), *second), targets, tab, ws = pre
+    gb, gsb = second[0] if second else (None, 0)
+    M, Ct = xv.numel() // xv.shape[3], xv.shape[3]
+    dxv = torch.empty(xv.shape, dtype=xv.dtype, device=xv.device)
+    riding = [j for j in jobs if not j.done][:2]
     with torch.cuda.device(xv.device):
-        L.check(L.TIMER.launch("bn_bwd", lambda: lib.liso_bn_relu_bwd_multi(
-            L.ptr(ga), gsa, L.ptr(gb_) if gb_ is not None else None, gsb, L.ptr(xv), xs, L.elem_code(xv.dtype), M, tab, len(Cs),
-            int(fold.training), int(fold.relu), L.ptr(dxv), Ct, L.ptr(ws), nbytes, riding[0].ride() if len(riding) > 0 else None,
-            riding[1].ride() if len(riding) > 1 else None, L.stream_ptr()), units=units), "bn_relu_bwd_multi")
-    return dxv.permute(0, 3, 1, 2), grads
+        L.check(L.TIMER.launch("bn_bwd", lambda: L.lib().liso_bn_relu_bwd_multi(
+            L.ptr(ga), gsa, L.ptr(gb) if gb is not None else None, gsb, L.ptr(xv), xs, L.elem_code(xv.dtype), M, tab, len(Cs),
+            int(fold.training), int(fold.relu), L.ptr(dxv), Ct, L.ptr(ws), ws.numel(), *[j.ride() for j in riding], *[None] * (2 - len(riding)),
+            L.stream_ptr()), units=(3 + 2 * len(gs)) * M * Ct * xv.element_size()), "bn_relu_bwd_multi")
+    return dxv.permute(0, 3, 1, 2), [None if direct else t for gg, gb_, direct in targets for t in (gg, gb_)]
+
+
+def _bn_backward(gs, x_raw, fold, jobs=(), out=None, shared=False):
+    """gradient through relu?(bn(x_raw)) of `fold` given the gradients `gs` of its output (a list: one per consumer of x_raw)
+    -> (dx_raw logical NCHW, summed over the gradients, [dgamma0, dbeta0, dgamma1, dbeta1, ...]).  The one place that picks the call:
+      the grouped call       a `shared` fold (shared_fold's node) with one or two gradients; several groups of more than 256 channels
+                             together (the deblocks' 3 x 128-channel concatenation) while the joint backward is switched on
+      one pass per gradient  more gradients than that, or layouts the grouped call does not read in place: the results added
+      the single call        one group (`out`: see _bn_backward_group); several groups of more than 256 channels, one call per group on its
+                             channel slices of g / x_raw and of ONE input-gradient tensor; several groups of at most 256 channels, ONE
+                             call over all channels on the groups' merged or concatenated gamma / statistics (BatchNorm is per channel)
+    `jobs`: WgradReduceJobs (None entries skipped); those not done yet ride in the finalize launches issued here, in order."""
+    jobs = [j for j in jobs if j is not None]
+    Cs = [grp["gamma"].shape[0] for grp in fold.groups]
+    assert out is None or (len(gs), len(Cs)) == (1, 1)
+    if len(gs) <= 2 and (shared or (len(Cs) > 1 and sum(Cs) > 256 and _JOINT_BN_BACKWARD)):
+        res = _bn_backward_grouped(gs, x_raw, fold, jobs)
+        if res is not None:
+            return res
+    if len(gs) > 1:
+        dx, grads = None, [None] * (2 * len(Cs))
+        for g in gs:
+            d, gr = _bn_backward([g], x_raw, fold, jobs)
+            dx = d if dx is None else dx + d
+            grads = [b if a is None else (a if b is None else a + b) for a, b in zip(grads, gr)]
+        return dx, grads
+    g, job = gs[0], next((j for j in jobs if not j.done), None)
+    if len(Cs) == 1:
+        dx, gg, gb = _bn_backward_group(g, x_raw, fold.groups[0], fold.relu, fold.training, out=out, job=job)
+        return dx, [gg, gb]
+    if sum(Cs) > 256:  # (the BatchNorm kernels take up to 256 channels per call)
+        B, _, H, W = x_raw.shape
+        dx_full = torch.empty((B, H, W, sum(Cs)), dtype=x_raw.dtype, device=x_raw.device).permute(0, 3, 1, 2)
+        grads, a = [], 0
+        for k, C in enumerate(Cs):
+            dx, gr = _bn_backward([g[:, a:a + C]], x_raw[:, a:a + C], fold.group(k), jobs, out=dx_full[:, a:a + C])
+            if dx.data_ptr() != dx_full[:, a:a + C].data_ptr():  # (irregular layout: the group wrote a tensor of its own)
+                dx_full[:, a:a + C].copy_(dx)
+            grads += gr
+            a += C
+        return dx_full, grads
+    if fold.merged is not None:  # (written by the groups' finalize launches in the forward pass)
+        buf, total = fold.merged
+        gam, stats = buf[4 * total:], buf[:4 * total]
+    else:
+        gam = torch.cat([grp["gamma"].detach() for grp in fold.groups])
+        stats = torch.cat([grp["stats"][k * c:(k + 1) * c] for k in range(4) for grp, c in zip(fold.groups, Cs)])  # scale | shift | mean | invstd
+    dx, gg, gb = _bn_backward_group(g, x_raw, {"gamma": gam, "beta": None, "stats": stats}, fold.relu, fold.training, job=job)
+    grads, a = [], 0
+    for c in Cs:
+        grads += [gg[a:a + c], gb[a:a + c]]
+        a += c
+    return dx, grads
 
 
 class _SharedFold(torch.autograd.Function):
@@ -946,21 +986,12 @@ class _SharedFold(torch.autograd.Function):
         fold, jobs = ctx.node["fold"], ctx.node["jobs"]
         gs = [g for g in gs if g is not None]
         try:
-            if not gs:
-                return (None, None, None) + (None,) * ctx.n_fold_params
-            res = _bn_backward_multi(gs, x_raw, fold, jobs) if len(gs) <= 2 else None
-            if res is None:  # (a layout the grouped call does not read in place: one backward per gradient, added)
-                dx, grads = None, [None] * ctx.n_fold_params
-                for g in gs:
-                    d, gr = _bn_backward(g, x_raw, fold, next((j for j in jobs if not j.done), None))
-                    dx = d if dx is None else dx + d
-                    grads = [b if a is None else (a if b is None else a + b) for a, b in zip(grads, gr)]
-                res = dx, grads
+            dx, grads = _bn_backward(gs, x_raw, fold, jobs, shared=True) if gs else (None, [None] * ctx.n_fold_params)
         finally:
             for j in jobs:
                 j.flush()  # (no finalize launch took it: the plain reduction)
             jobs.clear()
-        return (res[0], None, None, *res[1])
+        return (dx, None, None, *grads)
 
 
 def shared_fold(x_raw, fold, n=2):
@@ -970,7 +1001,7 @@ def shared_fold(x_raw, fold, n=2):
     map written) instead of once per consumer with autograd adding the results; the consumers' deferred weight-gradient reductions ride
     in its finalize launch.  None where the joint backward does not apply (switched off, no gradient wanted, an eval-mode fold, a layout
     the kernels do not read in place): the caller hands x_raw and fold to every consumer as before."""
-    vec = 8 if L.is_half(x_raw.dtype) else 4
+    vec = L.lane_channels(x_raw.dtype)
     if (not _JOINT_BN_BACKWARD or fold is None or not fold.training or fold.deferred is not None or not torch.is_grad_enabled()
             or not x_raw.requires_grad or not x_raw.is_cuda or _rows_view(x_raw, vec)[0] is None
             or bn_group_table([g["gamma"].shape[0] for g in fold.groups], vec) is None):
@@ -980,47 +1011,6 @@ def shared_fold(x_raw, fold, n=2):
     held = BnFold(fold.groups, fold.relu, fold.training)
     held._ss, held.merged, held.deferred = fold.scale_shift(), fold.merged, node
     return list(outs), held
-
-
-def _bn_backward(g, x_raw, fold, job=None):
-    """-> (dx_raw logical NCHW, [dgamma0, dbeta0, dgamma1, dbeta1, ...]); `job`: see _bn_backward_group (the first group's call takes it)"""
-    if len(fold.groups) == 1:
-        dx, gg, gb = _bn_backward_group(g, x_raw, fold.groups[0], fold.relu, fold.training, job=job)
-        return dx, [gg, gb]
-    # several BatchNorms over consecutive channel ranges of one raw tensor (the deblocks' concatenation in front of the head's shared
-    # convolution, the four heads' hidden maps): BatchNorm is per channel, so ONE backward over all channels with the groups'
-    # gamma / statistics concatenated (two small launches) replaces a slice copy of x and g, three kernels per group and the
-    # concatenation of the partial results; the per-group parameter gradients are slices of its two output vectors
-    Cs = [grp["gamma"].shape[0] for grp in fold.groups]
-    if sum(Cs) > 256:  # (the BatchNorm kernels take up to 256 channels per call: e.g. the deblocks' 3 x 128-channel concatenation)
-        # every group reads its channel slice of g / x_raw in place and writes its slice of ONE input-gradient tensor: no slice
-        # copies, no concatenation -- in one grouped call (three launches for all groups) where the layouts allow
-        res = _bn_backward_multi([g], x_raw, fold, [job]) if _JOINT_BN_BACKWARD else None
-        if res is not None:
-            return res
-        B, _, H, W = x_raw.shape
-        dx_full = torch.empty((B, H, W, sum(Cs)), dtype=x_raw.dtype, device=x_raw.device).permute(0, 3, 1, 2)
-        grads, a = [], 0
-        for grp in fold.groups:
-            C = grp["gamma"].shape[0]
-            dx, gg, gb = _bn_backward_group(g[:, a:a + C], x_raw[:, a:a + C], grp, fold.relu, fold.training, out=dx_full[:, a:a + C], job=job)
-            if dx.data_ptr() != dx_full[:, a:a + C].data_ptr():  # (irregular layout: the group wrote a tensor of its own)
-                dx_full[:, a:a + C].copy_(dx)
-            grads += [gg, gb]
-            a += C
-        return dx_full, grads
-    if fold.merged is not None:  # (written by the groups' finalize launches in the forward pass)
-        buf, total = fold.merged
-        gam, stats = buf[4 * total:], buf[:4 * total]
-    else:
-        gam = torch.cat([grp["gamma"].detach() for grp in fold.groups])
-        stats = torch.cat([grp["stats"][k * c:(k + 1) * c] for k in range(4) for grp, c in zip(fold.groups, Cs)])  # scale | shift | mean | invstd
-    dx, gg, gb = _bn_backward_group(g, x_raw, {"gamma": gam, "beta": None, "stats": stats}, fold.relu, fold.training, job=job)
-    grads, a = [], 0
-    for c in Cs:
-        grads += [gg[a:a + c], gb[a:a + c]]
-        a += c
-    return dx, grads
 
 
 class _FusedConv(torch.autograd.Function):
@@ -1109,7 +1099,7 @@ class _FusedConv(torch.autograd.Function):
                         fold.deferred["jobs"].append(job)
                         job = None
                 elif fold is not None:
-                    dx, fold_grads = _bn_backward(g, x_raw, fold, job)
+                    dx, fold_grads = _bn_backward([g], x_raw, fold, [job])
                 else:
                     dx = g
         finally:
@@ -1519,7 +1509,7 @@ class _Materialize(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (x_raw,) = ctx.saved_tensors
-        dx, grads = _bn_backward(g, x_raw, ctx.fold)
+        dx, grads = _bn_backward([g], x_raw, ctx.fold)
         return (dx, None, *grads)
 
 
@@ -1582,7 +1572,7 @@ def conv2d(layer, x, relu=False, occupancy=None, out=None):
     if x.is_cuda and not spec.transposed:
         # 1-3 (7) input channels -- the motion encoder's conv_flow1: 7x7 on the 2-channel flow, liso/slim/model/update.py:53-60 --
         # the kernels read channels in 16-B groups: zero channels (and zero filter slices) up to one group, then the own kernel
-        vec = 8 if L.is_half(x.dtype) else 4
+        vec = L.lane_channels(x.dtype)
         pad = (-x.shape[1]) % vec
         xp = torch.nn.functional.pad(x.permute(0, 2, 3, 1), (0, pad)).permute(0, 3, 1, 2)  # one launch: dense NHWC rows of one 16-B group
         if torch.is_grad_enabled() and layer.weight.requires_grad:

@@ -3,6 +3,7 @@ over 50 calls after warm-up, at the detector step's sites (B = 2, bf16):
   block 0 output   64 ch @ 256 x 256, two gradients: 2 x liso_bn_relu_bwd + add of the dx maps + adds of dgamma / dbeta
   block 1 output  128 ch @ 128 x 128, two gradients: the same
   concatenation   3 x 128 ch @ 256 x 256, one gradient: 3 x liso_bn_relu_bwd_strided
+  single map      64 ch @ 256 x 256, one gradient: the single call (one group, one gradient) next to the grouped call on the same map
 python scripts/bn_joint_time.py [B]"""
 import os
 import sys
@@ -84,3 +85,4 @@ def site(name, cs, hw, n_grads):
 site("block 0 output", [64], 256, 2)
 site("block 1 output", [128], 128, 2)
 site("concatenation", [128, 128, 128], 256, 1)
+site("single map", [64], 256, 1)

@@ -110,9 +110,52 @@ def test_instance_norm_relu_matches_fp64_module(C, H, W, B, affine, relu, dtype)
         assert _rel(norm.weight.grad, ref.weight.grad) < tb and _rel(norm.bias.grad, ref.bias.grad) < tb
 
 
+@pytest.mark.parametrize("relu", [1, 0], ids=["relu", "linear"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_instance_norm_backward_equals_per_sample_batchnorm_backward_bitwise(dtype, relu):
+    """liso_in_relu_bwd on G = 3 samples == G calls of liso_bn_relu_bwd (training = 1) on each sample's rows and statistics, bit for bit
+    in dx and in the [G, C] parameter gradients; liso_in_relu_bwd_sum writes the same dx bits and the fp64 sum of the per-sample parameter
+    gradients (at most 4 floats: exact in fp64, rounded once).  C = one 16-byte lane, 96 (24 / 12 lanes per row: idle threads in the
+    block), 256; m = 37 (row lanes left idle) and 261 (three 128-row blocks, a ragged last one).  dx sits between guard bands."""
+    from liso_amd import _lib as L
+    from tests.test_gpu_bn_multi import Guarded, _same
+
+    lib, dev, G, code = L.lib(), torch.device("cuda"), 3, L.elem_code(dtype)
+    torch.manual_seed(21)
+    for C in (4 if dtype == torch.float32 else 8, 96, 256):
+        for m in (37, 261):
+            tag = (str(dtype), relu, C, m)
+            x = (torch.randn(G, m, C, device=dev) * 0.5 + 0.1).to(dtype)
+            dy = torch.randn(G, m, C, device=dev).to(dtype)
+            gamma, beta = torch.rand(C, device=dev) + 0.5, torch.randn(C, device=dev) * 0.1
+            xf = x.float()
+            mean, invstd = xf.mean(dim=1), (xf.var(dim=1, unbiased=False) + 1e-3).rsqrt()
+            stats = torch.cat([gamma * invstd, beta - mean * gamma * invstd, mean, invstd], dim=1).contiguous()  # [G, 4C]
+            ref_dx = torch.empty_like(x)
+            ref_gg, ref_gb = torch.empty(G, C, device=dev), torch.empty(G, C, device=dev)
+            nb = lib.liso_bn_workspace_bytes(C)
+            ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            for s in range(G):
+                L.check(lib.liso_bn_relu_bwd(L.ptr(dy[s]), L.ptr(x[s]), code, m, C, L.ptr(gamma), L.ptr(stats[s]), 1, relu, L.ptr(ref_dx[s]),
+                                             L.ptr(ref_gg[s]), L.ptr(ref_gb[s]), L.ptr(ws), nb, L.stream_ptr()), "bn_relu_bwd")
+            nbytes = lib.liso_in_workspace_bytes(G, C)
+            wsg = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            for fn, rows in ((lib.liso_in_relu_bwd, G), (lib.liso_in_relu_bwd_sum, 1)):
+                dx, gg, gb = Guarded(G * m * C, dtype, dev), Guarded(rows * C, torch.float32, dev), Guarded(rows * C, torch.float32, dev)
+                L.check(fn(L.ptr(dy), L.ptr(x), code, G, m, C, L.ptr(gamma), L.ptr(stats), relu, L.ptr(dx.inner), L.ptr(gg.inner),
+                           L.ptr(gb.inner), L.ptr(wsg), nbytes, L.stream_ptr()), "in_relu_bwd")
+                torch.cuda.synchronize()
+                assert dx.intact() and gg.intact() and gb.intact(), ("guard band overwritten", rows, tag)
+                assert _same(ref_dx, dx.inner.view(G, m, C)), ("dx", rows, tag)
+                want_gg = ref_gg if rows == G else ref_gg.double().sum(0).float()[None]
+                want_gb = ref_gb if rows == G else ref_gb.double().sum(0).float()[None]
+                assert _same(want_gg, gg.inner.view(rows, C)), ("grad_gamma", rows, tag)
+                assert _same(want_gb, gb.inner.view(rows, C)), ("grad_beta", rows, tag)
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32, torch.float16])
 def test_bn_backward_on_channel_slices_equals_the_dense_call(dtype):
-    """liso_bn_relu_bwd_strided: the BatchNorms behind a channel concatenation (3 x 128 channels in front of the detector's head) read
+    """the single call on row strides (liso_bn_relu_bwd_chained, job = NULL): the BatchNorms behind a channel concatenation (3 x 128 channels in front of the detector's head) read
     their slices of g / x and write their slice of dx in place: same dx / dgamma / dbeta as the call on contiguous copies of the slices,
     bit for bit (same kernels, other row strides), and nothing outside the slice is touched"""
     if dtype == torch.float16:
