@@ -52,4 +52,15 @@ def install_as(name="liso", iou3d_name="iou3d_nms"):
     sys.modules.setdefault("iou3d_nms_cuda", importlib.import_module(__name__ + ".iou3d_nms_cuda"))
     sys.modules.setdefault(iou3d_name, importlib.import_module(__name__ + ".iou3d_nms"))
     sys.modules.setdefault(iou3d_name + ".iou3d_nms_utils", importlib.import_module(__name__ + ".iou3d_nms.iou3d_nms_utils"))
+    # the dataset builders' odometry (`from kiss_icp.config import KISSConfig`, `from kiss_icp.kiss_icp import KissICP`): this
+    # package's, unless a real kiss_icp can be imported
+    import importlib.util
+    import types
+
+    if "kiss_icp" not in sys.modules and importlib.util.find_spec("kiss_icp") is None:
+        pkg = types.ModuleType("kiss_icp")
+        pkg.__path__, pkg.__liso_amd_alias__ = [], True
+        pkg.config = importlib.import_module(__name__ + ".odometry.config")
+        pkg.kiss_icp = importlib.import_module(__name__ + ".odometry.kiss_icp")
+        sys.modules["kiss_icp"], sys.modules["kiss_icp.config"], sys.modules["kiss_icp.kiss_icp"] = pkg, pkg.config, pkg.kiss_icp
     return me

@@ -351,6 +351,15 @@ SIGNATURES = {
     # include/liso_frame_prep.h
     "liso_frame_prep_workspace_bytes": (_sz, [_vp]),
     "liso_prepare_tracker_frames": (_i, [_vp] * 27 + [_sz, _vp]),
+    # include/liso_odometry.h
+    "liso_odometry_workspace_bytes": (_sz, [_vp]),
+    "liso_odometry_workspace_layout": (_i, [_vp, _vp]),
+    "liso_odometry_preprocess": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "liso_odometry_register": (_i, [_vp, _i] + [_vp] * 8 + [_sz, _vp]),
+    "liso_odometry_map_update": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "liso_odometry_sequences": (_i, [_vp] * 11 + [_sz, _vp]),
+    "liso_odometry_relative_f64": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "liso_correct_kitti_scan_f64": (_i, [_lg, _vp, _vp, _vp]),
 }
 
 
@@ -472,6 +481,13 @@ class FramePrepCfg(ctypes.Structure):
     _fields_ = [("n_seq", _i), ("max_frames", _i), ("max_box", _i), ("cap", _i), ("n_points", ctypes.c_long), ("point_stride", _i),
                 ("n_fov_points", ctypes.c_long), ("fov_stride", _i), ("bev_range_x", _f), ("bev_range_y", _f), ("drop_on_bev_boundaries", _i),
                 ("min_points_in_box", _i), ("fov_min_points", _i), ("align", _i), ("no_align_below_m", _d), ("full_align_above_m", _d)]
+
+
+class OdometryCfg(ctypes.Structure):
+    """mirror of liso_odometry_cfg (include/liso_odometry.h)"""
+    _fields_ = [("n_seq", _i), ("max_frames", _i), ("n_max", _i), ("point_stride", _i), ("map_voxels", _i), ("max_points_per_voxel", _i),
+                ("max_num_iterations", _i), ("max_range", _d), ("min_range", _d), ("voxel_size", _d), ("initial_threshold", _d),
+                ("min_motion_th", _d), ("convergence_criterion", _d)]
 
 
 class GruCfg(ctypes.Structure):
