@@ -312,6 +312,11 @@ SIGNATURES = {
     "liso_det_nms_order": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
     "liso_det_nms_select": (_i, [_i, _i, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp]),
     "liso_det_nms_gather": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    # include/liso_det_val.h
+    "liso_det_val_pairs_f32": (_i, [_i, _i, _i] + [_vp] * 8),
+    "liso_det_val_pairs_cpu_f32": (_i, [_i, _i, _i] + [_vp] * 7),
+    "liso_det_val_transfer_classes": (_i, [_i, _i, _i] + [_vp] * 5 + [_f, _vp, _vp, _vp]),
+    "liso_det_val_match_f32": (_i, [_i, _i, _i] + [_vp] * 10 + [_i, _vp, _i, _vp, _i] + [_vp] * 6),
     # include/liso_ground.h
     "liso_ground_jcp_workspace_bytes": (_sz, [_vp]),
     "liso_ground_jcp_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1,0 +1,410 @@
+// Detector validation matching for gfx950 (MI355X), C ABI in include/liso_det_val.h: the pair matrices of every frame of a padded
+// batch in one launch, run_val's class transfer in one launch, and every (job, frame) matching in one launch.
+//
+// The work per matching is tiny (tens of boxes) and there are thousands of them per validation batch, so the shape is: one
+// wavefront per (job, frame) cell, the serial walk over the predictions kept short --
+//   * a lane owns the ground-truth slots lane, lane+64, ...: "in the filter set and not yet taken" is one bit per owned slot in
+//     a register, so the walk touches no memory but the prediction's row of the pair matrix;
+//   * the prediction order and the predictions' membership are staged in LDS once per cell;
+//   * a prediction with no value past the threshold (most of them) costs one ballot; otherwise the best candidate is a 64-bit
+//     key maximum over the wave: (order-preserving bits of the value, ~slot) -- largest value, lowest slot on ties, as
+//     liso_match_greedy_f32;
+//   * the matched pairs stay in LDS during the walk; the true-positive error terms are evaluated afterwards, one lane per
+//     match, and added in match order in fp64.
+// The pair geometry is rbev_geom.h's (shared with iou3d_nms.hip and det_nms.hip), so the BEV numbers equal
+// liso_iou3d_*_f32 bit for bit.  Built with -ffp-contract=off: every expression the header states is evaluated operation by
+// operation.
+#include <hip/hip_runtime.h>
+#include "dev_common.h"
+#include "rbev_geom.h"
+#include "rbev_geom_host.h"
+#include <float.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/liso_det_val.h"
+
+namespace {
+
+using liso_dev::check_launch;
+using namespace liso_rbev;
+
+constexpr int kCols = 64;      // ground-truth slots per tile == wavefront width
+constexpr int kRows = 16;      // prediction slots per tile
+constexpr int kThreads = 256;  // 4 waves, each owns kRows/4 rows
+constexpr int kMaxBoxes = LISO_DET_VAL_MAX_BOXES;
+constexpr int kOwned = kMaxBoxes / 64;  // ground-truth slots a lane owns in the walk
+static_assert(kThreads == kPolyThreads, "PolyLds holds one column per thread");
+static_assert(kOwned <= 32, "one bit per owned slot in a 32-bit register");
+
+// torch.min / torch.max, np.minimum: NaN if either operand is NaN
+__host__ __device__ inline float nan_min(float a, float b) { return (a != a || b != b) ? NAN : (a < b ? a : b); }
+__host__ __device__ inline float nan_max(float a, float b) { return (a != a || b != b) ? NAN : (a > b ? a : b); }
+
+// the header's 3-D IoU from the BEV overlap; area = dx*dy of each box
+__host__ __device__ inline float iou3d_from_overlap(float ov, float gz, float gdz, float garea, float pz, float pdz, float parea) {
+    const float lo_g = gz - 0.5f * gdz, hi_g = gz + 0.5f * gdz;
+    const float lo_p = pz - 0.5f * pdz, hi_p = pz + 0.5f * pdz;
+    const float h = nan_min(hi_g, hi_p) - nan_max(lo_g, lo_p);
+    const float inter = h > 0.f ? ov * h : 0.f;
+    const float uni = garea * gdz + parea * pdz - inter;
+    const float den = uni < FLT_EPSILON ? FLT_EPSILON : uni;  // NaN stays NaN
+    return inter / den;
+}
+
+__host__ __device__ inline float centre_dist(const float* g, const float* p) {
+    const float dx = g[0] - p[0], dy = g[1] - p[1];
+    return sqrtf(dx * dx + dy * dy);
+}
+
+__host__ __device__ inline bool in_set(const float* b, uint8_t valid, int cls, const liso_det_val_filter& f) {
+    if (!valid) return false;
+    const float x = b[0], y = b[1];
+    if (f.use_area && !(f.area_min_x <= x && x <= f.area_max_x && f.area_min_y <= y && y <= f.area_max_y)) return false;
+    if (f.use_range) {
+        const float r = sqrtf(x * x + y * y);
+        if (!(f.range_min <= r && r < f.range_max)) return false;
+    }
+    if (f.class_id >= 0 && cls != f.class_id) return false;
+    return true;
+}
+
+struct PairLds {
+    float col[G_N][kCols];  // ground truth
+    float row[G_N][kCols];  // predictions; only kRows used, same shape keeps one load_geo
+    PolyLds poly;
+};
+
+__global__ __launch_bounds__(kThreads) void pairs_kernel(int G, int P, const float* __restrict__ gt,
+                                                          const uint8_t* __restrict__ gv, const float* __restrict__ pred,
+                                                          const uint8_t* __restrict__ pv, float* __restrict__ o_bev,
+                                                          float* __restrict__ o_3d, float* __restrict__ o_dist) {
+    __shared__ PairLds L;
+    const int f = blockIdx.z, c0 = blockIdx.x * kCols, r0 = blockIdx.y * kRows;
+    gt += (size_t)f * G * 7;
+    gv += (size_t)f * G;
+    pred += (size_t)f * P * 7;
+    pv += (size_t)f * P;
+    const int t = threadIdx.x;
+    const bool want_overlap = o_bev != nullptr || o_3d != nullptr;
+    if (want_overlap) {
+        if (t < kCols) {
+            const int g = c0 + t;
+            if (g < G && gv[g]) store_geo(L.col, t, make_geo(gt + (size_t)g * 7));
+        } else if (t < kCols + kRows) {
+            const int p = r0 + (t - kCols);
+            if (p < P && pv[p]) store_geo(L.row, t - kCols, make_geo(pred + (size_t)p * 7));
+        }
+    }
+    __syncthreads();
+    const int lane = t & 63, wave = t >> 6;
+    const int g = c0 + lane;
+    if (g >= G) return;
+    const bool g_ok = gv[g] != 0;
+    const float* gb = gt + (size_t)g * 7;
+    Geo A;
+    if (g_ok && want_overlap) A = load_geo(L.col, lane);
+#pragma unroll 1
+    for (int rr = wave; rr < kRows; rr += kThreads / 64) {
+        const int p = r0 + rr;
+        if (p >= P) break;
+        float bev = 0.f, i3d = 0.f, d = 0.f;
+        if (g_ok && pv[p]) {
+            const float* pb = pred + (size_t)p * 7;
+            if (want_overlap) {
+                const Geo B = load_geo(L.row, rr);
+                const float ov = box_overlap_dev(A, B, &L.poly, t);
+                bev = iou_from_overlap(A, B, ov);
+                i3d = iou3d_from_overlap(ov, gb[2], gb[5], A.area, pb[2], pb[5], B.area);
+            }
+            d = centre_dist(gb, pb);
+        }
+        const size_t o = ((size_t)f * P + p) * G + g;
+        if (o_bev) o_bev[o] = bev;
+        if (o_3d) o_3d[o] = i3d;
+        if (o_dist) o_dist[o] = d;
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned int lo = (unsigned int)__shfl_xor((int)(unsigned int)v, m);
+        const unsigned int hi = (unsigned int)__shfl_xor((int)(unsigned int)(v >> 32), m);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// The greedy walk of one wavefront.  val: the frame's [P,G] matrix; s_order / s_pin: the prediction order and the predictions'
+// membership, in LDS; avail: bit r = ground-truth slot lane + 64 r is in the set and free.  on_match(m, g, p) runs on every lane
+// with the same arguments.  Returns the number of matches.
+template <class OnMatch>
+__device__ __forceinline__ int greedy_walk(const float* __restrict__ val, bool smaller_wins, float thr, int G, int P,
+                                           const int* s_order, const uint8_t* s_pin, uint32_t avail, OnMatch on_match) {
+    const int lane = threadIdx.x & 63;
+    const float sgn = smaller_wins ? -1.f : 1.f;  // "smallest distance below thr" == "largest -distance above -thr", exactly
+    const float t = sgn * thr;
+    int m = 0;
+    for (int k = 0; k < P; ++k) {
+        const int p = s_order[k];
+        if (p < 0 || p >= P || !s_pin[p]) continue;
+        const float* row = val + (size_t)p * G;
+        unsigned long long key = 0;
+        uint32_t a = avail;
+        for (int r = 0; a != 0u; ++r, a >>= 1) {
+            if (!(a & 1u)) continue;
+            const int g = lane + 64 * r;
+            const float v = sgn * row[g];
+            if (v > t) {  // NaN never passes
+                const uint32_t u = __float_as_uint(v);
+                const unsigned long long kk =
+                    ((unsigned long long)(u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u)) << 32) | (0xFFFFFFFFu - (uint32_t)g);
+                key = kk > key ? kk : key;
+            }
+        }
+        if (__ballot(key != 0ull) == 0ull) continue;
+        const unsigned long long top = wave_max_u64(key);
+        const int bi = (int)(0xFFFFFFFFu - (uint32_t)top);
+        if ((bi & 63) == lane) avail &= ~(1u << (bi >> 6));
+        on_match(m, bi, p);
+        ++m;
+    }
+    return m;
+}
+
+// the three true-positive error terms of one match (header), fp32
+__host__ __device__ inline void tp_terms(const float* g, const float* p, float& ate, float& ase, float& aoe) {
+    ate = centre_dist(g, p);
+    const float inter = nan_min(g[3], p[3]) * nan_min(g[4], p[4]) * nan_min(g[5], p[5]);
+    const float uni = g[3] * g[4] * g[5] + p[3] * p[4] * p[5] - inter;
+    const float den = uni < 1e-6f ? 1e-6f : uni;
+    ase = 1.0f - inter / den;
+    const float pi = 3.14159265358979323846f, two_pi = (float)(2.0 * 3.14159265358979323846);
+    float r = fmodf(g[6] - p[6] + pi, two_pi);
+    if (r != 0.f) {
+        if (r < 0.f) r = r + two_pi;
+    } else {
+        r = 0.f;
+    }
+    float d = r - pi;
+    if (d > pi) d = d - two_pi;
+    aoe = fabsf(d);
+}
+
+struct MatchArgs {
+    int G, P, S, J, M;
+    const float* gt;
+    const uint8_t* gv;
+    const int32_t* gc;
+    const float* pred;
+    const uint8_t* pv;
+    const int32_t* pc;
+    const int32_t* order;
+    const float* mat[3];
+    const liso_det_val_filter* filters;
+    const liso_det_val_job* jobs;
+    int32_t* count;
+    int16_t* pairs;
+    double* sums;
+    uint8_t* gt_in;
+    uint8_t* pred_in;
+};
+
+__global__ __launch_bounds__(64) void match_kernel(MatchArgs a) {
+    __shared__ int s_order[kMaxBoxes];
+    __shared__ int s_pair[kMaxBoxes];  // (gt slot << 16) | pred slot
+    __shared__ uint8_t s_pin[kMaxBoxes];
+    const int lane = threadIdx.x;
+    const size_t cell = blockIdx.x;
+    const int f = (int)(cell / (size_t)a.J), j = (int)(cell - (size_t)f * a.J);
+    const int G = a.G, P = a.P, M = a.M;
+    const liso_det_val_job job = a.jobs[j];
+    int16_t* pairs = a.pairs + cell * (size_t)M * 2;
+    int m = 0;
+    double ate = 0.0, ase = 0.0, aoe = 0.0;
+    const bool ok = job.filter >= 0 && job.filter < a.S && job.criterion >= 0 && job.criterion <= 2;
+    if (ok) {
+        const liso_det_val_filter fl = a.filters[job.filter];
+        const float* gt = a.gt + (size_t)f * G * 7;
+        const float* pred = a.pred + (size_t)f * P * 7;
+        uint32_t avail = 0u;
+        for (int r = 0; r < kOwned; ++r) {
+            const int g = lane + 64 * r;
+            if (g >= G) break;
+            const size_t s = (size_t)f * G + g;
+            const bool in = in_set(gt + (size_t)g * 7, a.gv[s], a.gc[s], fl);
+            a.gt_in[((size_t)f * a.S + job.filter) * G + g] = in ? 1 : 0;
+            if (in) avail |= 1u << r;
+        }
+        for (int p = lane; p < P; p += 64) {
+            const size_t s = (size_t)f * P + p;
+            const bool in = in_set(pred + (size_t)p * 7, a.pv[s], a.pc[s], fl);
+            a.pred_in[((size_t)f * a.S + job.filter) * P + p] = in ? 1 : 0;
+            s_pin[p] = in ? 1 : 0;
+            s_order[p] = a.order[s];
+        }
+        __syncthreads();
+        if (G > 0 && P > 0) {
+            const float* val = a.mat[job.criterion] + (size_t)f * P * G;
+            m = greedy_walk(val, job.criterion == LISO_DET_VAL_DIST, job.threshold, G, P, s_order, s_pin, avail,
+                            [&](int i, int g, int p) {
+                                if (lane == 0 && i < M) s_pair[i] = (g << 16) | p;
+                            });
+            if (m > M) m = M;  // (only an `order` that names a slot twice gets here)
+        }
+        __syncthreads();
+        for (int base = 0; base < m; base += 64) {
+            const int i = base + lane;
+            float ta = 0.f, ts = 0.f, to = 0.f;
+            if (i < m) {
+                const int g = s_pair[i] >> 16, p = s_pair[i] & 0xFFFF;
+                pairs[2 * i] = (int16_t)g;
+                pairs[2 * i + 1] = (int16_t)p;
+                tp_terms(gt + (size_t)g * 7, pred + (size_t)p * 7, ta, ts, to);
+            }
+            const int n = m - base < 64 ? m - base : 64;
+            for (int q = 0; q < n; ++q) {  // match order, every lane the same sum
+                ate += (double)__shfl(ta, q);
+                ase += (double)__shfl(ts, q);
+                aoe += (double)__shfl(to, q);
+            }
+        }
+    }
+    for (int i = m + lane; i < M; i += 64) {
+        pairs[2 * i] = -1;
+        pairs[2 * i + 1] = -1;
+    }
+    if (lane == 0) {
+        a.count[cell] = m;
+        a.sums[cell * 3] = ate;
+        a.sums[cell * 3 + 1] = ase;
+        a.sums[cell * 3 + 2] = aoe;
+    }
+}
+
+__global__ __launch_bounds__(64) void transfer_kernel(int G, int P, const uint8_t* __restrict__ gv,
+                                                       const int32_t* __restrict__ gc, const uint8_t* __restrict__ pv,
+                                                       const int32_t* __restrict__ order, const float* __restrict__ dist,
+                                                       float thr, const int32_t* __restrict__ draws,
+                                                       int32_t* __restrict__ out) {
+    __shared__ int s_order[kMaxBoxes];
+    __shared__ int s_cls[kMaxBoxes];
+    __shared__ int s_gc[kMaxBoxes];
+    __shared__ uint8_t s_pin[kMaxBoxes];
+    const int lane = threadIdx.x, f = blockIdx.x;
+    uint32_t avail = 0u;
+    for (int r = 0; r < kOwned; ++r) {
+        const int g = lane + 64 * r;
+        if (g >= G) break;
+        const size_t s = (size_t)f * G + g;
+        s_gc[g] = gc[s];
+        if (gv[s]) avail |= 1u << r;
+    }
+    for (int p = lane; p < P; p += 64) {
+        const size_t s = (size_t)f * P + p;
+        const bool in = pv[s] != 0;
+        s_pin[p] = in ? 1 : 0;
+        s_cls[p] = in ? draws[s] : -1;
+        s_order[p] = order[s];
+    }
+    __syncthreads();
+    if (G > 0 && P > 0)
+        greedy_walk(dist + (size_t)f * P * G, true, thr, G, P, s_order, s_pin, avail, [&](int, int g, int p) {
+            if (lane == 0) s_cls[p] = s_gc[g];
+        });
+    __syncthreads();
+    for (int p = lane; p < P; p += 64) out[(size_t)f * P + p] = s_cls[p];
+}
+
+bool bad_shape(int frames, int G, int P) { return frames < 0 || G < 0 || P < 0 || G > kMaxBoxes || P > kMaxBoxes; }
+
+}  // namespace
+
+extern "C" {
+
+int liso_det_val_pairs_f32(int frames, int n_gt, int n_pred, const float* gt, const uint8_t* gt_valid, const float* pred,
+                           const uint8_t* pred_valid, float* iou_bev, float* iou_3d, float* dist, void* stream) {
+    if (bad_shape(frames, n_gt, n_pred)) return LISO_EINVAL;
+    if (frames == 0 || n_gt == 0 || n_pred == 0) return LISO_OK;
+    if (!gt || !gt_valid || !pred || !pred_valid) return LISO_EINVAL;
+    if (!iou_bev && !iou_3d && !dist) return LISO_OK;
+    if (frames > 65535) return LISO_EINVAL;
+    const dim3 grid((n_gt + kCols - 1) / kCols, (n_pred + kRows - 1) / kRows, frames);
+    hipLaunchKernelGGL(pairs_kernel, grid, dim3(kThreads), 0, (hipStream_t)stream, n_gt, n_pred, gt, gt_valid, pred, pred_valid,
+                       iou_bev, iou_3d, dist);
+    return check_launch();
+}
+
+int liso_det_val_pairs_cpu_f32(int frames, int n_gt, int n_pred, const float* gt, const uint8_t* gt_valid, const float* pred,
+                               const uint8_t* pred_valid, float* iou_bev, float* iou_3d, float* dist) {
+    using namespace liso_rbev_host;
+    if (bad_shape(frames, n_gt, n_pred)) return LISO_EINVAL;
+    if (frames == 0 || n_gt == 0 || n_pred == 0) return LISO_OK;
+    if (!gt || !gt_valid || !pred || !pred_valid) return LISO_EINVAL;
+    for (int f = 0; f < frames; ++f)
+        for (int p = 0; p < n_pred; ++p)
+            for (int g = 0; g < n_gt; ++g) {
+                const float* gb = gt + ((size_t)f * n_gt + g) * 7;
+                const float* pb = pred + ((size_t)f * n_pred + p) * 7;
+                float bev = 0.f, i3d = 0.f, d = 0.f;
+                if (gt_valid[(size_t)f * n_gt + g] && pred_valid[(size_t)f * n_pred + p]) {
+                    if (iou_bev || iou_3d) {
+                        const float ov = h_overlap_bev(gb, pb);
+                        bev = h_iou_from_overlap(gb, pb, ov);
+                        i3d = iou3d_from_overlap(ov, gb[2], gb[5], gb[3] * gb[4], pb[2], pb[5], pb[3] * pb[4]);
+                    }
+                    d = centre_dist(gb, pb);
+                }
+                const size_t o = ((size_t)f * n_pred + p) * n_gt + g;
+                if (iou_bev) iou_bev[o] = bev;
+                if (iou_3d) iou_3d[o] = i3d;
+                if (dist) dist[o] = d;
+            }
+    return LISO_OK;
+}
+
+int liso_det_val_transfer_classes(int frames, int n_gt, int n_pred, const uint8_t* gt_valid, const int32_t* gt_class,
+                                  const uint8_t* pred_valid, const int32_t* order, const float* dist, float threshold,
+                                  const int32_t* draws, int32_t* pred_class_out, void* stream) {
+    if (bad_shape(frames, n_gt, n_pred)) return LISO_EINVAL;
+    if (frames == 0 || n_pred == 0) return LISO_OK;
+    if (!pred_valid || !order || !draws || !pred_class_out) return LISO_EINVAL;
+    if (n_gt > 0 && (!gt_valid || !gt_class || !dist)) return LISO_EINVAL;
+    hipLaunchKernelGGL(transfer_kernel, dim3(frames), dim3(64), 0, (hipStream_t)stream, n_gt, n_pred, gt_valid, gt_class,
+                       pred_valid, order, dist, threshold, draws, pred_class_out);
+    return check_launch();
+}
+
+int liso_det_val_match_f32(int frames, int n_gt, int n_pred, const float* gt, const uint8_t* gt_valid, const int32_t* gt_class,
+                           const float* pred, const uint8_t* pred_valid, const int32_t* pred_class, const int32_t* order,
+                           const float* iou_bev, const float* iou_3d, const float* dist, int criteria_mask,
+                           const liso_det_val_filter* filters, int n_filters, const liso_det_val_job* jobs, int n_jobs,
+                           int32_t* count, int16_t* pairs, double* sums, uint8_t* gt_in, uint8_t* pred_in, void* stream) {
+    if (bad_shape(frames, n_gt, n_pred) || n_filters < 0 || n_jobs < 0 || criteria_mask < 0 || criteria_mask > 7) return LISO_EINVAL;
+    if (frames == 0 || n_jobs == 0) return LISO_OK;
+    if (n_filters == 0 || !filters || !jobs || !count || !sums) return LISO_EINVAL;
+    if (n_gt > 0 && (!gt || !gt_valid || !gt_class || !gt_in)) return LISO_EINVAL;
+    if (n_pred > 0 && (!pred || !pred_valid || !pred_class || !order || !pred_in)) return LISO_EINVAL;
+    const int M = n_gt < n_pred ? n_gt : n_pred;
+    if (M > 0) {
+        if (!pairs) return LISO_EINVAL;
+        const float* mats[3] = {iou_bev, iou_3d, dist};
+        for (int c = 0; c < 3; ++c)
+            if (((criteria_mask >> c) & 1) && !mats[c]) return LISO_EINVAL;
+    }
+    if ((long long)frames * n_jobs > 0x7FFFFFFFLL) return LISO_EINVAL;
+    MatchArgs a;
+    a.G = n_gt, a.P = n_pred, a.S = n_filters, a.J = n_jobs, a.M = M;
+    a.gt = gt, a.gv = gt_valid, a.gc = gt_class, a.pred = pred, a.pv = pred_valid, a.pc = pred_class, a.order = order;
+    // a criterion whose bit is not set never reaches its matrix: point it at one that is there so a job that names it reads valid memory
+    const float* any = iou_bev ? iou_bev : (iou_3d ? iou_3d : dist);
+    if (M > 0 && !any) return LISO_EINVAL;
+    a.mat[0] = iou_bev ? iou_bev : any, a.mat[1] = iou_3d ? iou_3d : any, a.mat[2] = dist ? dist : any;
+    a.filters = filters, a.jobs = jobs, a.count = count, a.pairs = pairs, a.sums = sums, a.gt_in = gt_in, a.pred_in = pred_in;
+    hipLaunchKernelGGL(match_kernel, dim3((unsigned)(frames * n_jobs)), dim3(64), 0, (hipStream_t)stream, a);
+    return check_launch();
+}
+
+}  // extern "C"

@@ -192,6 +192,21 @@ class ObjectDetectionMetrics:
             if g.rot is not None and p.rot is not None:
                 e["AOE"] += abs_yaw_diff(np.squeeze(g.rot[idx_gt, ...], axis=-1), np.squeeze(p.rot[idx_pred, ...], axis=-1)).sum()
 
+    def accumulate_matches(self, gt_mask, pred_mask, logits, idx_pred, idx_gt, moving, thr, class_name, tp_error_sums):
+        """Public entry of the book-keeping for a matching done elsewhere (liso_amd/eval/det_validation.py: on the device, for all
+        frames and collections at once): what `_update_class_threshold` does after its matcher returned.  The arguments index the
+        FILTERED, compacted box lists of one frame: gt_mask / moving bool [n_gt], pred_mask bool [n_pred], logits [n_pred], idx_gt /
+        idx_pred the matched pairs in match order; tp_error_sums = (ATE, ASE, AOE) summed over the matches."""
+        assert gt_mask.shape == moving.shape, (gt_mask.shape, moving.shape)
+        for category, ignore in (("moving", ~moving), ("still", moving), ("overall", np.zeros_like(moving))):
+            self._update_category(gt_mask, pred_mask, logits, idx_pred, idx_gt, ignore, thr, category, class_name)
+        n_tp = int(np.count_nonzero(gt_mask))
+        e = self.tp_errors[class_name][thr]
+        e["tps"] += n_tp
+        if n_tp > 0:
+            assert len(idx_gt) == len(idx_pred) == n_tp
+            e["ATE"] += float(tp_error_sums[0]); e["ASE"] += float(tp_error_sums[1]); e["AOE"] += float(tp_error_sums[2])
+
     def _update_category(self, gt_mask, pred_mask, logits, idx_pred, idx_gt, ignore_gt, thr, category, class_name):
         self.label_stats[class_name][thr][category] += int(np.count_nonzero(~ignore_gt))
         ignore_matched = ignore_gt[idx_gt]

@@ -363,6 +363,19 @@ class DetectorTrainer:
     # The graph holds backbone + head + fused loss, forward and backward (~95 % of the step's launches).  The pillar encoder
     # (voxelise + PFN + scatter; 10 launches) runs eagerly around it: its launches carry the raw clouds' lengths as kernel arguments
     # (the history of that rule, and the capture protocol: liso_amd/utils/graph_capture.py).
+    def eval_model(self, val_batches, max_iterations=None, **run_val_args):
+        """The detector's counterpart of `SlimTrainer.eval_model`: liso_amd.eval.eval_ours.run_val over `val_batches` (dictionaries
+        with `pcls`, `gt_boxes`, `benchmark_gt_boxes` and optionally `pcl_full_w_ground`) in eval mode, then the previous mode again.
+        -> the metric dictionary.  No parameter or buffer changes."""
+        from liso_amd.eval.eval_ours import run_val
+
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            return run_val(self.cfg, val_batches, self.net, max_num_steps=max_iterations, **run_val_args)
+        finally:
+            self.net.train(was_training)
+
     def _pillars(self, pcls, out=None, prep=None):
         """`out`: (canvas rows [B, gx, gy, 64], occupancy) to write into -- the graph's static inputs (no copy afterwards)"""
         return self.net.model.pfn(pcl_t0=pcls, img_t0=None, out=out, prep=prep)
