@@ -10,61 +10,6 @@ from liso_amd.networks.centerpoint.rpn import conv_bn_relu
 from liso_amd.networks.centerpoint.weight_init import kaiming_init
 
 
-class _BlockDiagonalFilters(torch.autograd.Function):
-    """The output convolutions of the heads -- same geometry, each on its own 64-channel slice of the merged hidden map -- as ONE
-    convolution: filters [sum co_k, sum ci_k, kh, kw] with head k's filter in its diagonal block and zeros elsewhere, biases
-    concatenated.  One forward, one data-gradient and one weight-gradient launch instead of four of each on 1-3 output channels
-    (launch-bound: 9 + 21 + 28 us per head at B = 4).  Backward: the diagonal blocks of the dense weight gradient."""
-
-    @staticmethod
-    def forward(ctx, n, static, *wb):
-        """`static`: (W, bias) that an optimizer table keeps current (mfma_conv.merged_static) -- then nothing is launched -- or None"""
-        ws, bs = wb[:n], wb[n:]
-        co = [w.shape[0] for w in ws]
-        ci = [w.shape[1] for w in ws]
-        if static is not None:
-            ctx.co, ctx.ci, ctx.device_blocks = co, ci, True
-            return static[0].detach(), static[1].detach()
-        W = ws[0].new_zeros((sum(co), sum(ci)) + tuple(ws[0].shape[2:]))
-        ctx.co, ctx.ci = co, ci
-        ctx.device_blocks = W.is_cuda and W.dtype == torch.float32
-        if ctx.device_blocks:  # every block and bias by one launch (include/liso_optim.h: liso_multi_copy_rows)
-            from liso_amd import _lib as L
-
-            bias = bs[0].new_empty(sum(co))
-            jobs, o, c = [], 0, 0
-            for w, b_, a, b in zip(ws, bs, co, ci):
-                jobs += [(W[o:o + a, c:c + b], w.detach()), (bias[o:o + a], b_.detach())]
-                o, c = o + a, c + b
-            L.copy_blocks(jobs)
-            return W, bias
-        o = c = 0
-        for w, a, b in zip(ws, co, ci):
-            W[o:o + a, c:c + b] = w
-            o, c = o + a, c + b
-        return W, torch.cat(bs)
-
-    @staticmethod
-    def backward(ctx, gW, gb):
-        gws, gbs, o, c = [], [], 0, 0
-        if ctx.device_blocks and gW is not None and gW.dtype == torch.float32:
-            from liso_amd import _lib as L
-
-            jobs = []
-            for a, b in zip(ctx.co, ctx.ci):
-                gws.append(gW.new_empty((a, b) + tuple(gW.shape[2:])))
-                jobs.append((gws[-1], gW[o:o + a, c:c + b]))
-                gbs.append(gb[o:o + a] if gb is not None else None)
-                o, c = o + a, c + b
-            L.copy_blocks(jobs)
-            return (None, None, *gws, *gbs)
-        for a, b in zip(ctx.co, ctx.ci):
-            gws.append(gW[o:o + a, c:c + b].contiguous() if gW is not None else None)
-            gbs.append(gb[o:o + a] if gb is not None else None)
-            o, c = o + a, c + b
-        return (None, None, *gws, *gbs)
-
-
 class SepHead(nn.Module):
     def __init__(self, in_channels, heads, norm_cfg, head_conv=64, final_kernel=1, bn=False, **kwargs):
         super().__init__(**kwargs)
@@ -97,14 +42,11 @@ class SepHead(nn.Module):
         same = all(l.kernel_size == lasts[0].kernel_size and l.stride == lasts[0].stride and l.padding == lasts[0].padding and
                    l.bias is not None for l in lasts)
         if same and getattr(self, "merge_output_convs", True):
-            # the heads' output convolutions as one block-diagonal convolution on the whole hidden map (see _BlockDiagonalFilters);
+            # the heads' output convolutions as one block-diagonal convolution on the whole hidden map (conv_panels.merged_filters);
             # every head reads its channels of the result (a split: its backward is one concatenation of the heads' gradients)
             import types
 
-            static = MC.merged_static("blockdiag", [l.weight for l in lasts])
-            W, b = _BlockDiagonalFilters.apply(len(lasts), static, *[l.weight for l in lasts], *[l.bias for l in lasts])
-            if static is None:
-                MC.note_merged_filter("blockdiag", W, [l.weight for l in lasts], [l.bias for l in lasts])
+            W, b = MC.merged_filters("blockdiag", lasts)
             y, _ = MC.fused_conv(hid, hfold, types.SimpleNamespace(weight=W, bias=b), out_dtype=torch.float32, spec=MC.ConvSpec.of(lasts[0]))
             return dict(zip(self.heads, torch.split(y, [l.out_channels for l in lasts], dim=1)))
         # (split, not four slices: the backward of split is ONE concatenation of the heads' input gradients, the backward of each

@@ -138,9 +138,11 @@ def _broadcast_replicas(net):  # (replicas start identical: what the DDP constru
 @contextlib.contextmanager
 def _captured_training_pass(tr, canvases, second_half=False):
     """prologue and epilogue of a captured training step, around its loss + backward.  `tr` carries `_flat_grad`, `_gather_params`,
-    `device` and `_pack_jobs` (recorded in the warm-up: every layer's forward / data-gradient panels then come from ONE launch);
-    `canvases`: the leaf inputs.  `second_half` of a backward pass split in two (GradCut): gradients and panels of the first stay."""
-    from liso_amd.utils import mfma_conv as MC
+    `device`, `_pack_jobs` (recorded in the warm-up: every layer's forward / data-gradient panels then come from ONE launch) and, where
+    it has one, `_opt_packs` (then from the AdamW launch: no pack launch, no filter-building copy in this step; requests that table
+    does not cover are packed as before).  `canvases`: the leaf inputs.  `second_half` of a backward pass split in two (GradCut):
+    gradients and panels of the first stay."""
+    from liso_amd.utils import conv_panels as CP
 
     if not second_half:
         tr._flat_grad.zero_()
@@ -148,26 +150,15 @@ def _captured_training_pass(tr, canvases, second_half=False):
         # gradient -- a 134-MB fill and a 400-MB accumulation into zeros per detector step at B = 4 otherwise)
         for c in canvases:
             c.grad = None
-        opt_packs = getattr(tr, "_opt_packs", None) if MC.optimizer_packs_enabled() else None
-        if opt_packs is not None:
-            # panels and merged filters that the AdamW launch keeps current: no pack launch, no filter-building copy in this step
-            # (requests the table does not cover are packed as before)
-            tr._step_packs = dict(opt_packs.panels)
-            if opt_packs.leftover_jobs:
-                tr._step_packs.update(MC.batched_pack(opt_packs.leftover_jobs))
-            tr._step_merged = opt_packs.merged
-        else:
-            tr._step_packs = MC.batched_pack(tr._pack_jobs) if tr._pack_jobs else None
-            tr._step_merged = None
-    MC.set_step_packs(tr._step_packs, getattr(tr, "_step_merged", None))
+        tr._step_table = CP.step_table(tr._pack_jobs, getattr(tr, "_opt_packs", None))
     gathered = tr._gather_params or []
-    for p_, _ in gathered:  # (autograd then KEEPS the gradient tensor it is handed instead of adding it into the zeroed slice)
-        p_.grad = None
-    try:
-        yield
-    finally:
-        MC.set_step_packs(None)
-        tr._gather_keepalive = gather_gradients(tr.device, gathered, second_half)
+    with CP.step(tr._step_table):
+        for p_, _ in gathered:  # (autograd then KEEPS the gradient tensor it is handed instead of adding it into the zeroed slice)
+            p_.grad = None
+        try:
+            yield
+        finally:
+            tr._gather_keepalive = gather_gradients(tr.device, gathered, second_half)
 
 
 class DetectorTrainer:
@@ -393,6 +384,7 @@ class DetectorTrainer:
             self._static_targets = {k: v.to(dev).clone() for k, v in targets.items()}
             side = side_stream(dev, "flow")  # (the process's one: in the loop trainer, SLIM inference's stream)
             self._graph2, self._pack_jobs, self._gather_params = None, [], None
+            merged_jobs = []
             cut = self._grad_cut if self.n_grad_buckets == 2 else None
             rpn = self.net.model.rpn
 
@@ -426,8 +418,8 @@ class DetectorTrainer:
 
             if self._opt_packs is not None:
                 self._opt_packs.ensure_current()  # (the warm-up passes of a re-capture read the table's panels)
-            GC.warm_up(body, side, pack_jobs=self._pack_jobs, after_first=after_first_pass, restore=restore)
-            self._attach_optimizer_packs(MC.recorded_merged_jobs())
+            GC.warm_up(body, side, pack_jobs=self._pack_jobs, merged_jobs=merged_jobs, after_first=after_first_pass, restore=restore)
+            self._attach_optimizer_packs(merged_jobs)
             if cut is None:
                 self._graph, self._static_loss = GC.capture(body, side)
             else:  # two graphs sharing one memory pool: the second one reads the leaf gradient and the saved tensors of the first

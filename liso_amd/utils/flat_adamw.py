@@ -53,7 +53,7 @@ class FlatAdamW(torch.optim.Optimizer):
             p.grad = g
             self.state[p] = {"step": torch.tensor(0.0), "exp_avg": view(self.flat_exp_avg), "exp_avg_sq": view(self.flat_exp_avg_sq)}
         # an OptimizerPacks (liso_amd/utils/optimizer_packs.py): the update launch then also writes the convolutions' packed panels and
-        # merged filters (liso_adamw_step_packed_f32).  None, a loss scale, or mfma_conv.set_optimizer_packs(False): the plain update.
+        # merged filters (liso_adamw_step_packed_f32).  None, a loss scale, or conv_panels.set_optimizer_packs(False): the plain update.
         self.packs = None
 
     def attach_packs(self, packs):
@@ -78,9 +78,9 @@ class FlatAdamW(torch.optim.Optimizer):
         self._step += 1
         packs = self.packs
         if packs is not None:
-            from liso_amd.utils import mfma_conv as MC
+            from liso_amd.utils import conv_panels as CP
 
-            packs = packs if MC.optimizer_packs_enabled() else None
+            packs = packs if CP.optimizer_packs_enabled() else None
         scalars = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                    float(self.grad_scale), self._step)
         with torch.cuda.device(self.flat_param.device):

@@ -52,21 +52,26 @@ def frozen_buffers(net, keep=lambda k, v: v.is_floating_point() or v.dtype == to
         quiet(True)
 
 
-def warm_up(body, stream, n=2, pack_jobs=None, after_first=None, restore=None):
+def warm_up(body, stream, n=2, pack_jobs=None, merged_jobs=None, after_first=None, restore=None):
     """`body()` n times on `stream`, which starts behind the current stream's work; the current stream goes on behind the warm-up.
-    The list `pack_jobs` receives the weight panels the first pass asks for (mfma_conv.record_pack_jobs: a captured step then packs
-    them with ONE launch); `after_first()` runs between the first pass and the others; `restore()` (frozen_buffers) at the end."""
-    from liso_amd.utils import mfma_conv as MC
+    The lists `pack_jobs` / `merged_jobs` receive the weight panels the first pass asks for (conv_panels.recording: a captured step then
+    takes them from ONE launch, or from the optimizer's); `after_first()` runs between the first pass and the others; `restore()`
+    (frozen_buffers) at the end."""
+    from liso_amd.utils import conv_panels as CP
 
     cur = torch.cuda.current_stream(stream.device)
     if cur != stream:
         stream.wait_stream(cur)
     with torch.cuda.stream(stream):
-        if pack_jobs is not None:
-            MC.record_pack_jobs(True)
-        body()
-        if pack_jobs is not None:
-            pack_jobs.extend(MC.record_pack_jobs(False))
+        if pack_jobs is None and merged_jobs is None:
+            body()
+        else:
+            with CP.recording() as rec:
+                body()
+            if pack_jobs is not None:
+                pack_jobs.extend(rec.jobs)
+            if merged_jobs is not None:
+                merged_jobs.extend(rec.merged_jobs)
         if after_first is not None:
             after_first()
         for _ in range(n - 1):

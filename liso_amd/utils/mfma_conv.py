@@ -13,11 +13,11 @@ and optionally emits the per-block partial sums from which `finalize_bn` derives
 """
 import ctypes
 import os
-import weakref
 
 import torch
 
 from liso_amd import _lib as L
+from liso_amd.utils.conv_panels import merged_filters, optimizer_packs_enabled, pack_weights, set_optimizer_packs  # noqa: F401
 
 
 def on_device(x):
@@ -196,9 +196,6 @@ def as_nhwc(t, vec):
     return v, ps
 
 
-_PACK_CACHE = {}
-
-
 _SHARED_DEPTH = [0]
 
 
@@ -237,161 +234,6 @@ class roles_cus:
         if self.n:
             L.check(L.lib().liso_conv_set_option(L.CONV_OPT_ROLES_CUS, 0), "conv_set_option")
         return False
-
-
-_PACK_RECORD = None  # dict while the pack requests of a step are being recorded
-_STEP_PACKS = None   # dict while a step runs on panels that were packed by ONE batched launch
-
-
-def record_pack_jobs(on=True):
-    """start (-> None) / stop (-> list of jobs) recording which (Parameter, geometry, direction, arithmetic) panels a step asks
-    for.  A trainer records one warm-up step, then opens every captured step with `set_step_packs(batched_pack(jobs))`: one
-    launch instead of one per layer and direction (57 for the CenterPoint backbone + head)."""
-    global _PACK_RECORD, _MERGED_RECORD
-    if on:
-        _PACK_RECORD, _MERGED_RECORD = {}, {}
-        _MERGE_SOURCES.clear()
-        return None
-    jobs, _PACK_RECORD = list((_PACK_RECORD or {}).values()), None
-    return jobs
-
-
-def batched_pack(jobs):
-    """-> {key: packed panels} for `set_step_packs`; one liso_conv_pack_weights_batched call"""
-    out, arr = {}, (L.ConvPackJob * len(jobs))()
-    keep = []
-    for i, (key, weight, spec, for_dgrad, mode) in enumerate(jobs):
-        w, d0, d1, dst = _pack_operands(weight, spec, for_dgrad, mode)
-        keep.append(w)
-        arr[i] = L.ConvPackJob(w.data_ptr(), dst.data_ptr(), d0, d1, spec.kh, spec.kw, int(spec.transposed), int(bool(for_dgrad)), mode)
-        out[key] = dst
-    if jobs:
-        with torch.cuda.device(jobs[0][1].device):
-            L.check(L.lib().liso_conv_pack_weights_batched(arr, len(jobs), L.stream_ptr()), "conv_pack_weights_batched")
-    return out
-
-
-def set_step_packs(packs, merged=None):
-    """`packs`: {key: panel} the step's pack requests resolve to (None: every request packs for itself); `merged`: the always-current
-    merged filters of an attached optimizer table (liso_amd/utils/optimizer_packs.py), see `merged_static`"""
-    global _STEP_PACKS, _MERGED_STATIC
-    _STEP_PACKS = packs
-    _MERGED_STATIC = merged if packs is not None else None
-
-
-# ---- panels and merged filters that the optimizer keeps current (include/liso_optim.h: liso_adamw_step_packed_f32) -----------------------
-_OPTIMIZER_PACKS = [True]
-_MERGED_STATIC = None   # {(kind, ids of the source weights): (W, bias)} while a step runs on an optimizer table
-_MERGE_SOURCES = {}     # data_ptr of a merged filter built during a recorded step -> (kind, weights, biases, shape)
-_MERGED_RECORD = None   # the merged filters' pack requests of a recorded step
-
-
-def set_optimizer_packs(on):
-    """True: a graph-captured detector step reads packed panels, merged filters and concatenated biases that the AdamW launch wrote
-    (no pack launch, no filter-building copy in the graph); False: every step packs and merges for itself.  Identical results.  Takes
-    effect at the next capture.  -> the previous setting."""
-    was, _OPTIMIZER_PACKS[0] = _OPTIMIZER_PACKS[0], bool(on)
-    return was
-
-
-def optimizer_packs_enabled():
-    return _OPTIMIZER_PACKS[0]
-
-
-def merged_static(kind, weights):
-    """the optimizer-maintained merged filter and bias of these source weights ("cat": concatenated along the output channels,
-    "blockdiag": diagonal blocks), or None when the running step has none"""
-    if _MERGED_STATIC is None:
-        return None
-    return _MERGED_STATIC.get((kind,) + tuple(id(w) for w in weights))
-
-
-def note_merged_filter(kind, merged, weights, biases):
-    """a recorded step built `merged` from `weights`: its pack requests are then recorded with their sources"""
-    if _PACK_RECORD is not None and all(isinstance(w, torch.nn.Parameter) for w in weights):
-        _MERGE_SOURCES[merged.data_ptr()] = (kind, list(weights), list(biases), tuple(merged.shape))
-
-
-def recorded_merged_jobs():
-    """-> [(kind, weights, biases, spec, for_dgrad, mode)] of the step recorded last, once"""
-    global _MERGED_RECORD
-    jobs, _MERGED_RECORD = list((_MERGED_RECORD or {}).values()), None
-    _MERGE_SOURCES.clear()
-    return jobs
-
-
-class MergedFilters(torch.autograd.Function):
-    """(merged filter, merged bias) of parallel convolutions WITHOUT a launch: the buffers of an optimizer table, which the AdamW
-    launch keeps equal to torch.cat of the sources along the output channels.  Backward: the slices of the dense gradients, as
-    torch.cat's."""
-
-    @staticmethod
-    def forward(ctx, static, n, *wb):
-        ctx.co = [w.shape[0] for w in wb[:n]]
-        return static[0].detach(), static[1].detach()
-
-    @staticmethod
-    def backward(ctx, gW, gb):
-        gws, gbs, o = [], [], 0
-        for a in ctx.co:
-            gws.append(gW.narrow(0, o, a) if gW is not None else None)
-            gbs.append(gb.narrow(0, o, a) if gb is not None else None)
-            o += a
-        return (None, None, *gws, *gbs)
-
-
-def pack_weights(weight, spec, for_dgrad, mode):
-    """torch-layout fp32 master weights -> the kernels' packed bf16 panels (one launch).  The result is cached per weight
-    tensor until the tensor is modified in place (`_version`: optimizer steps bump it), so frozen networks pack once and
-    the forward / backward of one training step share the panels of a layer."""
-    L.require_cuda(weight)
-    if not isinstance(weight, torch.nn.Parameter):  # (temporaries: their storage is recycled, no stable identity)
-        if _STEP_PACKS is not None:  # (a merged filter that an optimizer table keeps: its storage IS stable)
-            hit = _STEP_PACKS.get(("merged", weight.data_ptr(), spec.kh, spec.kw, spec.transposed, bool(for_dgrad), mode))
-            if hit is not None:
-                return hit
-        if _PACK_RECORD is not None:
-            src = _MERGE_SOURCES.get(weight.data_ptr())
-            if src is not None and src[3] == tuple(weight.shape):
-                _MERGED_RECORD[(src[0],) + tuple(id(w) for w in src[1]) + (spec.kh, spec.kw, spec.transposed, bool(for_dgrad), mode)] = \
-                    (src[0], src[1], src[2], spec, bool(for_dgrad), mode)
-        return _pack_weights(weight, spec, for_dgrad, mode)
-    pkey = (id(weight), spec.kh, spec.kw, spec.transposed, bool(for_dgrad), mode)
-    if _STEP_PACKS is not None and pkey in _STEP_PACKS:
-        return _STEP_PACKS[pkey]
-    if _PACK_RECORD is not None:
-        _PACK_RECORD[pkey] = (pkey, weight, spec, bool(for_dgrad), mode)
-    if weight.requires_grad and torch.cuda.is_current_stream_capturing():
-        # a captured training step must re-pack on every replay (the optimizer changes the weights in between): never let a
-        # cache hit elide the pack launch from the graph
-        return _pack_weights(weight, spec, for_dgrad, mode)
-    key = (id(weight), spec.transposed, bool(for_dgrad), mode)
-    hit = _PACK_CACHE.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
-        return hit[3]
-    out = _pack_weights(weight, spec, for_dgrad, mode)
-    # the entry dies with the Parameter object (a recycled id() can therefore never hit a stale panel)
-    _PACK_CACHE[key] = (weakref.ref(weight, lambda _r, k=key: _PACK_CACHE.pop(k, None)), weight._version, weight.data_ptr(), out)
-    return out
-
-
-def _pack_operands(weight, spec, for_dgrad, mode):
-    """-> (fp32 contiguous source, its two leading dimensions, uninitialised panel buffer) of one pack job"""
-    w = weight.detach()
-    if w.dtype != torch.float32 or not w.is_contiguous():
-        w = w.float().contiguous()
-    d0, d1 = w.shape[0], w.shape[1]
-    K, N = (d1, d0) if spec.transposed == bool(for_dgrad) else (d0, d1)
-    dst = torch.empty(L.lib().liso_conv_packed_bytes(K, N, spec.kh * spec.kw, mode), dtype=torch.uint8, device=w.device)
-    return w, d0, d1, dst
-
-
-def _pack_weights(weight, spec, for_dgrad, mode):
-    w, d0, d1, out = _pack_operands(weight, spec, for_dgrad, mode)
-    with torch.cuda.device(w.device):
-        L.check(L.lib().liso_conv_pack_weights(L.ptr(w), d0, d1, spec.kh, spec.kw, int(spec.transposed), int(bool(for_dgrad)), mode,
-                                               L.ptr(out), L.stream_ptr()), "conv_pack_weights")
-    return out
 
 
 def _half_mode(mode):
@@ -1124,23 +966,8 @@ def fused_conv(x_raw, fold, conv, out_bn=None, out_dtype=None, out_relu=False, s
     spec = spec or ConvSpec.of(convs[0])
     if len(convs) == 1:
         weight, bias = convs[0].weight, convs[0].bias
-    elif torch.is_grad_enabled() and any(c.weight.requires_grad for c in convs):
-        static = merged_static("cat", [c.weight for c in convs]) if convs[0].bias is not None else None
-        if static is not None:  # (kept current by the AdamW launch: nothing to concatenate)
-            weight, bias = MergedFilters.apply(static, len(convs), *[c.weight for c in convs], *[c.bias for c in convs])
-        else:
-            weight = torch.cat([c.weight for c in convs], dim=0)
-            bias = torch.cat([c.bias for c in convs], dim=0) if convs[0].bias is not None else None
-            if bias is not None:
-                note_merged_filter("cat", weight, [c.weight for c in convs], [c.bias for c in convs])
-    else:  # frozen / inference: the concatenated filters are built once per weight version (their packed panels are cached with them)
-        key = tuple((id(c), c.weight._version, c.weight.data_ptr(), None if c.bias is None else c.bias._version) for c in convs)
-        hit = getattr(convs[0], "_liso_merged_weights", None)
-        if hit is None or hit[0] != key:
-            w = torch.nn.Parameter(torch.cat([c.weight.detach() for c in convs], dim=0), requires_grad=False)
-            b = torch.cat([c.bias.detach() for c in convs], dim=0) if convs[0].bias is not None else None
-            hit = convs[0]._liso_merged_weights = (key, w, b)
-        weight, bias = hit[1], hit[2]
+    else:
+        weight, bias = merged_filters("cat", convs)
     training_bn = bns is not None and (bns[0].training or not bns[0].track_running_stats)
     # (`out`: (channels-last buffer, first channel) the raw output is written into, see conv_forward)
     meta = {"spec": spec, "fold": fold, "out_dtype": out_dtype, "want_stats": training_bn, "out_relu": out_relu, "occupancy": occupancy,

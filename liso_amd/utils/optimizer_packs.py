@@ -1,35 +1,27 @@
 """What a FlatAdamW launch writes besides the parameters (include/liso_optim.h: liso_adamw_step_packed_f32): the packed filter panels
 of the convolutions, and the merged fp32 filters / concatenated biases of convolutions that run as one launch.
 
-`OptimizerPacks` is built once from the pack requests that a warm-up step recorded (mfma_conv.record_pack_jobs /
-recorded_merged_jobs).  Panels and merged buffers are allocated here, outside any graph's memory pool, filled once from the master
-weights, and from then on rewritten by every `optimizer.step()`.  A captured step hands `panels` / `merged` to
-mfma_conv.set_step_packs and contains no pack launch.  Whatever else changes a parameter (load_state_dict, an in-place edit, an
-update by another path) moves its `_version` away from the one the panels were written at: `ensure_current()`, called before every
-replay, then repacks everything with one launch (liso_conv_pack_weights_placed)."""
+`OptimizerPacks` is built once from the pack requests that a warm-up step recorded (conv_panels.recording: `jobs`, `merged_jobs`).
+Panels and merged buffers are allocated here, outside any graph's memory pool, filled once from the master weights, and from then on
+rewritten by every `optimizer.step()`.  A captured step opens `step_table()` (conv_panels.step) and contains no pack launch.  Whatever
+else changes a parameter (load_state_dict, an in-place edit, an update by another path) moves its `_version` away from the one the
+panels were written at: `ensure_current()`, called before every replay, then repacks everything with one launch
+(liso_conv_pack_weights_placed)."""
 import ctypes
 
 import torch
 
 from liso_amd import _lib as L
+from liso_amd.utils import conv_panels as CP
 
-_MODES = None
-
-
-def _modes():
-    global _MODES
-    if _MODES is None:
-        _MODES = (L.CONV_BF16, L.CONV_F32X3, L.CONV_F32)
-    return _MODES
+_MODES = (L.CONV_BF16, L.CONV_F32X3, L.CONV_F32)
 
 
 class OptimizerPacks:
     def __init__(self, opt, pack_jobs, merged_jobs=()):
-        """`opt`: the FlatAdamW; `pack_jobs`: [(key, Parameter, spec, for_dgrad, mode)] as recorded; `merged_jobs`: [(kind, weights,
-        biases, spec, for_dgrad, mode)].  Requests this table does not cover (a parameter outside the optimizer, a third panel of one
-        tensor, an fp16 panel) stay in `leftover_jobs`: the step packs those as before."""
-        from liso_amd.utils import mfma_conv as MC  # noqa: F401
-
+        """`opt`: the FlatAdamW; `pack_jobs`: conv_panels.PackJobs as recorded; `merged_jobs`: conv_panels.MergedJobs.  Requests this
+        table does not cover (a parameter outside the optimizer, a third panel of one tensor, an fp16 panel) stay in `leftover_jobs`:
+        the step packs those as before."""
         lib = L.lib()
         self.device = opt.flat_param.device
         self.panels, self.merged, self.leftover_jobs = {}, {}, []
@@ -60,10 +52,10 @@ class OptimizerPacks:
         # merged filters first: their sources' two panel slots go to the merged panels
         groups = {}
         for kind, ws, bs, spec, for_dgrad, mode in merged_jobs:
-            gkey = (kind,) + tuple(id(w) for w in ws)
+            gkey = CP.merged_key(kind, ws)
             its = [item_of(w, spec.kh, spec.kw, spec.transposed) for w in ws]
             bits = [item_of(b, 1, 1, False) for b in bs]
-            usable = mode in _modes() and not spec.transposed and all(i is not None for i in its + bits) and \
+            usable = mode in _MODES and not spec.transposed and all(i is not None for i in its + bits) and \
                 all(len(i["dests"]) < 2 for i in its)
             if not usable:
                 continue
@@ -96,12 +88,12 @@ class OptimizerPacks:
                 k_off, n_off = (o, col) if for_dgrad else (col, o)
                 add_dest(it, dst, for_dgrad, mode, K, N, k_off, n_off)
                 o, c = o + a, c + k
-            self.panels[("merged", W.data_ptr(), spec.kh, spec.kw, spec.transposed, bool(for_dgrad), mode)] = dst
+            self.panels[CP.request_key(W, spec, for_dgrad, mode)] = dst
         self.merged = groups
 
         for job in pack_jobs:
             key, w, spec, for_dgrad, mode = job
-            it = item_of(w, spec.kh, spec.kw, spec.transposed) if (w.dim() == 4 and mode in _modes()) else None
+            it = item_of(w, spec.kh, spec.kw, spec.transposed) if (w.dim() == 4 and mode in _MODES) else None
             if it is None or len(it["dests"]) >= 2:
                 self.leftover_jobs.append(job)
                 continue
@@ -130,6 +122,11 @@ class OptimizerPacks:
         self._versions = None
         self.repacks = 0
         self.repack(clear=True)
+
+    def step_table(self):
+        """what a captured step's requests resolve to: the panels and merged buffers kept here, and the `leftover_jobs` packed now with
+        one launch"""
+        return CP.StepTable.packed(self.leftover_jobs, self.panels, self.merged)
 
     def repack(self, clear=False):
         """panels and merged buffers from the current master weights: one pack launch (+ one zero fill with `clear`) and one copy launch"""

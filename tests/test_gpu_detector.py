@@ -354,7 +354,7 @@ def test_two_graph_step_with_the_backward_pass_cut_behind_block0_equals_the_one_
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32, torch.float16])
 def test_merged_output_convolutions_of_the_heads_equal_the_four_separate_ones(dtype):
     """SepHead.forward_fused runs the four output convolutions (64 -> 3 / 3 / 2 / 1 on their slices of the merged hidden map) as ONE
-    convolution with block-diagonal filters (center_head.py:_BlockDiagonalFilters).  Zeros off the diagonal add exact zeros: logits
+    convolution with block-diagonal filters (conv_panels.py:_BlockDiagonalFilters).  Zeros off the diagonal add exact zeros: logits
     and every gradient equal the four-launch path to fp32 summation order."""
     if dtype == torch.float16:
         require_fp16()
