@@ -9,12 +9,14 @@
  * box_groundtruth_matching.py:193-229), and sum the true-positive errors (:489-545).  The precision / recall sweep stays on
  * the host (liso_amd/eval/od_metrics.py says why).
  *
- * Launches of this library's kernels per validation batch, whatever the number of frames F and of jobs J: at most THREE --
+ * Launches of this library's kernels per validation batch, whatever the number of frames F and of jobs J: at most THREE, and a
+ * FOURTH only when Waymo-style collections (WaymoObjectDetectionMetrics, liso/eval/od_metrics.py:1397-1835) were asked for --
  *   (1) liso_det_val_pairs_f32        the [P,G] pair matrices of every frame
  *   (2) liso_det_val_transfer_classes run_val's class transfer (:406-447), a launch of its own BEFORE the jobs: the class
  *                                     filtered jobs of (3) read the classes it wrote (the alternative, every class job
  *                                     repeating the transfer walk, was not chosen)
  *   (3) liso_det_val_match_f32        all (job, frame) cells
+ *   (4) liso_det_val_assign_f32       all (job, frame) cells of the optimal-assignment jobs (a job table of their own)
  *
  * Conventions (as include/liso_iou3d.h): device pointers, no allocation, no host synchronisation; every entry point checks
  * its arguments before it launches anything and returns LISO_OK, LISO_EINVAL or LISO_ELAUNCH.
@@ -115,6 +117,46 @@ int liso_det_val_match_f32(int frames, int n_gt, int n_pred, const float* gt, co
                            const float* iou_bev, const float* iou_3d, const float* dist, int criteria_mask,
                            const liso_det_val_filter* filters, int n_filters, const liso_det_val_job* jobs, int n_jobs,
                            int32_t* count, int16_t* pairs, double* sums, uint8_t* gt_in, uint8_t* pred_in, void* stream);
+
+/* (4) Assign: a grid of (job, frame) cells, one wavefront each, for the collections that match by optimal assignment
+ *     (match_boxes_by_descending_confidence_iou(..., matching_mode="hungarian"), liso/kabsch/box_groundtruth_matching_iou.py:70-118:
+ *     the IoU matrix padded to a square with -1, non-finite entries -> -1, scipy's linear_sum_assignment(maximize=True), matches
+ *     with IoU >= threshold kept).  The cell applies its job's filter set to both box sets; with V the criterion's matrix:
+ *       - either set empty: no matches;
+ *       - c(g,p) = V[p][g] if finite, else -1.0f (assignable, never kept);
+ *       - every member of the smaller set is assigned to a distinct member of the larger one so that the sum of c is largest (the
+ *         reference's padded square problem has the same optima: its number of dummy assignments is fixed at |n_p - n_g|);
+ *       - the assigned pairs with c >= threshold are kept, compared in fp32 with the job's fp32 threshold.  fp32(0.4), the
+ *         reference's threshold, is the smallest fp32 not below 0.4, so every fp32 value is decided as the reference's fp64
+ *         comparison decides it.
+ *     Which of several equally good assignments is found is fixed by the method (scipy leaves it unspecified): rows are the smaller
+ *     set in ascending slot order (the ground truth when both are equally large), columns the other set in ascending slot order;
+ *     rows are inserted one by one by a shortest augmenting path; cost -c, potentials and running minima in fp64, starting at 0; a
+ *     search step takes the unvisited column of the smallest reduced distance -- on equal distances a free (unassigned) column
+ *     before an assigned one, then the lowest column position -- and shifts the potentials of the visited rows and columns and the minima of the others by that distance.  Additions, subtractions
+ *     and comparisons only; liso_amd/eval/det_validation.py::assign_host is the same procedure in numpy and gives the same pairs bit
+ *     for bit from the same matrix.
+ *   Inputs as (3) without `order`; only the IoU criteria: criteria_mask in [0,3], a set bit with a NULL matrix is LISO_EINVAL, and a
+ *     job that names LISO_DET_VAL_DIST (or a filter out of range) matches nothing.
+ *   Outputs, with M = min(G,P):
+ *     count  int32 [F,J]        kept pairs of the cell
+ *     pairs  int16 [F,J,M,2]    (gt slot, pred slot) in ascending ground-truth slot, (-1,-1) after the last
+ *     gt_in  uint8 [F,S,G], pred_in uint8 [F,S,P]   as (3) writes them, for THIS call's filter table
+ *   No true-positive error sums: these collections never read them.
+ *   Cost: one wavefront walks a cell alone; its dependent chain is (rows) x (steps of a row's search), a step being one pass over
+ *   the 16 columns a lane owns at most.  Typical cells end a search after one or two steps; the worst case is 1024 rows x up to
+ *   1024 steps.  Measured on MI355X: 512 cells of about 22 x 99 boxes 0.033 ms, one 1000 x 1024 cell with about 800 true overlaps
+ *   9.4 ms. */
+int liso_det_val_assign_f32(int frames, int n_gt, int n_pred, const float* gt, const uint8_t* gt_valid, const int32_t* gt_class,
+                            const float* pred, const uint8_t* pred_valid, const int32_t* pred_class, const float* iou_bev,
+                            const float* iou_3d, int criteria_mask, const liso_det_val_filter* filters, int n_filters,
+                            const liso_det_val_job* jobs, int n_jobs, int32_t* count, int16_t* pairs, uint8_t* gt_in, uint8_t* pred_in,
+                            void* stream);
+
+/* The same device body on a caller's batch of plain matrices, no filters: value_pred_major fp32 [batch,n_pred,n_gt] (every slot takes
+ * part), 0 <= n_gt, n_pred <= LISO_DET_VAL_MAX_BOXES -> count int32 [batch], pairs int16 [batch,min(n_gt,n_pred),2] as (4). */
+int liso_match_assign_f32(const float* value_pred_major, long batch, int n_gt, int n_pred, float threshold, int32_t* count,
+                          int16_t* pairs, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 // Detector validation matching for gfx950 (MI355X), C ABI in include/liso_det_val.h: the pair matrices of every frame of a padded
-// batch in one launch, run_val's class transfer in one launch, and every (job, frame) matching in one launch.
+// batch in one launch, run_val's class transfer in one launch, every (job, frame) greedy matching in one launch, and every (job, frame)
+// optimal assignment of the Waymo-style collections in one launch (assign_kernel, further down).
 //
 // The work per matching is tiny (tens of boxes) and there are thousands of them per validation batch, so the shape is: one
 // wavefront per (job, frame) cell, the serial walk over the predictions kept short --
@@ -318,6 +319,230 @@ __global__ __launch_bounds__(64) void transfer_kernel(int G, int P, const uint8_
     for (int p = lane; p < P; p += 64) out[(size_t)f * P + p] = s_cls[p];
 }
 
+// ---- optimal assignment of a cell (header: "(4) Assign") ---------------------------------------------------------------------------
+// Shortest augmenting paths with potentials, one wavefront per cell.  Rows: the smaller set, inserted one by one; columns: the larger
+// set; a lane owns the column positions lane, lane + 64, ...  Potentials and running minima are fp64 in LDS, the "visited" flags one
+// bit per owned column in a register.  A step of a row's search is one pass over the lane's unvisited columns (one value of the
+// pair matrix each), a wave minimum of (reduced distance, assigned?, column position) and one pass that shifts potentials and minima
+// by it.
+// Only additions, subtractions and comparisons of fp64 values: liso_amd/eval/det_validation.py::assign_host performs the same
+// operations in the same order and so finds the same pairs bit for bit.
+struct AssignLds {
+    double u[kMaxBoxes];          // row potentials
+    double v[kMaxBoxes];          // column potentials
+    double minv[kMaxBoxes];       // running minima of the current row's search
+    int16_t way[kMaxBoxes];       // column visited before this one on its shortest path (-1: the search's start)
+    int16_t owner[kMaxBoxes];     // row assigned to a column (-1: free)
+    int16_t g_slot[kMaxBoxes];    // the members' slots in ascending order: one list is the rows, the other the columns
+    int16_t p_slot[kMaxBoxes];
+    int16_t col_of_row[kMaxBoxes];  // the result read by rows: a row's column position (-1: none)
+    uint8_t gin[kMaxBoxes], pin[kMaxBoxes];
+};
+static_assert(sizeof(AssignLds) <= 48 * 1024, "static LDS of a cell");
+
+// members of `in[0..n)` in ascending slot order -> list; every lane returns their number
+__device__ __forceinline__ int compact_members(const uint8_t* in, int n, int16_t* list) {
+    const int lane = threadIdx.x & 63;
+    int k = 0;
+    for (int base = 0; base < n; base += 64) {
+        const int s = base + lane;
+        const bool m = s < n && in[s] != 0;
+        const unsigned long long b = __ballot(m);
+        if (m) {
+            list[k + __popcll(b & ((1ull << lane) - 1ull))] = (int16_t)s;
+        }
+        k += __popcll(b);
+    }
+    return k;
+}
+
+// the value of a pair as the assignment sees it: non-finite entries count as -1 (assignable, never kept)
+__device__ __forceinline__ float assign_value(float x) { return (x - x == 0.f) ? x : -1.0f; }
+
+// One cell.  val: [P,G] pred-major; L.gin / L.pin hold the membership of every slot (written by the caller, visible after its
+// barrier).  Writes the kept pairs (ascending ground-truth slot) to pairs[0..M) and pads with (-1,-1); returns their number.
+__device__ int assign_cell(AssignLds& L, const float* __restrict__ val, int G, int P, int M, float thr, int16_t* __restrict__ pairs) {
+    const int lane = threadIdx.x & 63;
+    const int n_g = compact_members(L.gin, G, L.g_slot), n_p = compact_members(L.pin, P, L.p_slot);
+    __syncthreads();
+    int kept = 0;
+    if (n_g > 0 && n_p > 0) {
+        const bool gt_rows = n_g <= n_p;  // the ground truth takes the rows when both sets are equally large
+        const int n = gt_rows ? n_g : n_p, m = gt_rows ? n_p : n_g;
+        const int16_t* row_slot = gt_rows ? L.g_slot : L.p_slot;
+        const int16_t* col_slot = gt_rows ? L.p_slot : L.g_slot;
+        // element strides of a step along the columns / of a row, in the pred-major matrix
+        const size_t col_stride = gt_rows ? (size_t)G : 1, row_stride = gt_rows ? 1 : (size_t)G;
+        const int owned = (m + 63) >> 6;
+        for (int r = 0; r < owned; ++r) {
+            const int j = lane + 64 * r;
+            if (j < m) L.v[j] = 0.0, L.owner[j] = -1;
+        }
+        for (int i = lane; i < n; i += 64) L.u[i] = 0.0, L.col_of_row[i] = -1;
+        __syncthreads();
+        const double inf = __longlong_as_double(0x7FF0000000000000LL);
+        for (int i = 0; i < n; ++i) {
+            for (int r = 0; r < owned; ++r) {
+                const int j = lane + 64 * r;
+                if (j < m) L.minv[j] = inf;
+            }
+            uint32_t used = 0u;
+            int j0 = -1;
+            bool found = false;
+            for (int step = 0; step <= n; ++step) {  // (a search visits at most the i assigned columns and one free one)
+                const int i0 = j0 < 0 ? i : (int)L.owner[j0];
+                const double ui = L.u[i0];
+                const float* row = val + (size_t)row_slot[i0] * row_stride;
+                double best = inf;
+                int bj = 0x7FFFFFFF;
+                for (int r = 0; r < owned; ++r) {
+                    const int j = lane + 64 * r;
+                    if (j >= m || ((used >> r) & 1u)) continue;
+                    const float c = assign_value(row[(size_t)col_slot[j] * col_stride]);
+                    const double cur = ((double)(-c) - ui) - L.v[j];
+                    double mv = L.minv[j];
+                    if (cur < mv) {
+                        mv = cur;
+                        L.minv[j] = cur;
+                        L.way[j] = (int16_t)j0;
+                    }
+                    const int key = j | (L.owner[j] >= 0 ? kMaxBoxes : 0);  // on equal distances: a free column first, then the lowest position
+                    if (mv < best || (mv == best && key < bj)) best = mv, bj = key;
+                }
+#pragma unroll
+                for (int x = 32; x >= 1; x >>= 1) {  // wave minimum of (distance, key)
+                    const long long bits = __double_as_longlong(best);
+                    const int lo = __shfl_xor((int)(unsigned int)bits, x), hi = __shfl_xor((int)(bits >> 32), x);
+                    const double ob = __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+                    const int oj = __shfl_xor(bj, x);
+                    if (ob < best || (ob == best && oj < bj)) best = ob, bj = oj;
+                }
+                if (bj == 0x7FFFFFFF) break;  // (cannot happen: a free column exists and every value is finite)
+                bj &= kMaxBoxes - 1;
+                const double delta = best;
+                for (int r = 0; r < owned; ++r) {
+                    const int j = lane + 64 * r;
+                    if (j >= m) continue;
+                    if ((used >> r) & 1u) {
+                        L.u[L.owner[j]] = L.u[L.owner[j]] + delta;
+                        L.v[j] = L.v[j] - delta;
+                    } else {
+                        L.minv[j] = L.minv[j] - delta;
+                    }
+                }
+                if (lane == 0) L.u[i] = L.u[i] + delta;
+                j0 = bj;
+                if ((j0 & 63) == lane) used |= 1u << (j0 >> 6);
+                __syncthreads();
+                if (L.owner[j0] < 0) {
+                    found = true;
+                    break;
+                }
+            }
+            if (lane == 0 && found) {  // flip the path back to the start
+                int j = j0;
+                for (int guard = 0; guard <= n && j >= 0; ++guard) {
+                    const int j1 = L.way[j];
+                    L.owner[j] = j1 < 0 ? (int16_t)i : L.owner[j1];
+                    j = j1;
+                }
+            }
+            __syncthreads();
+        }
+        // the kept pairs in ascending ground-truth slot: position k of the ground truth's side (rows or columns) in ascending k
+        if (gt_rows) {
+            for (int r = 0; r < owned; ++r) {
+                const int j = lane + 64 * r;
+                if (j < m && L.owner[j] >= 0) L.col_of_row[L.owner[j]] = (int16_t)j;
+            }
+            __syncthreads();
+        }
+        for (int base = 0; base < n_g; base += 64) {
+            const int k = base + lane;
+            int g = -1, p = -1;
+            bool keep = false;
+            if (k < n_g) {
+                const int q = gt_rows ? L.col_of_row[k] : L.owner[k];  // the prediction's position; -1: a column left free
+                if (q >= 0) {
+                    g = L.g_slot[k], p = L.p_slot[q];
+                    keep = assign_value(val[(size_t)p * G + g]) >= thr;
+                }
+            }
+            const unsigned long long b = __ballot(keep);
+            if (keep) {
+                const int at = kept + __popcll(b & ((1ull << lane) - 1ull));
+                if (at < M) pairs[2 * at] = (int16_t)g, pairs[2 * at + 1] = (int16_t)p;
+            }
+            kept += __popcll(b);
+        }
+        if (kept > M) kept = M;
+    }
+    for (int i = kept + lane; i < M; i += 64) pairs[2 * i] = -1, pairs[2 * i + 1] = -1;
+    return kept;
+}
+
+struct AssignArgs {
+    int G, P, S, J, M;
+    const float* gt;
+    const uint8_t* gv;
+    const int32_t* gc;
+    const float* pred;
+    const uint8_t* pv;
+    const int32_t* pc;
+    const float* mat[2];
+    const liso_det_val_filter* filters;
+    const liso_det_val_job* jobs;
+    int32_t* count;
+    int16_t* pairs;
+    uint8_t* gt_in;
+    uint8_t* pred_in;
+};
+
+__global__ __launch_bounds__(64) void assign_kernel(AssignArgs a) {
+    __shared__ AssignLds L;
+    const int lane = threadIdx.x;
+    const size_t cell = blockIdx.x;
+    const int f = (int)(cell / (size_t)a.J), j = (int)(cell - (size_t)f * a.J);
+    const int G = a.G, P = a.P, M = a.M;
+    const liso_det_val_job job = a.jobs[j];
+    int16_t* pairs = a.pairs + cell * (size_t)M * 2;
+    const bool set_ok = job.filter >= 0 && job.filter < a.S;
+    const bool ok = set_ok && (job.criterion == LISO_DET_VAL_IOU_BEV || job.criterion == LISO_DET_VAL_IOU_3D);
+    liso_det_val_filter fl = {};
+    if (set_ok) fl = a.filters[job.filter];
+    const float* gt = a.gt + (size_t)f * G * 7;
+    const float* pred = a.pred + (size_t)f * P * 7;
+    for (int g = lane; g < G; g += 64) {
+        const size_t s = (size_t)f * G + g;
+        const bool in = set_ok && in_set(gt + (size_t)g * 7, a.gv[s], a.gc[s], fl);
+        if (set_ok) a.gt_in[((size_t)f * a.S + job.filter) * G + g] = in ? 1 : 0;
+        L.gin[g] = (in && ok) ? 1 : 0;
+    }
+    for (int p = lane; p < P; p += 64) {
+        const size_t s = (size_t)f * P + p;
+        const bool in = set_ok && in_set(pred + (size_t)p * 7, a.pv[s], a.pc[s], fl);
+        if (set_ok) a.pred_in[((size_t)f * a.S + job.filter) * P + p] = in ? 1 : 0;
+        L.pin[p] = (in && ok) ? 1 : 0;
+    }
+    __syncthreads();
+    const float* val = a.mat[ok ? job.criterion : 0];
+    if (val) val += (size_t)f * P * G;
+    const int kept = assign_cell(L, val, G, P, M, job.threshold, pairs);
+    if (lane == 0) a.count[cell] = kept;
+}
+
+__global__ __launch_bounds__(64) void assign_plain_kernel(int G, int P, int M, const float* __restrict__ val, float thr,
+                                                           int32_t* __restrict__ count, int16_t* __restrict__ pairs) {
+    __shared__ AssignLds L;
+    const int lane = threadIdx.x;
+    const size_t cell = blockIdx.x;
+    for (int g = lane; g < G; g += 64) L.gin[g] = 1;
+    for (int p = lane; p < P; p += 64) L.pin[p] = 1;
+    __syncthreads();
+    const int kept = assign_cell(L, val + cell * (size_t)P * G, G, P, M, thr, pairs + cell * (size_t)M * 2);
+    if (lane == 0) count[cell] = kept;
+}
+
 bool bad_shape(int frames, int G, int P) { return frames < 0 || G < 0 || P < 0 || G > kMaxBoxes || P > kMaxBoxes; }
 
 }  // namespace
@@ -404,6 +629,44 @@ int liso_det_val_match_f32(int frames, int n_gt, int n_pred, const float* gt, co
     a.mat[0] = iou_bev ? iou_bev : any, a.mat[1] = iou_3d ? iou_3d : any, a.mat[2] = dist ? dist : any;
     a.filters = filters, a.jobs = jobs, a.count = count, a.pairs = pairs, a.sums = sums, a.gt_in = gt_in, a.pred_in = pred_in;
     hipLaunchKernelGGL(match_kernel, dim3((unsigned)(frames * n_jobs)), dim3(64), 0, (hipStream_t)stream, a);
+    return check_launch();
+}
+
+int liso_det_val_assign_f32(int frames, int n_gt, int n_pred, const float* gt, const uint8_t* gt_valid, const int32_t* gt_class,
+                            const float* pred, const uint8_t* pred_valid, const int32_t* pred_class, const float* iou_bev,
+                            const float* iou_3d, int criteria_mask, const liso_det_val_filter* filters, int n_filters,
+                            const liso_det_val_job* jobs, int n_jobs, int32_t* count, int16_t* pairs, uint8_t* gt_in, uint8_t* pred_in,
+                            void* stream) {
+    if (bad_shape(frames, n_gt, n_pred) || n_filters < 0 || n_jobs < 0 || criteria_mask < 0 || criteria_mask > 3) return LISO_EINVAL;
+    if (frames == 0 || n_jobs == 0) return LISO_OK;
+    if (n_filters == 0 || !filters || !jobs || !count) return LISO_EINVAL;
+    if (n_gt > 0 && (!gt || !gt_valid || !gt_class || !gt_in)) return LISO_EINVAL;
+    if (n_pred > 0 && (!pred || !pred_valid || !pred_class || !pred_in)) return LISO_EINVAL;
+    const int M = n_gt < n_pred ? n_gt : n_pred;
+    const float* any = iou_bev ? iou_bev : iou_3d;
+    if (M > 0) {
+        if (!pairs || !any) return LISO_EINVAL;
+        if (((criteria_mask & 1) && !iou_bev) || ((criteria_mask & 2) && !iou_3d)) return LISO_EINVAL;
+    }
+    if ((long long)frames * n_jobs > 0x7FFFFFFFLL) return LISO_EINVAL;
+    AssignArgs a;
+    a.G = n_gt, a.P = n_pred, a.S = n_filters, a.J = n_jobs, a.M = M;
+    a.gt = gt, a.gv = gt_valid, a.gc = gt_class, a.pred = pred, a.pv = pred_valid, a.pc = pred_class;
+    a.mat[0] = iou_bev ? iou_bev : any, a.mat[1] = iou_3d ? iou_3d : any;  // (as liso_det_val_match_f32: never a NULL read)
+    a.filters = filters, a.jobs = jobs, a.count = count, a.pairs = pairs, a.gt_in = gt_in, a.pred_in = pred_in;
+    hipLaunchKernelGGL(assign_kernel, dim3((unsigned)(frames * n_jobs)), dim3(64), 0, (hipStream_t)stream, a);
+    return check_launch();
+}
+
+int liso_match_assign_f32(const float* value_pred_major, long batch, int n_gt, int n_pred, float threshold, int32_t* count,
+                          int16_t* pairs, void* stream) {
+    if (batch < 0 || batch > 0x7FFFFFFFL || bad_shape(0, n_gt, n_pred)) return LISO_EINVAL;
+    if (batch == 0) return LISO_OK;
+    if (!count) return LISO_EINVAL;
+    const int M = n_gt < n_pred ? n_gt : n_pred;
+    if (M > 0 && (!value_pred_major || !pairs)) return LISO_EINVAL;
+    hipLaunchKernelGGL(assign_plain_kernel, dim3((unsigned)batch), dim3(64), 0, (hipStream_t)stream, n_gt, n_pred, M, value_pred_major,
+                       threshold, count, pairs);
     return check_launch();
 }
 

@@ -48,7 +48,7 @@ def kitti_annotated_fov_mask(pred_boxes: Shape, pcl_full_w_ground):
 @torch.no_grad()
 def run_val(cfg, val_batches, box_predictor, writer_prefix: str = "", max_num_steps=None, logit_threshold=-1.0e32, dataset_kind="kitti",
             movable_class_names=("car", "pedestrian", "cyclist"), class_idxs=None, class_frequencies=None, generator=None,
-            filter_to_kitti_annotated_fov=None, validator=None):
+            filter_to_kitti_annotated_fov=None, validator=None, waymo_metrics=False):
     """The detector's validation pass (reference :120-757).  Per batch of `val_batches` -- dictionaries with `pcls` (the list of
     clouds the detector takes), `gt_boxes` and `benchmark_gt_boxes` (padded Shapes [B,G*] on the device) and optionally
     `pcl_full_w_ground` [B,N,>=3] -- it runs `box_predictor.predict_boxes` with run_val's defaults (:361-386), the optional KITTI rule
@@ -58,7 +58,11 @@ def run_val(cfg, val_batches, box_predictor, writer_prefix: str = "", max_num_st
 
     Class transfer (:406-447) draws every prediction's class on the device from `generator` (`class_frequencies`: the dataset's
     movable_class_frequencies -> torch.multinomial; else torch.randint), not from numpy's global state.
-    Out of scope: the nuScenes and Waymo devkit wrappers (the packages are absent), flow metrics (liso_amd/slim/validation.py has
+    waymo_metrics=True adds the reference's Waymo-style L1 / L2 collections (`WaymoObjectDetectionMetrics`, :249-255, 741-747; tags
+    `<writer_prefix>final_result/WAYMO/detection_metrics/<lo>_<hi>m<criterion>/overall/<L1|L2>/AP@0.4`, ...: the reference writes no
+    separator before the criterion), matched by optimal assignment on the device in one more launch per ground-truth set, and makes
+    dataset_kind="waymo" buildable (`DetectionValidator.for_run_val`).  With the default the result's keys are unchanged.
+    Out of scope: the nuScenes devkit wrapper (the package is absent), flow metrics (liso_amd/slim/validation.py has
     them), images, exports and TensorBoard writers."""
     from liso_amd.eval.det_validation import DetectionValidator
 
@@ -66,7 +70,8 @@ def run_val(cfg, val_batches, box_predictor, writer_prefix: str = "", max_num_st
     if validator is None:
         if class_idxs is None:
             class_idxs = tuple(range(len(movable_class_names)))
-        validator = DetectionValidator.for_run_val(dataset_kind, movable_class_names, class_idxs, moving, class_frequencies, generator)
+        validator = DetectionValidator.for_run_val(dataset_kind, movable_class_names, class_idxs, moving, class_frequencies, generator,
+                                                   waymo_metrics=waymo_metrics)
     for val_step, batch in enumerate(val_batches):
         if max_num_steps is not None and val_step > max_num_steps:  # (the reference's own off-by-one, :260)
             break

@@ -4,7 +4,8 @@ Mirror of the numeric part of liso/eval/od_metrics.py: `calc_ap` (:25-39), `get_
 `angle_diff` / `abs_yaw_diff` (:83-113), and `ObjectDetectionMetrics` (:161-545: range / class filters, per-threshold matching,
 the overall / moving / still book-keeping, ATE / ASE / AOE sums) with `compute()` returning the metric dictionary that the
 reference's `log()` (:1106-1311) fills -- same keys (`<prefix>/<criterion>/<class>/<category>/AP@<thr><unit>`, ...), without its
-matplotlib figures and the sklearn ROC / DET curves.
+matplotlib figures and the sklearn ROC / DET curves.  `WaymoObjectDetectionMetrics` (:1397-1835): the Waymo-style L1 / L2 AP@0.4
+collections, matched by optimal assignment, with `compute()` returning what its `log()` reports.
 
 Where the work is: per sample the IoU matrix and the greedy matching run on the device (`box_iou_matrix` -> HIP rotated IoU,
 `liso_match_greedy_f32`); the book-keeping is a handful of small host arrays per sample, as in the reference.  The precision /
@@ -330,3 +331,99 @@ def waymo_precisions_recalls_apscore(precisions, recalls, max_recall_gap=0.05):
         recalls = np.insert(recalls, np.repeat(i + 1, n_new), new_r)
     trapz = getattr(np, "trapezoid", None) or np.trapz
     return precisions, recalls, trapz(precisions, recalls)
+
+
+class WaymoObjectDetectionMetrics:
+    """Waymo-style L1 / L2 AP@0.4 (reference :1397-1835, without its plots and writers): boxes inside an inclusive BEV area (and
+    optionally a radial range, per class), matched by OPTIMAL ASSIGNMENT on the IoU (`matching_mode="hungarian"`) for both criteria,
+    pairs with IoU >= 0.4 kept.  L2 counts every ground-truth box; L1 drops the boxes with `difficulty > 0` and the predictions
+    assigned to them (:1581-1599).  `compute()` returns what the reference's `log()` puts into its metrics dictionary."""
+    CRITERIA = ("iou_3d", "iou_bev")
+    CATEGORIES = ("L1", "L2")
+    REPORT_AT_CONFIDENCES = (0.3, 1.0)
+
+    def __init__(self, eval_movable_classes_as_one: bool = True, bev_range_min_xy_m=(-50, -20), bev_range_max_xy_m=(50, 20),
+                 class_names: Tuple[str] = ("overall",), class_idxs: Tuple[int] = (0,), min_eval_range_m: float = None,
+                 max_eval_range_m: float = None):
+        self.min_eval_range_m, self.max_eval_range_m = min_eval_range_m, max_eval_range_m
+        self.eval_movable_classes_as_one = eval_movable_classes_as_one
+        if class_names == ("overall",):
+            class_idxs = (0,)
+        assert len(class_names) == len(class_idxs), (class_names, class_idxs)
+        self.class_idxs, self.class_names = class_idxs, class_names
+        self.box_matching_criterions, self.extra_categories = self.CRITERIA, self.CATEGORIES
+        self.iou_matching_threshold = 0.4
+        self.bev_range_min_xy_m, self.bev_range_max_xy_m = torch.tensor(bev_range_min_xy_m), torch.tensor(bev_range_max_xy_m)
+        new = lambda: {c: {crit: {cat: [] for cat in self.CATEGORIES} for crit in self.CRITERIA} for c in self.class_names}  # noqa: E731
+        self.gt_labels, self.scores, self.is_fn = new(), new(), new()
+
+    _in_bev_range = ObjectDetectionMetrics._in_bev_range
+    _in_abs_range = ObjectDetectionMetrics._in_abs_range
+    _of_class = staticmethod(ObjectDetectionMetrics._of_class)
+
+    # ---- accumulation (reference :1459-1664) ------------------------------------------------------------------------------------
+    def update(self, *, non_batched_gt_boxes: Shape, non_batched_pred_boxes: Shape, sample_token: str = ""):
+        """one frame through the host `hungarian` matching (IoU matrix from the HIP kernels, scipy's assignment)"""
+        gt, pred = self._in_bev_range(non_batched_gt_boxes.clone()), self._in_bev_range(non_batched_pred_boxes.clone())
+        if self.max_eval_range_m is not None and self.min_eval_range_m is not None:
+            gt, pred = self._in_abs_range(gt), self._in_abs_range(pred)
+        for class_idx, class_name in zip(self.class_idxs, self.class_names):
+            if class_name == "overall":
+                c_gt, c_pred = gt, pred
+            else:
+                c_gt, c_pred = self._of_class(gt.clone(), class_idx), self._of_class(pred.clone(), class_idx)
+            for crit in self.CRITERIA:
+                idx_gt, idx_pred, _, pred_mask, gt_mask = match_boxes_by_descending_confidence_iou(
+                    c_gt, c_pred, matching_threshold=self.iou_matching_threshold, iou_mode=crit, matching_mode="hungarian")
+                hard = np.squeeze(c_gt.numpy().difficulty, axis=-1) > 0
+                self.accumulate_matches(gt_mask, pred_mask, np.squeeze(c_pred.numpy().probs, axis=-1), idx_pred, idx_gt, hard, crit, class_name)
+
+    def accumulate_matches(self, gt_mask, pred_mask, logits, idx_pred, idx_gt, hard, crit, class_name):
+        """Public entry of the book-keeping for a matching done elsewhere (liso_amd/eval/det_validation.py), what
+        `update_for_specific_class_and_matching_crit` does after its matcher returned (:1527-1563).  The arguments index the
+        FILTERED, compacted box lists of one frame: gt_mask / hard (difficulty > 0) bool [n_gt], pred_mask bool [n_pred], logits
+        [n_pred], idx_gt / idx_pred the kept pairs."""
+        assert gt_mask.shape == hard.shape, (gt_mask.shape, hard.shape)
+        idx_gt, idx_pred = np.asarray(idx_gt, np.int64), np.asarray(idx_pred, np.int64)
+        for category, ignore in (("L2", np.zeros_like(hard)), ("L1", hard)):
+            self._update_category(gt_mask, pred_mask, logits, idx_pred, idx_gt, ignore, category, crit, class_name)
+
+    def _update_category(self, gt_mask, pred_mask, logits, idx_pred, idx_gt, ignore_gt, category, crit, class_name):
+        ignore_matched = ignore_gt[idx_gt]
+        use_pred = np.ones_like(pred_mask)
+        use_pred[idx_pred] = ~ignore_matched  # a prediction assigned to an ignored ground-truth box is neither TP nor FP
+        s_logits, s_pred_mask, s_gt_mask = logits[use_pred], pred_mask[use_pred], gt_mask[~ignore_gt]
+        n_tp = int(np.count_nonzero(s_gt_mask))
+        assert n_tp == np.count_nonzero(s_pred_mask), "mismatch"
+        n_fn = len(s_gt_mask) - n_tp
+        fp_scores = s_logits[~s_pred_mask]
+        L, S, F = self.gt_labels[class_name][crit][category], self.scores[class_name][crit][category], self.is_fn[class_name][crit][category]
+        L.append(np.zeros(fp_scores.shape[0], dtype=bool)); S.append(fp_scores); F.append(np.zeros(fp_scores.shape[0], dtype=bool))
+        L.append(np.ones(n_fn, dtype=bool)); S.append(-np.inf * np.ones(n_fn)); F.append(np.ones(n_fn, dtype=bool))
+        if n_tp > 0:
+            tp_scores = logits[idx_pred[~ignore_matched]]
+            L.append(np.ones(n_tp, dtype=bool)); S.append(tp_scores); F.append(np.zeros(n_tp, dtype=bool))
+
+    # ---- the numbers `log()` reports (reference :1666-1807) ------------------------------------------------------------------------
+    def collected(self, class_name, crit, category):
+        cat = lambda lists, dt: np.concatenate(lists[class_name][crit][category]).astype(dt) if lists[class_name][crit][category] else np.zeros(0, dt)  # noqa: E731
+        return cat(self.gt_labels, bool), cat(self.scores, np.float64), cat(self.is_fn, bool)
+
+    def compute(self, writer_prefix: str = "") -> Dict[str, float]:
+        """tags `<prefix><crit>/<class>/<L1|L2>/AP@0.4`, `.../Precision@0.4/@conf<c>`, `.../Recall@0.4/@conf<c>` for c in 0.3, 1.0.
+        The prefix is used as given: the reference puts no separator between it and the criterion (:1780-1798)."""
+        out = {}
+        thr = self.iou_matching_threshold
+        for class_name in self.class_names:
+            for crit in self.CRITERIA:
+                for category in self.CATEGORIES:
+                    conf, prec, rec = (t.numpy() for t in get_conf_prec_rec(*self.collected(class_name, crit, category), use_interpolation=False))
+                    pre = writer_prefix + f"{crit}/{class_name}/{category}/"
+                    for at in self.REPORT_AT_CONFIDENCES:
+                        if len(conf) == 0:
+                            continue
+                        i = np.abs(conf - at).argmin()
+                        out[pre + f"Precision@{thr:.1f}/@conf{at:.1f}"] = float(prec[i])
+                        out[pre + f"Recall@{thr:.1f}/@conf{at:.1f}"] = float(rec[i])
+                    out[pre + f"AP@{thr:.1f}"] = float(waymo_precisions_recalls_apscore(prec, rec)[2])
+        return out

@@ -34,6 +34,28 @@ def greedy_match_iou_matrix(iou_matrix, pred_order, matching_threshold: float):
     return idx_gt, idx_pred, miou, num, pmask[:n_pred].view(torch.bool), gmask[:n_gt].view(torch.bool)
 
 
+@torch.no_grad()
+def assign_iou_matrix(iou_matrix, matching_threshold: float):
+    """The optimal assignment on the device (liso_match_assign_f32, include/liso_det_val.h: the kernel body of the validation pass's
+    Waymo-style collections on a plain matrix).  iou_matrix fp32 [n_gt,n_pred] or a batch [B,n_gt,n_pred] (cuda), n_gt, n_pred <= 1024
+    -> device tensors (pairs int16 [..., min(n_gt,n_pred), 2]: the assigned (gt, pred) pairs with IoU >= threshold in ascending gt
+    index, (-1,-1) after the last; count int32 [...]).  Non-finite entries count as -1.  The same kept set as
+    `hungarian_match_iou_matrix` wherever the optimum is unique; among equal optima the kernel's documented rule decides.  No host
+    synchronisation."""
+    L.require_cuda(iou_matrix)
+    batched = iou_matrix.dim() == 3
+    iou = (iou_matrix if batched else iou_matrix[None]).float().transpose(1, 2).contiguous()  # [B, n_pred, n_gt]: the kernel's layout
+    B, n_pred, n_gt = iou.shape
+    if n_gt > 1024 or n_pred > 1024:
+        raise L.LisoHipError(f"at most 1024 boxes a side, got {n_gt} x {n_pred}")
+    count = torch.empty(B, dtype=torch.int32, device=iou.device)
+    pairs = torch.empty((B, min(n_gt, n_pred), 2), dtype=torch.int16, device=iou.device)
+    with torch.cuda.device(iou.device):
+        L.check(L.lib().liso_match_assign_f32(L.ptr(iou) if iou.numel() else None, B, n_gt, n_pred, float(matching_threshold), L.ptr(count),
+                                              L.ptr(pairs) if pairs.numel() else None, L.stream_ptr()), "match_assign")
+    return (pairs, count) if batched else (pairs[0], count[0])
+
+
 def hungarian_match_iou_matrix(iou_matrix, matching_threshold: float):
     """reference :70-118, the "hungarian" branch: optimal assignment on the host (scipy.optimize.linear_sum_assignment, as the
     reference does it), the IoU matrix padded with -1 rows / columns to a square, non-finite entries -> -1, matches kept where

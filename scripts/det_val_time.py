@@ -7,6 +7,9 @@ benchmark / waymo_cropped x 4 range bins x 2 criteria x 4 thresholds + 3 classes
 Device events around synchronised work; the kernel launches per frame of each path are counted with torch.profiler.
 Prints one JSON line.
     python scripts/det_val_time.py [--iters 5] [--per-frame-iters 1]
+--waymo times the Waymo-style L1 / L2 collections instead (run_val(..., waymo_metrics=True): four range bins on the benchmark ground
+truth, matched by optimal assignment in one more launch): the validation pass with the flag off and on in the same run, the per-frame
+`WaymoObjectDetectionMetrics.update` loop over the same frames (host scipy assignment), and the assignment launch's own device time.
 """
 import argparse
 import json
@@ -47,12 +50,12 @@ def frame(g):
     return gt, gt[torch.from_numpy(g.uniform(size=n_gt) < 0.7)], pred
 
 
-def new_validator():
-    return DetectionValidator.for_run_val("kitti", CLASSES, (0, 1, 2), moving_velocity_thresh=0.1)
+def new_validator(waymo=False):
+    return DetectionValidator.for_run_val("kitti", CLASSES, (0, 1, 2), moving_velocity_thresh=0.1, waymo_metrics=waymo)
 
 
-def batched_path(gt, bm, pred, draws):
-    v = new_validator()
+def batched_path(gt, bm, pred, draws, waymo=False):
+    v = new_validator(waymo)
     v.update_batch(gt, bm, pred, class_draws=draws)
     return v.compute("val/")
 
@@ -71,6 +74,61 @@ def per_frame_path(gts, bms, preds, draws, frames=None):
     for c, m in zip(v.collections, v.metrics):
         out.update(m.compute("val/" + c.tag))
     return out
+
+
+def waymo_per_frame_path(bms, preds):
+    """the reference's way: every frame through every range bin's `update` (the overall class: no class transfer needed)"""
+    from liso_amd.eval.det_validation import RANGE_BINS
+    from liso_amd.eval.od_metrics import WaymoObjectDetectionMetrics
+
+    ms = {f"val/final_result/WAYMO/detection_metrics/{int(lo)}_{int(hi)}m": WaymoObjectDetectionMetrics(min_eval_range_m=lo, max_eval_range_m=hi)
+          for lo, hi in RANGE_BINS}
+    for bm, pred in zip(bms, preds):
+        for m in ms.values():
+            m.update(non_batched_gt_boxes=bm, non_batched_pred_boxes=pred)
+    out = {}
+    for tag, m in ms.items():
+        out.update(m.compute(tag))
+    return out
+
+
+def assign_launch_ms(bm, pred, iters=20):
+    """device time of liso_det_val_assign_f32 alone on the benchmark set's jobs (events around the one launch, median)"""
+    from liso_amd import _lib as L
+    from liso_amd.eval.det_validation import JobTable, match_detections_packed, pack_boxes
+    from liso_amd.utils.device_args import opt_ptr as _p
+
+    at = new_validator(True).assign_tables["benchmark"]
+    g, p = pack_boxes(bm), pack_boxes(pred)
+    o = match_detections_packed(g, p, JobTable(), assign=at)
+    ft, jt = at.device_tables(g["rows"].device)
+    F, G = g["valid"].shape
+    P = p["valid"].shape[1]
+
+    def launch():
+        L.check(L.lib().liso_det_val_assign_f32(F, G, P, _p(g["rows"]), _p(g["valid"]), _p(g["cls"]), _p(p["rows"]), _p(p["valid"]), _p(o["pred_class"]),
+                                                _p(o["iou_bev"]), _p(o["iou_3d"]), at.criteria_mask, L.ptr(ft), len(at.filters), L.ptr(jt), len(at.jobs),
+                                                _p(o["assign_count"]), _p(o["assign_pairs"]), _p(o["assign_gt_in"]), _p(o["assign_pred_in"]),
+                                                L.stream_ptr()), "det_val assign")
+    launch()
+    return event_ms(launch, iters)[0], F * len(at.jobs)
+
+
+def waymo_leg(args, gts, bms, preds, gt, bm, pred, draws):
+    batched_path(gt, bm, pred, draws, True)  # warm-up
+    waymo_per_frame_path(bms[:2], preds[:2])
+    off_ms, off = event_ms(lambda: batched_path(gt, bm, pred, draws), args.iters)
+    on_ms, on = event_ms(lambda: batched_path(gt, bm, pred, draws, True), args.iters)
+    loop_ms, ref = event_ms(lambda: waymo_per_frame_path(bms, preds), args.per_frame_iters)
+    a_ms, cells = assign_launch_ms(bm, pred)
+    same = lambda a, b: (np.isnan(a) and np.isnan(b)) or a == b  # noqa: E731
+    worst = max((abs(on[k] - w) for k, w in ref.items() if "AP@" in k and not (np.isnan(on[k]) and np.isnan(w))), default=0.0)
+    print(json.dumps({
+        "frames": F, "benchmark_gt_per_frame": round(float(bm.valid.sum()) / F, 1), "pred_per_frame": round(float(pred.valid.sum()) / F, 1),
+        "validator_flag_off_ms": round(off_ms, 2), "validator_flag_on_ms": round(on_ms, 2), "waymo_per_frame_loop_ms": round(loop_ms, 1),
+        "flag_on_not_slower_than_off_plus_loop": on_ms <= off_ms + loop_ms, "assign_launch_ms": round(a_ms, 4), "assign_cells": cells,
+        "greedy_results_unchanged": all(same(on[k], w) for k, w in off.items()), "waymo_keys": len(ref),
+        "waymo_keys_equal_per_frame_loop": set(ref) == set(on) - set(off), "max_abs_waymo_ap_difference": worst}))
 
 
 def event_ms(fn, iters):
@@ -106,6 +164,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--per-frame-iters", type=int, default=1)
+    ap.add_argument("--waymo", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     g = np.random.default_rng(0)
@@ -113,6 +172,14 @@ def main():
     gts, bms, preds = ([s[i].to(dev) for s in frames] for i in range(3))
     gt, bm, pred = (Shape.from_list_of_shapes([s[i] for s in frames]).to(dev) for i in range(3))
     draws = torch.from_numpy(g.integers(0, 3, tuple(pred.valid.shape)).astype(np.int32)).to(dev)
+    if args.waymo:
+        gd = np.random.default_rng(1)  # Waymo difficulty levels, 0 and > 0 mixed (a generator of its own: the boxes above stay the same)
+        for s in frames:
+            for b in s[:2]:
+                b.difficulty = torch.from_numpy((gd.integers(0, 3, (b.valid.shape[0], 1)) * (gd.uniform(size=(b.valid.shape[0], 1)) < 0.6)).astype(np.int32))
+        gts, bms = ([s[i].clone().to(dev) for s in frames] for i in range(2))
+        gt, bm = (Shape.from_list_of_shapes([s[i] for s in frames]).to(dev) for i in range(2))
+        return waymo_leg(args, gts, bms, preds, gt, bm, pred, draws)
     batched_path(gt, bm, pred, draws)  # warm-up: library load, job tables on the device
     per_frame_path(gts, bms, preds, draws, frames=2)
     b_ms, b_out = event_ms(lambda: batched_path(gt, bm, pred, draws), args.iters)
