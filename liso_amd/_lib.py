@@ -367,6 +367,10 @@ SIGNATURES = {
     "liso_odometry_sequences": (_i, [_vp] * 11 + [_sz, _vp]),
     "liso_odometry_relative_f64": (_i, [_i, _vp, _vp, _vp, _vp]),
     "liso_correct_kitti_scan_f64": (_i, [_lg, _vp, _vp, _vp]),
+    # include/liso_flow_labels.h
+    "liso_flow_labels_workspace_bytes": (_sz, [_i, _i]),
+    "liso_flow_labels_f32": (_i, [_vp] * 18 + [_sz, _vp]),
+    "liso_kitti_rows_cols_f32": (_i, [_i, _i, _i, _vp, _vp, _d, _i, _i, _vp, _vp, _vp]),
 }
 
 

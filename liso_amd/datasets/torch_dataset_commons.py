@@ -13,6 +13,7 @@ from liso_amd.datasets.label_prep import (  # noqa: F401  (:190-339, :793-876, :
     object_velocity_in_obj_coords,
     select_centermaps_target_confidence,
 )
+from liso_amd.datasets.range_projection import add_lidar_rows_to_kitti_sample  # noqa: F401  (:78-86)
 from liso_amd.datasets.sample_prep import (  # noqa: F401  (:743-902, :1147-1223, :1291-1483, :1870-1899)
     add_bev_flow,
     add_bev_ground_height_occupancy_maps,
