@@ -104,6 +104,28 @@ int liso_pfn_backward(const float* feat, const int* pt_off, const int* voxel_cel
                       const double* moments, int training, const void* grad_canvas, int grad_bf16, float* grad_weight,
                       float* grad_gamma, float* grad_beta, void* partials, void* stream);
 
+/* Sub-range forms: the same four passes on samples [sample0, sample0 + batch) of a voxelisation + decoration made for a LARGER batch
+ * (one voxelisation of a sweep serving several consumers, each with its own weights and its own batch).  feat, pt_off, voxel_cell,
+ * num_voxels and cell_to_voxel are the WHOLE call's arrays, unsliced; canvas / rows / cell_to_row / occupancy / grad_canvas are the
+ * consumer's own and span `batch` samples.  The inputs are only read.  Statistics (training != 0) cover the sub-range's samples alone.
+ * Every output equals, bit for bit, what liso_pillars_voxelize_f32 + liso_pfn_decorate_f32 on those samples' clouds alone followed
+ * by the plain entry point gives: the chunking of the statistics, the pillar -> wave deal and the summation orders are relative to
+ * the sub-range.  sample0 = 0 with the whole batch is the plain entry point.  0 <= sample0, sample0 + batch <= LISO_PILLARS_MAX_BATCH. */
+int liso_pfn_bn_prepare_sub_f32(const float* feat, const int* pt_off, const liso_pillar_cfg* cfg, int sample0, int batch,
+                                const int* num_voxels, const float* weight, const float* gamma, const float* beta,
+                                float* running_mean, float* running_var, float momentum, float eps, int training, float* bn_out,
+                                double* moments, void* partials, void* stream);
+int liso_pfn_forward_scatter_sub(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int sample0,
+                                 int batch, const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas,
+                                 int out_bf16, float* occupancy, void* stream);
+int liso_pfn_forward_rows_sub(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int sample0,
+                              int batch, const int* cell_to_voxel, const float* weight, const float* bn_out, void* rows, int out_bf16,
+                              int row_base, int* cell_to_row, float* occupancy, void* stream);
+int liso_pfn_backward_sub(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int sample0,
+                          int batch, const int* num_voxels, const float* weight, const float* gamma, const float* bn_out,
+                          const double* moments, int training, const void* grad_canvas, int grad_bf16, float* grad_weight,
+                          float* grad_gamma, float* grad_beta, void* partials, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

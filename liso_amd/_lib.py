@@ -151,6 +151,10 @@ SIGNATURES = {
     "liso_pfn_forward_scatter": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "liso_pfn_forward_rows": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "liso_pfn_backward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "liso_pfn_bn_prepare_sub_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "liso_pfn_forward_scatter_sub": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "liso_pfn_forward_rows_sub": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "liso_pfn_backward_sub": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     # include/liso_kabsch.h
     "liso_kabsch_workspace_bytes": (_sz, [_vp]),
     "liso_kabsch_trafos_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -553,6 +557,9 @@ class PillarCfg(ctypes.Structure):
     """mirror of liso_pillar_cfg (include/liso_pillars.h)"""
     _fields_ = [("x_min", _f), ("y_min", _f), ("z_min", _f), ("vx", _f), ("vy", _f), ("vz", _f), ("gx", _i),
                 ("gy", _i), ("max_points", _i), ("max_voxels", _i), ("n_channels", _i)]
+
+
+PILLARS_MAX_BATCH = 32  # LISO_PILLARS_MAX_BATCH (include/liso_pillars.h): samples of one voxelisation call
 
 
 class _Everything:

@@ -463,7 +463,11 @@ __global__ __launch_bounds__(kPfnThreads) void pfn_stats_kernel(const float* __r
                 if (idx == lane + 64) { pj[1] = j; pk[1] = k; }
             }
     }
-    const long n = pt_off[rows];
+    // `pt_off` starts at the first pillar row of the samples in use: their feature rows are [pt_off[0], pt_off[rows]), and the per-wave
+    // chunks are cut from the first of them (0 unless the call takes a sub-range of a larger voxelisation)
+    const long p0 = pt_off[0];
+    const long n = pt_off[rows] - p0;
+    feat += (size_t)p0 * kFP;
     const long waves = (long)gridDim.x * (kPfnThreads / 64);
     const long per = ((n + waves - 1) / waves + 63) / 64 * 64;  // rows per wave, multiple of the 64-row tile
     const long w_id = (long)blockIdx.x * (kPfnThreads / 64) + wave;
@@ -629,6 +633,9 @@ constexpr int kCellsPerBlock = 256;
 // ROWS (the compact canvas): a pillar's row goes to canvas[v] instead of canvas[cell] -- `canvas` is then the [rows, 64] row array of
 // this call -- and the last blocks write the occupancy map and the caller's cell -> row map (cell_to_voxel + row_base, 0 = empty: the
 // rows of several calls may share one array) but no zeros: the rows of unused pillars are never written.
+// Sub-range of a larger voxelisation: every array starts at the sub-range's first sample, `rows` / `total_cells` count its pillar rows
+// and cells; the VALUES still number the whole voxelisation, so `cell_base` (its first cell) comes off voxel_cell and `row_base`
+// arrives less its first pillar row.
 template <int C, typename OutT, bool ROWS>
 __global__ __launch_bounds__(kPfnThreads) void pfn_forward_kernel(const float* __restrict__ feat, const int* __restrict__ pt_off,
                                                                   const int* __restrict__ voxel_cell, int rows, int max_points,
@@ -636,7 +643,7 @@ __global__ __launch_bounds__(kPfnThreads) void pfn_forward_kernel(const float* _
                                                                   const int* __restrict__ cell_to_voxel,
                                                                   const float* __restrict__ weight, const float* __restrict__ bn,
                                                                   OutT* __restrict__ canvas, float* __restrict__ occupancy,
-                                                                  int* __restrict__ map_out, int row_base) {
+                                                                  int* __restrict__ map_out, int row_base, long cell_base) {
     constexpr int F = C + 6;
     constexpr int kChunks = kOut * (int)sizeof(OutT) / 16;  // 16-B chunks per cell (8 for bf16, 16 for fp32)
     __shared__ __attribute__((aligned(16))) float frow[kPfnThreads / 64][kStage][kFP];
@@ -692,7 +699,7 @@ __global__ __launch_bounds__(kPfnThreads) void pfn_forward_kernel(const float* _
                 for (int k = 0; k < F; k++) x = fmaf(w[k], f[k], x);
                 best = fmaxf(best, fmaxf(fmaf(x, scale, shift), 0.f));
             }
-            store_out<OutT>(canvas + (size_t)(ROWS ? v0 + g : cell) * kOut + lane, best);
+            store_out<OutT>(canvas + (size_t)(ROWS ? v0 + g : cell - cell_base) * kOut + lane, best);
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -703,7 +710,7 @@ template <int C, typename GT>
 __global__ __launch_bounds__(kPfnThreads) void pfn_backward_kernel(const float* __restrict__ feat, const int* __restrict__ pt_off,
                                                                    const int* __restrict__ voxel_cell, int rows, int max_points,
                                                                    const float* __restrict__ weight, const float* __restrict__ bn,
-                                                                   const GT* __restrict__ grad_canvas,
+                                                                   const GT* __restrict__ grad_canvas, long cell_base,
                                                                    float* __restrict__ partials) {
     constexpr int F = C + 6, NA = F + 2;
     __shared__ __attribute__((aligned(16))) float frow[kPfnThreads / 64][kStage][kFP];
@@ -741,7 +748,7 @@ __global__ __launch_bounds__(kPfnThreads) void pfn_backward_kernel(const float* 
                 if (y > best) { best = y; best_s = s; best_x = x; }
             }
             if (num < max_points && pad_val > best) { best = pad_val; best_s = -1; best_x = 0.f; }
-            const float gy = load_in<GT>(grad_canvas + (size_t)cell * kOut + lane);
+            const float gy = load_in<GT>(grad_canvas + (size_t)(cell - cell_base) * kOut + lane);
             const float dz = best > 0.f ? gy : 0.f;  // ReLU gate; the max routes the gradient to one row
             if (best_s >= 0) {
                 const float* f = frow[wave][r0 + best_s];
@@ -837,6 +844,12 @@ __global__ __launch_bounds__(64) void pfn_backward_finalize_kernel(const double*
 inline bool cfg_ok(const liso_pillar_cfg* c, int batch) {
     return c && batch >= 1 && batch <= LISO_PILLARS_MAX_BATCH && c->gx > 0 && c->gy > 0 && c->max_points >= 1 &&
            c->max_points <= kMaxPts && c->max_voxels >= 1 && c->n_channels >= 3 && c->n_channels <= 5;
+}
+
+// samples [sample0, sample0 + batch) of a voxelisation made for a larger batch (sample0 == 0: any call)
+inline bool sub_ok(const liso_pillar_cfg* c, int sample0, int batch) {
+    return cfg_ok(c, batch) && sample0 >= 0 && sample0 <= LISO_PILLARS_MAX_BATCH - batch &&
+           (long)(sample0 + batch) * c->max_voxels < (1L << 31);
 }
 
 inline BatchInfo make_batch(const int* off, int batch) {
@@ -949,11 +962,11 @@ int liso_pfn_decorate_f32(const float* points, const liso_pillar_cfg* cfg, int b
     return check_launch();
 }
 
-int liso_pfn_bn_prepare_f32(const float* feat, const int* pt_off, const liso_pillar_cfg* cfg, int batch, const int* num_voxels,
-                            const float* weight, const float* gamma, const float* beta, float* running_mean,
-                            float* running_var, float momentum, float eps, int training, float* bn_out, double* moments,
-                            void* partials, void* stream) {
-    if (!cfg_ok(cfg, batch) || !gamma || !beta || !running_mean || !running_var || !bn_out) return LISO_EINVAL;
+int liso_pfn_bn_prepare_sub_f32(const float* feat, const int* pt_off, const liso_pillar_cfg* cfg, int sample0, int batch,
+                                const int* num_voxels, const float* weight, const float* gamma, const float* beta,
+                                float* running_mean, float* running_var, float momentum, float eps, int training, float* bn_out,
+                                double* moments, void* partials, void* stream) {
+    if (!sub_ok(cfg, sample0, batch) || !gamma || !beta || !running_mean || !running_var || !bn_out) return LISO_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (!training) {
         pfn_bn_eval_kernel<<<1, 64, 0, st>>>(gamma, beta, running_mean, running_var, eps, bn_out);
@@ -962,6 +975,8 @@ int liso_pfn_bn_prepare_f32(const float* feat, const int* pt_off, const liso_pil
     if (!feat || !pt_off || !num_voxels || !weight || !moments || !partials) return LISO_EINVAL;
     const int rows = batch * cfg->max_voxels;
     const int grid = kPfnGrid;
+    pt_off += (size_t)sample0 * cfg->max_voxels;  // (the kernel takes the feature rows' base from pt_off[0])
+    num_voxels += sample0;
 #define LISO_PREP(CC)                                                                                                     \
     do {                                                                                                                  \
         pfn_stats_kernel<CC><<<grid, kPfnThreads, 0, st>>>(feat, pt_off, rows, (double*)partials);                           \
@@ -978,21 +993,35 @@ int liso_pfn_bn_prepare_f32(const float* feat, const int* pt_off, const liso_pil
     return check_launch();
 }
 
-static int pfn_forward_launch(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
-                              const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas, int out_bf16,
+int liso_pfn_bn_prepare_f32(const float* feat, const int* pt_off, const liso_pillar_cfg* cfg, int batch, const int* num_voxels,
+                            const float* weight, const float* gamma, const float* beta, float* running_mean,
+                            float* running_var, float momentum, float eps, int training, float* bn_out, double* moments,
+                            void* partials, void* stream) {
+    return liso_pfn_bn_prepare_sub_f32(feat, pt_off, cfg, 0, batch, num_voxels, weight, gamma, beta, running_mean, running_var, momentum,
+                                       eps, training, bn_out, moments, partials, stream);
+}
+
+static int pfn_forward_launch(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int sample0,
+                              int batch, const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas, int out_bf16,
                               float* occupancy, int* map_out, int row_base, bool compact, void* stream) {
-    if (!cfg_ok(cfg, batch) || !feat || !pt_off || !voxel_cell || !cell_to_voxel || !weight || !bn_out || !canvas || !occupancy)
+    if (!sub_ok(cfg, sample0, batch) || !feat || !pt_off || !voxel_cell || !cell_to_voxel || !weight || !bn_out || !canvas || !occupancy)
         return LISO_EINVAL;
     if (out_bf16 != LISO_ELEM_F32 && out_bf16 != LISO_ELEM_BF16 && out_bf16 != LISO_ELEM_F16) return LISO_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const long cells = (long)batch * cfg->gx * cfg->gy;
     const int rows = batch * cfg->max_voxels;
+    // the sub-range's slice of every input; feat stays whole (pt_off indexes it), canvas / occupancy / map_out are this call's own
+    const long cell_base = (long)sample0 * cfg->gx * cfg->gy;
+    pt_off += (size_t)sample0 * cfg->max_voxels;
+    voxel_cell += (size_t)sample0 * cfg->max_voxels;
+    cell_to_voxel += cell_base;
+    row_base -= sample0 * cfg->max_voxels;  // (cell_to_voxel holds rows of the whole voxelisation, + 1)
     const int zero_blocks = (int)((cells + kCellsPerBlock - 1) / kCellsPerBlock);
     const int groups = (rows + kGroup - 1) / kGroup;
     int pfn_blocks = (groups + kPfnThreads / 64 - 1) / (kPfnThreads / 64);
     if (pfn_blocks > 4096) pfn_blocks = 4096;
     const unsigned grid = (unsigned)(zero_blocks + pfn_blocks);
-#define LISO_FWD_(CC, T, R) pfn_forward_kernel<CC, T, R><<<grid, kPfnThreads, 0, st>>>(feat, pt_off, voxel_cell, rows, cfg->max_points, cells, zero_blocks, cell_to_voxel, weight, bn_out, (T*)canvas, occupancy, map_out, row_base)
+#define LISO_FWD_(CC, T, R) pfn_forward_kernel<CC, T, R><<<grid, kPfnThreads, 0, st>>>(feat, pt_off, voxel_cell, rows, cfg->max_points, cells, zero_blocks, cell_to_voxel, weight, bn_out, (T*)canvas, occupancy, map_out, row_base, cell_base)
 #define LISO_FWD(CC, T) do { if (compact) LISO_FWD_(CC, T, true); else LISO_FWD_(CC, T, false); } while (0)
     switch (cfg->n_channels * 3 + out_bf16) {  // (n_channels 3..5, element code 0..2)
         case 9: LISO_FWD(3, float); break;
@@ -1010,38 +1039,56 @@ static int pfn_forward_launch(const float* feat, const int* pt_off, const int* v
     return check_launch();
 }
 
+int liso_pfn_forward_scatter_sub(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int sample0,
+                                 int batch, const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas,
+                                 int out_bf16, float* occupancy, void* stream) {
+    return pfn_forward_launch(feat, pt_off, voxel_cell, cfg, sample0, batch, cell_to_voxel, weight, bn_out, canvas, out_bf16, occupancy,
+                              nullptr, 0, false, stream);
+}
+
 int liso_pfn_forward_scatter(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
                              const int* cell_to_voxel, const float* weight, const float* bn_out, void* canvas, int out_bf16,
                              float* occupancy, void* stream) {
-    return pfn_forward_launch(feat, pt_off, voxel_cell, cfg, batch, cell_to_voxel, weight, bn_out, canvas, out_bf16, occupancy, nullptr,
-                              0, false, stream);
+    return liso_pfn_forward_scatter_sub(feat, pt_off, voxel_cell, cfg, 0, batch, cell_to_voxel, weight, bn_out, canvas, out_bf16,
+                                        occupancy, stream);
+}
+
+int liso_pfn_forward_rows_sub(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int sample0,
+                              int batch, const int* cell_to_voxel, const float* weight, const float* bn_out, void* rows, int out_bf16,
+                              int row_base, int* cell_to_row, float* occupancy, void* stream) {
+    if (!cell_to_row || row_base < 0 || (long)row_base + (long)batch * (cfg ? cfg->max_voxels : 0) >= (1L << 31)) return LISO_EINVAL;
+    return pfn_forward_launch(feat, pt_off, voxel_cell, cfg, sample0, batch, cell_to_voxel, weight, bn_out, rows, out_bf16, occupancy,
+                              cell_to_row, row_base, true, stream);
 }
 
 int liso_pfn_forward_rows(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
                           const int* cell_to_voxel, const float* weight, const float* bn_out, void* rows, int out_bf16, int row_base,
                           int* cell_to_row, float* occupancy, void* stream) {
-    if (!cell_to_row || row_base < 0 || (long)row_base + (long)batch * (cfg ? cfg->max_voxels : 0) >= (1L << 31)) return LISO_EINVAL;
-    return pfn_forward_launch(feat, pt_off, voxel_cell, cfg, batch, cell_to_voxel, weight, bn_out, rows, out_bf16, occupancy, cell_to_row,
-                              row_base, true, stream);
+    return liso_pfn_forward_rows_sub(feat, pt_off, voxel_cell, cfg, 0, batch, cell_to_voxel, weight, bn_out, rows, out_bf16, row_base,
+                                     cell_to_row, occupancy, stream);
 }
 
-int liso_pfn_backward(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
-                      const int* num_voxels, const float* weight, const float* gamma, const float* bn_out,
-                      const double* moments, int training, const void* grad_canvas, int grad_bf16, float* grad_weight,
-                      float* grad_gamma, float* grad_beta, void* partials, void* stream) {
-    if (!cfg_ok(cfg, batch) || !feat || !pt_off || !voxel_cell || !num_voxels || !weight || !gamma || !bn_out || !grad_canvas ||
+int liso_pfn_backward_sub(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int sample0,
+                          int batch, const int* num_voxels, const float* weight, const float* gamma, const float* bn_out,
+                          const double* moments, int training, const void* grad_canvas, int grad_bf16, float* grad_weight,
+                          float* grad_gamma, float* grad_beta, void* partials, void* stream) {
+    if (!sub_ok(cfg, sample0, batch) || !feat || !pt_off || !voxel_cell || !num_voxels || !weight || !gamma || !bn_out || !grad_canvas ||
         !grad_weight || !grad_gamma || !grad_beta || !partials || (training && !moments))
         return LISO_EINVAL;
     if (grad_bf16 != LISO_ELEM_F32 && grad_bf16 != LISO_ELEM_BF16 && grad_bf16 != LISO_ELEM_F16) return LISO_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int rows = batch * cfg->max_voxels;
     const int grid = pfn_grid((rows + kGroup - 1) / kGroup);
+    const long cell_base = (long)sample0 * cfg->gx * cfg->gy;  // (grad_canvas is the sub-range's own: [batch, gx, gy, 64])
+    pt_off += (size_t)sample0 * cfg->max_voxels;
+    voxel_cell += (size_t)sample0 * cfg->max_voxels;
+    num_voxels += sample0;
 #define LISO_BWD(CC, T)                                                                                              \
     do {                                                                                                             \
         constexpr int NA_ = CC + 8;                                                                                  \
         double* tot_ = (double*)((float*)partials + (size_t)kPfnGrid * (11 + 2) * kOut);                             \
         pfn_backward_kernel<CC, T><<<grid, kPfnThreads, 0, st>>>(feat, pt_off, voxel_cell, rows, cfg->max_points,     \
-                                                                 weight, bn_out, (const T*)grad_canvas,             \
+                                                                 weight, bn_out, (const T*)grad_canvas, cell_base,  \
                                                                  (float*)partials);                                  \
         pfn_backward_reduce_kernel<NA_><<<NA_, 1024, 0, st>>>((const float*)partials, grid, tot_);                    \
         pfn_backward_finalize_kernel<CC><<<1, 64, 0, st>>>(tot_, num_voxels, batch, cfg->max_points, weight, gamma,   \
@@ -1061,6 +1108,14 @@ int liso_pfn_backward(const float* feat, const int* pt_off, const int* voxel_cel
     }
 #undef LISO_BWD
     return check_launch();
+}
+
+int liso_pfn_backward(const float* feat, const int* pt_off, const int* voxel_cell, const liso_pillar_cfg* cfg, int batch,
+                      const int* num_voxels, const float* weight, const float* gamma, const float* bn_out,
+                      const double* moments, int training, const void* grad_canvas, int grad_bf16, float* grad_weight,
+                      float* grad_gamma, float* grad_beta, void* partials, void* stream) {
+    return liso_pfn_backward_sub(feat, pt_off, voxel_cell, cfg, 0, batch, num_voxels, weight, gamma, bn_out, moments, training,
+                                 grad_canvas, grad_bf16, grad_weight, grad_gamma, grad_beta, partials, stream);
 }
 
 }  // extern "C"

@@ -95,14 +95,25 @@ def pillar_prep(points, offsets, pcfg):
     return pt_off, feat, voxel_cell, num_voxels, cell_to_voxel
 
 
-def _pfn_statistics(weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum, eps, prep):
+def _is_sub_range(prep, sample0, B):
+    """does a consumer of samples [sample0, sample0 + B) of `prep` need the sub-range entry points (include/liso_pillars.h)?  Only when
+    the voxelisation was made for more samples than it uses; the whole batch goes through the plain ones as ever."""
+    total = prep[3].shape[0]  # num_voxels: one entry per voxelised sample
+    assert 0 <= sample0 and sample0 + B <= total, (sample0, B, total)
+    return sample0 != 0 or total != B
+
+
+def _pfn_statistics(weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum, eps, prep, sample0=0):
     """what both canvas forms share: the voxelisation products (`prep`, computed here unless given) and the BatchNorm1d statistics ->
-    (prep, weight fp32 contiguous, bn_out [4 * 64], moments [80]); runs on the current stream of the points' device"""
+    (prep, weight fp32 contiguous, bn_out [4 * 64], moments [80]); runs on the current stream of the points' device.
+    `sample0`: `prep` was made for a larger batch, this call takes its samples [sample0, sample0 + len(offsets) - 1) -- statistics
+    over those alone -- and only reads it."""
     L.require_cuda(points, weight)
     lib = L.lib()
     dev = points.device
     B = len(offsets) - 1
     if prep is None:
+        assert sample0 == 0, sample0
         prep = pillar_prep(points, offsets, pcfg)
     pt_off, feat, _, num_voxels, _ = prep
     weight = weight.contiguous().float()
@@ -110,10 +121,12 @@ def _pfn_statistics(weight, gamma, beta, running_mean, running_var, points, offs
         bn_out = torch.empty(4 * 64, dtype=torch.float32, device=dev)
         moments = torch.empty(80, dtype=torch.float64, device=dev)
         partials = torch.empty(lib.liso_pfn_partials_bytes(), dtype=torch.uint8, device=dev)
-        L.check(lib.liso_pfn_bn_prepare_f32(L.ptr(feat), L.ptr(pt_off), ctypes.byref(pcfg), B, L.ptr(num_voxels),
-                                            L.ptr(weight), L.ptr(gamma), L.ptr(beta), L.ptr(running_mean),
-                                            L.ptr(running_var), float(momentum), float(eps), int(training),
-                                            L.ptr(bn_out), L.ptr(moments), L.ptr(partials), L.stream_ptr()), "pfn_bn_prepare")
+        tail = (L.ptr(num_voxels), L.ptr(weight), L.ptr(gamma), L.ptr(beta), L.ptr(running_mean), L.ptr(running_var), float(momentum),
+                float(eps), int(training), L.ptr(bn_out), L.ptr(moments), L.ptr(partials), L.stream_ptr())
+        if _is_sub_range(prep, sample0, B):
+            L.check(lib.liso_pfn_bn_prepare_sub_f32(L.ptr(feat), L.ptr(pt_off), ctypes.byref(pcfg), sample0, B, *tail), "pfn_bn_prepare_sub")
+        else:
+            L.check(lib.liso_pfn_bn_prepare_f32(L.ptr(feat), L.ptr(pt_off), ctypes.byref(pcfg), B, *tail), "pfn_bn_prepare")
     return prep, weight, bn_out, moments
 
 
@@ -122,14 +135,15 @@ class _PillarFeatureScatter(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum, eps,
-                out_dtype, out=None, prep=None):
+                out_dtype, out=None, prep=None, sample0=0):
         code = L.elem_code(out_dtype)  # (TypeError before anything is allocated or launched: the canvas rows are sized by out_dtype)
         lib = L.lib()
         dev = points.device
         B = len(offsets) - 1
         prep, weight, bn_out, moments = _pfn_statistics(weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training,
-                                                        momentum, eps, prep)
+                                                        momentum, eps, prep, sample0)
         pt_off, feat, voxel_cell, num_voxels, cell_to_voxel = prep
+        sub = _is_sub_range(prep, sample0, B)
         with torch.cuda.device(dev):
             st = L.stream_ptr()
             if out is not None:  # caller-owned destination (static graph inputs): [B, gx, gy, 64] rows + occupancy, both dense
@@ -139,14 +153,16 @@ class _PillarFeatureScatter(torch.autograd.Function):
             else:
                 canvas = torch.empty((B, pcfg.gx, pcfg.gy, 64), dtype=out_dtype, device=dev)  # written densely by the kernel
                 occupancy = torch.empty((B, 1, pcfg.gx, pcfg.gy), dtype=torch.float32, device=dev)
-            L.check(L.TIMER.launch("pfn_forward_scatter", lambda: lib.liso_pfn_forward_scatter(
-                L.ptr(feat), L.ptr(pt_off), L.ptr(voxel_cell), ctypes.byref(pcfg), B, L.ptr(cell_to_voxel), L.ptr(weight),
-                L.ptr(bn_out), L.ptr(canvas), code, L.ptr(occupancy), st),
+            head = (L.ptr(feat), L.ptr(pt_off), L.ptr(voxel_cell), ctypes.byref(pcfg))
+            tail = (L.ptr(cell_to_voxel), L.ptr(weight), L.ptr(bn_out), L.ptr(canvas), code, L.ptr(occupancy), st)
+            L.check(L.TIMER.launch("pfn_forward_scatter", lambda: (lib.liso_pfn_forward_scatter_sub(*head, sample0, B, *tail) if sub
+                                                                   else lib.liso_pfn_forward_scatter(*head, B, *tail)),
                 # algorithmic bytes: points read once + dense canvas (its own element size) + occupancy written once
-                units=points.numel() * 4 + canvas.numel() * canvas.element_size() + occupancy.numel() * 4),
+                units=(offsets[-1] - offsets[0]) * points.shape[1] * 4 + canvas.numel() * canvas.element_size() + occupancy.numel() * 4),
                 "pfn_forward_scatter")
+        # (the saved tensors are the prep's own: a voxelisation shared with another consumer stays alive until this backward has run)
         ctx.save_for_backward(feat, pt_off, voxel_cell, num_voxels, weight, gamma, bn_out, moments)
-        ctx.pcfg, ctx.B, ctx.training = pcfg, B, bool(training)
+        ctx.pcfg, ctx.B, ctx.training, ctx.sample0, ctx.sub = pcfg, B, bool(training), sample0, sub
         ctx.mark_non_differentiable(occupancy)
         return canvas.permute(0, 3, 1, 2), occupancy
 
@@ -165,16 +181,19 @@ class _PillarFeatureScatter(torch.autograd.Function):
         gb = torch.empty(64, dtype=torch.float32, device=dev)
         partials = torch.empty(lib.liso_pfn_partials_bytes(), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            L.check(lib.liso_pfn_backward(L.ptr(feat), L.ptr(pt_off), L.ptr(voxel_cell), ctypes.byref(ctx.pcfg), ctx.B,
-                                          L.ptr(num_voxels), L.ptr(weight), L.ptr(gamma), L.ptr(bn_out), L.ptr(moments),
-                                          int(ctx.training), L.ptr(g), L.elem_code(g.dtype), L.ptr(gw), L.ptr(gg),
-                                          L.ptr(gb), L.ptr(partials), L.stream_ptr()), "pfn_backward")
-        return gw, gg, gb, None, None, None, None, None, None, None, None, None, None, None
+            head = (L.ptr(feat), L.ptr(pt_off), L.ptr(voxel_cell), ctypes.byref(ctx.pcfg))
+            tail = (L.ptr(num_voxels), L.ptr(weight), L.ptr(gamma), L.ptr(bn_out), L.ptr(moments), int(ctx.training), L.ptr(g),
+                    L.elem_code(g.dtype), L.ptr(gw), L.ptr(gg), L.ptr(gb), L.ptr(partials), L.stream_ptr())
+            if ctx.sub:
+                L.check(lib.liso_pfn_backward_sub(*head, ctx.sample0, ctx.B, *tail), "pfn_backward_sub")
+            else:
+                L.check(lib.liso_pfn_backward(*head, ctx.B, *tail), "pfn_backward")
+        return gw, gg, gb, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 @torch.no_grad()
 def pillar_rows(weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum, eps, out_dtype, out=None,
-                prep=None):
+                prep=None, sample0=0):
     """The encoder's forward with a COMPACT canvas (mfma_conv.PillarCanvas; include/liso_pillars.h: liso_pfn_forward_rows): the same
     statistics and the same rows as `_PillarFeatureScatter`, stored per pillar -- the dense canvas, zeros in all but 1-6 % of its
     cells, is not written.  No autograd node: inference only.  `out`: the PillarCanvas (slice) to write into."""
@@ -185,8 +204,9 @@ def pillar_rows(weight, gamma, beta, running_mean, running_var, points, offsets,
     dev = points.device
     B = len(offsets) - 1
     prep, weight, bn_out, _ = _pfn_statistics(weight, gamma, beta, running_mean, running_var, points, offsets, pcfg, training, momentum,
-                                              eps, prep)
+                                              eps, prep, sample0)
     pt_off, feat, voxel_cell, num_voxels, cell_to_voxel = prep
+    sub = _is_sub_range(prep, sample0, B)
     if out is None:
         out = PillarCanvas.empty(B, (pcfg.gx, pcfg.gy), pcfg.max_voxels, out_dtype, dev)
     R = B * pcfg.max_voxels
@@ -196,13 +216,15 @@ def pillar_rows(weight, gamma, beta, running_mean, running_var, points, offsets,
     with torch.cuda.device(dev):
         st = L.stream_ptr()
         cells = B * pcfg.gx * pcfg.gy
-        L.check(L.TIMER.launch("pfn_forward_scatter", lambda: lib.liso_pfn_forward_rows(
-            L.ptr(feat), L.ptr(pt_off), L.ptr(voxel_cell), ctypes.byref(pcfg), B, L.ptr(cell_to_voxel), L.ptr(weight),
-            L.ptr(bn_out), L.ptr(rows), code, out.row_base, L.ptr(out.cell_map), L.ptr(out.occupancy), st),
+        head = (L.ptr(feat), L.ptr(pt_off), L.ptr(voxel_cell), ctypes.byref(pcfg))
+        tail = (L.ptr(cell_to_voxel), L.ptr(weight), L.ptr(bn_out), L.ptr(rows), code, out.row_base, L.ptr(out.cell_map),
+                L.ptr(out.occupancy), st)
+        L.check(L.TIMER.launch("pfn_forward_scatter", lambda: (lib.liso_pfn_forward_rows_sub(*head, sample0, B, *tail) if sub
+                                                               else lib.liso_pfn_forward_rows(*head, B, *tail)),
             # bytes the launch moves, the terms known on the host: points read once, the voxeliser's map read, the caller's map and
             # the occupancy written (12 B per cell); the pillars' rows are not counted -- their number is only known on the device
             # (1-6 % of the cells: 1-2 MB per sweep at 512^2), so the figure is a lower bound of a few per cent
-            units=points.numel() * 4 + cells * 12),
+            units=(offsets[-1] - offsets[0]) * points.shape[1] * 4 + cells * 12),
             "pfn_forward_rows")
     return out
 
@@ -284,10 +306,16 @@ class PointsPillarFeatureNetWrapper(nn.Module):
 
     def extract_pts_feat(self, pts, out=None, prep=None, compact=False):
         """reference :86-102.  `out` (extension): (canvas rows [B, gx, gy, 64], occupancy [B, 1, gx, gy]) to write into;
-        `prep` (extension): the result of `prepare(pts)` for the same clouds; `compact` (extension, inference only): the canvas as a
+        `prep` (extension): the result of `prepare(pts)` for the same clouds, or `(*prepare(more), sample0, batch)`: `pts` are the clouds
+        [sample0, sample0 + batch) of a `prepare` call on more of them (one voxelisation of a sweep, several consumers; only read); `compact` (extension, inference only): the canvas as a
         mfma_conv.PillarCanvas (`out`: one to write into) -> (PillarCanvas, its occupancy map)"""
         L.elem_code(self.out_dtype)  # an unsupported canvas dtype raises here, before any launch
-        if prep is not None:
+        sample0 = 0
+        if prep is not None and len(prep) == 5:
+            cat, offsets, prep, sample0, batch = prep
+            assert 0 <= sample0 and sample0 + batch < len(offsets), (sample0, batch, len(offsets))
+            offsets = offsets[sample0:sample0 + batch + 1]  # (absolute rows of `cat`: the consumers only take differences)
+        elif prep is not None:
             cat, offsets, prep = prep
         else:
             cat, offsets = self._cat(pts)
@@ -300,11 +328,11 @@ class PointsPillarFeatureNetWrapper(nn.Module):
         if compact:
             assert not torch.is_grad_enabled(), "the compact canvas has no backward: inference only"
             canvas = pillar_rows(lyr.linear.weight, lyr.norm.weight, lyr.norm.bias, lyr.norm.running_mean, lyr.norm.running_var, cat,
-                                 offsets, self._pcfg(C), training, lyr.norm.momentum, lyr.norm.eps, self.out_dtype, out, prep)
+                                 offsets, self._pcfg(C), training, lyr.norm.momentum, lyr.norm.eps, self.out_dtype, out, prep, sample0)
             return canvas, canvas.occupancy
         x, occ = _PillarFeatureScatter.apply(lyr.linear.weight, lyr.norm.weight, lyr.norm.bias, lyr.norm.running_mean,
                                              lyr.norm.running_var, cat, offsets, self._pcfg(C), training,
-                                             lyr.norm.momentum, lyr.norm.eps, self.out_dtype, out, prep)
+                                             lyr.norm.momentum, lyr.norm.eps, self.out_dtype, out, prep, sample0)
         return x, occ
 
     def forward(self, pcl_t0, img_t0=None, out=None, prep=None, compact=False):

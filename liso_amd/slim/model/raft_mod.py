@@ -95,30 +95,60 @@ class RAFT(nn.Module):
         return all(getattr(e, "fold_inference", True) and MC._norm_kind(e.norm1) is not None and MC.sparse_stem_covers(shape, dtype, e.conv1)
                    for e in (self.fnet, self.cnet))
 
-    def encode_pillars(self, pcl_t0, pcl_t1, out=None, compact=False):
+    encode_once = True  # (False: two encoder calls in inference too -- A/B runs and tests)
+
+    def encodes_once(self, n_pairs):
+        """does `encode_pillars` put both sweeps of `n_pairs` pairs through ONE encoder call?  In inference only: without gradients
+        and with the encoder's BatchNorm1d on its running statistics nothing couples the samples of a call, so one call over 2B
+        clouds writes what two calls over B write, bit for bit, with one voxelisation (~14 launches) instead of two.  Training keeps
+        two calls: its batch statistics are per call, as in the reference."""
+        from liso_amd import _lib as L
+
+        pp = self.pp_layer
+        norm = pp.pts_voxel_encoder.pfn_layers[0].norm
+        if not self.encode_once or torch.is_grad_enabled() or (pp.training and norm.training):
+            return False
+        # (what one voxelisation call takes: include/liso_pillars.h LISO_PILLARS_MAX_BATCH, and 4 M cells for its one-block scan)
+        return 2 * n_pairs <= L.PILLARS_MAX_BATCH and 2 * n_pairs * pp.grid[0] * pp.grid[1] <= 4096 * 1024
+
+    def encode_pillars(self, pcl_t0, pcl_t1, out=None, compact=False, prep=None):
         """the pillar canvases of both sweeps: (img_t0, occ_t0, img_t1, occ_t1); differentiable w.r.t. the pillar encoder's
         parameters when gradients are enabled.  `out` = (rows [2B, gx, gy, 64], occupancy [2B, 1, gx, gy]): both sweeps are
         written into these buffers (static hipGraph inputs: no copy, and the batch of both sweeps needs no concatenation);
         the result then carries a fifth element, the stacked canvas [2B, 64, gx, gy].
         `compact` (inference only): one mfma_conv.PillarCanvas of 2B samples (`out`: the one to write into) holds both sweeps -- rows,
-        cell -> row map, occupancy -- and the result is (its first B samples, occ_t0, its last B, occ_t1, the whole, occupancy [2B])."""
+        cell -> row map, occupancy -- and the result is (its first B samples, occ_t0, its last B, occ_t1, the whole, occupancy [2B]).
+        Inference (`encodes_once`) runs ONE encoder call over the clouds of both sweeps, t0 first; `prep`: the caller's
+        `self.pp_layer.prepare([*pcl_t0, *pcl_t1])` for that call (a trainer that shares the voxelisation with another consumer)."""
+        B = len(pcl_t0)
+        assert len(pcl_t1) == B
+        pp = self.pp_layer
+        once = self.encodes_once(B) and pcl_t0[0].is_cuda  # (the one-call form is the device path's; anything else keeps two plain calls)
+        assert prep is None or once, "a prepared voxelisation of both sweeps needs the one-call form"
         if compact:
             from liso_amd.utils.mfma_conv import PillarCanvas
 
-            B = len(pcl_t0)
-            assert len(pcl_t1) == B
-            pp = self.pp_layer
             both = out if out is not None else PillarCanvas.empty(2 * B, pp.grid, pp.max_voxels, pp.out_dtype, pcl_t0[0].device)
             assert isinstance(both, PillarCanvas) and both.shape[0] == 2 * B and both.row_base == 0
-            a, _ = pp(pcl_t0, out=both[:B], compact=True)
-            b, _ = pp(pcl_t1, out=both[B:], compact=True)
+            if once:
+                pp([*pcl_t0, *pcl_t1], out=both, prep=prep, compact=True)
+                a, b = both[:B], both[B:]
+            else:
+                a, _ = pp(pcl_t0, out=both[:B], compact=True)
+                b, _ = pp(pcl_t1, out=both[B:], compact=True)
             return (a, a.occupancy, b, b.occupancy, both, both.occupancy)
         if out is None:
-            return (*self.pp_layer(pcl_t0), *self.pp_layer(pcl_t1))
+            if once:
+                x, occ = pp([*pcl_t0, *pcl_t1]) if prep is None else pp([*pcl_t0, *pcl_t1], prep=prep)
+                return (x[:B], occ[:B], x[B:], occ[B:])
+            return (*pp(pcl_t0), *pp(pcl_t1))
         rows, occ = out
-        B = rows.shape[0] // 2
-        a = self.pp_layer(pcl_t0, out=(rows[:B], occ[:B]))
-        b = self.pp_layer(pcl_t1, out=(rows[B:], occ[B:]))
+        assert rows.shape[0] == 2 * B, (rows.shape, B)
+        if once:
+            x, _ = pp([*pcl_t0, *pcl_t1], out=(rows, occ), prep=prep)
+            return (x[:B], occ[:B], x[B:], occ[B:], x)
+        a = pp(pcl_t0, out=(rows[:B], occ[:B]))
+        b = pp(pcl_t1, out=(rows[B:], occ[B:]))
         return (*a, *b, rows.permute(0, 3, 1, 2))
 
     def infer_forward_direction(self, pcl_t0, pcl_t1, canvases=None):

@@ -715,15 +715,35 @@ class SlimTrainer:
 
 class _Prefetched:
     """what the pipeline of LisoLoopTrainer holds for one announced sample pair: the point flow of stage A and, after stage B, the
-    target maps / boxes and the cluster count (pinned host tensor) -- each guarded by the event recorded behind its work"""
-    __slots__ = ("pair", "flow", "done", "targets", "boxes", "cluster_count")
+    target maps / boxes and the cluster count (pinned host tensor) -- each guarded by the event recorded behind its work.  `shared`:
+    the voxelisation of the inference batch the pair went through (_SharedVoxelisation), `index`: the pair's place in that batch."""
+    __slots__ = ("pair", "flow", "done", "targets", "boxes", "cluster_count", "shared", "index")
 
-    def __init__(self, pair, flow, done, targets=None, boxes=None, cluster_count=None):
+    def __init__(self, pair, flow, done, targets=None, boxes=None, cluster_count=None, shared=None, index=None):
         self.pair, self.flow, self.done = pair, flow, done
         self.targets, self.boxes, self.cluster_count = targets, boxes, cluster_count
+        self.shared, self.index = shared, index
 
     def is_for(self, pair):
         return self.pair[0] is pair[0] and self.pair[1] is pair[1]
+
+
+class _SharedVoxelisation:
+    """the one voxelisation of an inference batch (stage A: the t0 sweeps of its pairs, then the t1 sweeps), kept for the detector
+    steps on those pairs: `prep` = pp_layer.prepare(clouds), `ready` = the event recorded right behind it on the stream that issued
+    it, `geometry` = the pillar geometry it was made with.  It lives exactly as long as a pipeline entry of one of its pairs or a
+    detector step's autograd node refers to it; the consumers only read it."""
+    __slots__ = ("prep", "clouds", "ready", "geometry", "seen")
+
+    def __init__(self, prep, clouds, ready, geometry):
+        self.prep, self.clouds, self.ready, self.geometry = prep, clouds, ready, geometry
+        self.seen = set()  # streams other than the issuing one that its tensors are marked as in use on
+
+
+def _pillar_geometry(pfn):
+    """what must agree for two PointsPillarFeatureNetWrapper to voxelise a cloud identically"""
+    return (tuple(float(v) for v in pfn.pc_range), tuple(float(v) for v in pfn.voxel_size), tuple(pfn.grid), pfn.max_num_points,
+            pfn.max_voxels, pfn.num_input_channels)
 
 
 class _BatchedTargets(dict):
@@ -766,14 +786,17 @@ class LisoLoopTrainer:
     Box-DB augmentation and tracking between the stages are outside this loop."""
 
     def __init__(self, cfg, device, compute_dtype=torch.float32, total_steps=None, slim_state_dict=None, use_graph=False,
-                 overlap=False, infer_batch=2, flow_ahead=0, exact=None):
+                 overlap=False, infer_batch=2, flow_ahead=0, exact=None, share_voxelisation=True):
         """`use_graph`: the frozen SLIM inference (one capture per input shape) and the detector's forward+loss+backward are
         replayed from hipGraphs; the flow clustering in between stays eager (its box count sizes the padded Shape).
         `overlap`: step(pair_i, upcoming=(pair_i+1, pair_i+2)) runs the iteration as a three-stage software pipeline on
         three HIP streams (see _stage_a / _stage_b below); results are those of the one-stream loop.
         `infer_batch`: pairs per SLIM inference replay; `flow_ahead`: steps by which an inference batch is issued BEFORE stage B needs
         its first flow (0: just in time -- stage B of the next two pairs then queues behind a whole batch replay).  The pipeline uses
-        up to `2 + flow_ahead + infer_batch - 1` announced pairs."""
+        up to `2 + flow_ahead + infer_batch - 1` announced pairs.
+        `share_voxelisation` (LISO_SHARE_VOXELISATION=0 overrides): every sweep is voxelised once -- the frozen SLIM inference puts
+        both sweeps of its pairs through one pillar-encoder call, and the detector step reads its t0 clouds' rows out of that call's
+        voxelisation (see _step_batch); False: two encoder calls per inference and the detector voxelises again, as before round 12."""
         from liso_amd.networks.flow_cluster_detector.flow_cluster_detector import FlowClusterDetector
         from liso_amd.slim.model.slim import SLIM
 
@@ -837,6 +860,12 @@ class LisoLoopTrainer:
                 self.infer_cus = 0
         self._pillar_prep = None  # (clouds, pfn.prepare(clouds), event) of the next detector step
         self._prep_ahead = os.environ.get("LISO_PREP_AHEAD", "1") != "0"
+        self.share_voxelisation = bool(share_voxelisation) and os.environ.get("LISO_SHARE_VOXELISATION", "1") != "0"
+        self.slim.raft_network.encode_once = self.share_voxelisation
+        # stage A's inference calls / the voxelisation calls they issued (one each when shared, two otherwise) / detector steps that
+        # took their rows out of a stage-A voxelisation
+        self.stage_a_replays, self.stage_a_voxelisations, self.shared_prep_steps = 0, 0, 0
+        self._infer_vox_calls, self._step_shared = 0, []
         self.pre_nms, self.post_nms = tcfg.max_num_boxes_before_nms, tcfg.max_num_boxes_after_nms
         self.nms_iou = cfg.setdefault("nms_iou_threshold", 0.1)
 
@@ -921,27 +950,40 @@ class LisoLoopTrainer:
         """what the captured inference reads from the samples (the network-input clouds go through the eager pillar encoder)"""
         return tuple({"pcl_ta": s_["pcl_ta"], "gt": {"odom_ta_tb": s_["gt"]["odom_ta_tb"]}} for s_ in (sample_t0, sample_t1))
 
-    def _infer_flow_padded(self, sample_t0, sample_t1):
+    def _infer_flow_padded(self, sample_t0, sample_t1, share=None):
+        """`share`: a list that receives the _SharedVoxelisation of this call's clouds, if it made one"""
+        from liso_amd.slim.model.slim import get_network_input_pcls
+
+        raft = self.slim.raft_network
+        with torch.no_grad():
+            once = raft.encodes_once(len(get_network_input_pcls(self.cfg, sample_t0, "ta")))
+        self._infer_vox_calls = 1 if once else 2
         if not self._graph_infer:
             return self.slim.infer_point_flow_t0_t1(sample_t0, sample_t1)
-        from liso_amd.slim.model.slim import get_network_input_pcls
         from liso_amd.utils import mfma_conv as MC
 
         dev = self.device
         ins = self._graph_inputs(sample_t0, sample_t1)
         # the key holds only what the graph consumes: the padded loss clouds + odometry (the raw clouds' lengths do not enter)
         sig = TT.tree_signature(ins)
-        raft = self.slim.raft_network
         pcls = (get_network_input_pcls(self.cfg, sample_t0, "ta", to_device=dev), get_network_input_pcls(self.cfg, sample_t1, "ta", to_device=dev))
         st = self._infer_graphs.lookup(sig)
         with torch.no_grad():  # pillar encoder eagerly (its rocPRIM sort memsets: liso_amd/utils/graph_safety.py) ...
             # (compact canvases -- mfma_conv.PillarCanvas -- where the encoders' stems read them: the graph's static inputs are then
             # the pillar rows, the cell -> row map and the occupancy map, ~25 MB per pair instead of the dense canvases' 134 MB)
             compact = raft.compact_canvas_ok(dev) if st is None else st["compact"]
+            prep = None
+            if once:  # ONE voxelisation of both sweeps; the event sits right behind it, not behind the replay: a detector step waits for no more
+                clouds = [*pcls[0], *pcls[1]]
+                prep = raft.pp_layer.prepare(clouds)
+                if share is not None:
+                    ready = torch.cuda.Event()
+                    ready.record(torch.cuda.current_stream(dev))
+                    share.append(_SharedVoxelisation(prep, clouds, ready, _pillar_geometry(raft.pp_layer)))
             if st is None:
-                canv = raft.encode_pillars(*pcls, compact=compact)
+                canv = raft.encode_pillars(*pcls, compact=compact, prep=prep)
             else:  # ... straight into the graph's input buffers: no copy, no concatenation of the two sweeps
-                raft.encode_pillars(*pcls, out=st["rows"], compact=compact)
+                raft.encode_pillars(*pcls, out=st["rows"], compact=compact, prep=prep)
             # a device scan (torch.cumsum): eagerly, its memset nodes do not survive in a graph (graph_safety.py)
             thr = self.slim.moving_dynamicness_threshold.value()
         if st is None:
@@ -1138,20 +1180,26 @@ class LisoLoopTrainer:
         if self._main_used_static is not None:  # the static inference buffers were last used on the caller's stream
             side.wait_event(self._main_used_static)
             self._main_used_static = None
+        share = [] if self.share_voxelisation else None
         with torch.cuda.stream(side), torch.no_grad():
             # (the flows stay bucket-padded: stage B reads them next to the padded view of the sample)
             if len(pairs) == 1:
-                flows = [self._infer_flow_padded(self._infer_view(pairs[0][0]), self._infer_view(pairs[0][1])).clone()]  # (the next replay overwrites the static output)
+                flows = [self._infer_flow_padded(self._infer_view(pairs[0][0]), self._infer_view(pairs[0][1]), share).clone()]  # (the next replay overwrites the static output)
             else:
                 # pairs from different point-count buckets share the batch at the largest bucket among them (more padding rows,
                 # ignored everywhere): the inference graph's signature is (batch size, largest bucket), not one per combination
-                flow = self._infer_flow_padded(self._stack_infer_views([p_[0] for p_ in pairs]), self._stack_infer_views([p_[1] for p_ in pairs]))
+                flow = self._infer_flow_padded(self._stack_infer_views([p_[0] for p_ in pairs]), self._stack_infer_views([p_[1] for p_ in pairs]),
+                                               share)
                 b = flow.shape[0] // len(pairs)
                 flows = [flow[k * b:(k + 1) * b].clone() for k in range(len(pairs))]
             done = torch.cuda.Event()
             done.record(side)
-        for p_, fl in zip(pairs, flows):
-            self._flows.append(_Prefetched(pair=p_, flow=fl, done=done))
+        self.stage_a_replays += 1
+        self.stage_a_voxelisations += self._infer_vox_calls
+        # (the batch holds the t0 clouds of its pairs first, one each: pair k's is sample k of the voxelisation -- _shared_prep checks)
+        shared = share[0] if share else None
+        for k, (p_, fl) in enumerate(zip(pairs, flows)):
+            self._flows.append(_Prefetched(pair=p_, flow=fl, done=done, shared=shared, index=k))
 
     def _same_shapes(self, pa, pb):
         """can the two pairs share one inference batch?  What the captured inference consumes -- the loss clouds and the odometry --
@@ -1202,13 +1250,15 @@ class LisoLoopTrainer:
                 count.copy_(self.cluster_detector.last_num_labels.max().reshape(1), non_blocking=True)
             done = torch.cuda.Event()
             done.record(side)
-        self._mined.append(_Prefetched(pair=pair, flow=f.flow, done=done, targets=targets, boxes=boxes, cluster_count=count))
+        self._mined.append(_Prefetched(pair=pair, flow=f.flow, done=done, targets=targets, boxes=boxes, cluster_count=count,
+                                       shared=f.shared, index=f.index))
 
     def _take_mined(self, pair, cur):
         """targets + boxes of `pair` from stage B (made visible to stream `cur`), or None if the pair was not prefetched"""
         m = self._take(self._mined, pair)
         if m is None:
             return None
+        self._step_shared.append((m.shared, m.index))
         if os.environ.get("LISO_NO_COUNT_WAIT") == "1":  # (experiment: what does the host's wait for the cluster count cost?  scripts/loop_floor.py)
             cur.wait_event(m.done)
             for t in list(m.targets.values()) + [v for v in m.boxes.__dict__.values() if torch.is_tensor(v)]:
@@ -1223,6 +1273,22 @@ class LisoLoopTrainer:
         for t in list(m.targets.values()) + [v for v in m.boxes.__dict__.values() if torch.is_tensor(v)]:
             t.record_stream(cur)  # (allocated on the mining stream, consumed here)
         return m.targets, m.boxes
+
+    def _shared_prep(self, held, pcls):
+        """can a detector step on `pcls` read a voxelisation of stage A?  `held`: (voxelisation, index) of the step's pairs, in order.
+        Yes when all pairs went through ONE voxelisation as consecutive samples, the clouds it voxelised there are these very tensor
+        objects (the detector reads `pcl_full_no_ground_ta`; SLIM reads the same list unless data.use_ground_for_network) and both
+        pillar encoders have one geometry -> (voxelisation, first sample), else None: the step then voxelises for itself."""
+        if not self.share_voxelisation or not held or len(held) != len(pcls):  # (one cloud per pair: samples of batch size 1)
+            return None
+        sv, first = held[0]
+        if sv is None or any(h[0] is not sv or h[1] != first + j for j, h in enumerate(held)):
+            return None
+        if first + len(pcls) > len(sv.clouds) or any(sv.clouds[first + j] is not c for j, c in enumerate(pcls)):
+            return None
+        if sv.geometry != _pillar_geometry(self.detector.net.model.pfn):
+            return None
+        return sv, first
 
     def step(self, sample_t0, sample_t1, upcoming=()):
         """one iteration on (sample_t0, sample_t1).  With `overlap`, `upcoming` = the pairs of the following calls (up to
@@ -1255,12 +1321,14 @@ class LisoLoopTrainer:
             if inputs_ready is not None:
                 cur.wait_event(inputs_ready)
         mined = []
+        self._step_shared = []  # (voxelisation, index) of every pair of this step that came out of the pipeline
         for pair in pairs:
             sample_t0, sample_t1 = pair
             got = self._take_mined(pair, cur) if cuda else None
             if got is None:
                 f = self._take(self._flows, pair)
                 if f is not None:
+                    self._step_shared.append((f.shared, f.index))
                     cur.wait_event(f.done)
                     f.flow.record_stream(cur)
                     flow = f.flow
@@ -1294,8 +1362,26 @@ class LisoLoopTrainer:
                 for t in (cat, *parts):
                     t.record_stream(cur)  # (allocated on the mining stream, consumed here and by the encoder's backward)
                 prep = got_prep
+        if prep is None and self.overlap and cuda:
+            hit = self._shared_prep(self._step_shared if len(self._step_shared) == nb else [], pcls)
+            if hit is not None:  # stage A voxelised these very clouds for SLIM: the detector reads its samples' rows out of that call
+                sv, first = hit
+                cur.wait_event(sv.ready)
+                if cur.cuda_stream not in sv.seen:  # (allocated on the flow stream, consumed here and by the encoder's backward)
+                    cat, _, parts = sv.prep
+                    for t in (cat, *parts):
+                        t.record_stream(cur)
+                    sv.seen.add(cur.cuda_stream)
+                prep = (*sv.prep, first, len(pcls))
+                self.shared_prep_steps += 1
+        self._step_shared = []
         loss = self.detector.step(pcls, targets, prep=prep) if prep is not None else self.detector.step(pcls, targets)
-        if self.overlap and cuda and len(upcoming) >= len(pairs) and self._prep_ahead and self.detector.use_graph:
+        prep_ahead = self.overlap and cuda and len(upcoming) >= len(pairs) and self._prep_ahead and self.detector.use_graph
+        if prep_ahead and self.share_voxelisation:  # (nothing to prepare where the next step will find its clouds in a voxelisation of stage A)
+            held = [next((e for e in (*self._mined, *self._flows) if e.is_for(p_)), None) for p_ in upcoming[:len(pairs)]]
+            prep_ahead = self._shared_prep([(e.shared, e.index) if e is not None else (None, None) for e in held],
+                                           [c for p_ in upcoming[:len(pairs)] for c in p_[0]["pcl_full_no_ground_ta"]]) is None
+        if prep_ahead:
             # the weight-independent half of the NEXT step's pillar encoder (voxelisation + decorated rows: ~14 of its ~20 eager
             # launches) now, on the mining stream, next to the detector step that was just enqueued: the detector's stream is the
             # pipeline's critical path, and these launches sat at the head of every step of it
@@ -1321,10 +1407,21 @@ class LisoLoopTrainer:
             missing = [p_ for k, p_ in enumerate(up) if not has(self._flows, p_) and not has(self._mined, p_)
                        and not any(p_[0] is q[0] and p_[1] is q[1] for q in up[:k])]
             if missing and any(p_ is q for p_ in missing for q in up[:ahead + fa]):
+                # a detector step reads stage A's voxelisation only where its pairs sit in ONE inference batch: with batches of whole
+                # detector batches, every inference batch ends where a detector batch ends.  A tail short of that waits for the next
+                # step's announcements unless stage B needs it now.  (Which pairs share a replay does not change any pair's flow.)
+                align = nb if self.share_voxelisation and nb > 1 and self.infer_batch % nb == 0 else 1
+                where = {id(p_): k for k, p_ in reversed(list(enumerate(up)))}  # (first place in `up`; up[0] opens the next detector batch)
                 while missing:
                     n = 1
                     while n < min(len(missing), self.infer_batch) and self._same_shapes(missing[0], missing[n]):
                         n += 1
+                    if align > 1:
+                        whole = [m for m in range(n, 0, -1) if (where[id(missing[m - 1])] + 1) % align == 0]
+                        if whole:
+                            n = whole[0]
+                        elif where[id(missing[0])] >= ahead + fa:
+                            break
                     self._stage_a(*missing[:n])
                     missing = missing[n:]
             for p_ in up[:ahead]:  # by the time a result is taken, its stream got there long ago

@@ -38,7 +38,7 @@ def main(mode):
     cb, ca, ct = {}, {}, {}
     tr._mine_from_graph = lambda s, f, side: cb.setdefault("r", real_b(s, f, side)) if "r" not in cb else cb["r"]
 
-    def infer(s0, s1):
+    def infer(s0, s1, share=None):  # (cached flows: no voxelisation to share)
         key = s0["pcl_ta"]["pcl"].shape
         if key not in ca:
             ca[key] = real_a(s0, s1).clone()

@@ -44,7 +44,7 @@ def run(fake_a, fake_b):
         real_a = tr._infer_flow_padded
         cache_a = {}
 
-        def infer(s0, s1):
+        def infer(s0, s1, share=None):  # (cached flows: no voxelisation to share)
             key = s0["pcl_ta"]["pcl"].shape
             if key not in cache_a:
                 cache_a[key] = real_a(s0, s1).clone()
