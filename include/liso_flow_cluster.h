@@ -20,6 +20,11 @@ extern "C" {
 /* bytes of scratch for liso_bev_dynamic_flow_f32: int64 fixed-point sums [B,H,W,4] + int32 counts [B,H,W] */
 size_t liso_bev_dynamic_flow_workspace_bytes(int batch, int h, int w);
 
+/* bytes of scratch with which liso_bev_dynamic_flow_f32 keeps a pillar's four sums and its count in one 40-byte record (the five
+ * atomics of a pillar then fall into one place); with fewer bytes, but at least liso_bev_dynamic_flow_workspace_bytes, it keeps the
+ * sums and the counts in two arrays.  The results are the same bits either way. */
+size_t liso_bev_dynamic_flow_record_workspace_bytes(int batch, int h, int w);
+
 /* Per point: nonrigid flow = point flow - (inv(odom) - I) p (fp64, bev_flow_utils.py:28-41), then the per-pillar mean
  * of |nonrigid| and of nonrigid (divided only where count > 1, torch_differentiable_forward_scatter.py:84-86).
  *   points [B,N,point_stride] fp32 (NaN padding allowed), valid [B,N] uint8, pillar_coors [B,N,2] int32 (row, col),
@@ -79,6 +84,19 @@ int liso_dbscan_components(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_ma
 int liso_dbscan_labels(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords, const float* col_coords,
                        const float* flow, const uint8_t* core, const int32_t* parent, const int32_t* root_rank,
                        int32_t* labels, void* stream);
+
+/* The two steps on the LIST of dynamic pillars: the same outputs, bit for bit, for every mask.  liso_dbscan_components_ws lists the
+ * dynamic pillars in row-major order in the workspace (no host read, fixed grids) and counts neighbours with one wavefront per listed
+ * pillar; liso_dbscan_labels_ws labels the listed pillars and zero-fills the rest.  It must get the workspace that
+ * liso_dbscan_components_ws filled for the same cfg and dynamic_mask.  0 bytes from the query: a bad cfg, or 2^31 cells or more
+ * (then use the calls above). */
+size_t liso_dbscan_workspace_bytes(const liso_dbscan_cfg* cfg);
+int liso_dbscan_components_ws(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords,
+                              const float* col_coords, const float* flow, uint8_t* core, int32_t* parent, int32_t* is_root,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int liso_dbscan_labels_ws(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords, const float* col_coords,
+                          const float* flow, const uint8_t* core, const int32_t* parent, const int32_t* root_rank, int32_t* labels,
+                          const void* workspace, size_t workspace_bytes, void* stream);
 
 /* regionprops of a label image: moments uint64 [B,max_labels,6] scratch (n, sum r, sum c, sum r^2, sum c^2, sum rc) ->
  * props float64 [B,max_labels,5] = (centroid_row, centroid_col, orientation, axis_major_length, axis_minor_length);

@@ -166,12 +166,16 @@ SIGNATURES = {
     "liso_weighted_moments_bwd_f32": (_i, [_vp, _vp, _vp, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _vp]),
     # include/liso_flow_cluster.h
     "liso_bev_dynamic_flow_workspace_bytes": (_sz, [_i, _i, _i]),
+    "liso_bev_dynamic_flow_record_workspace_bytes": (_sz, [_i, _i, _i]),
     "liso_bev_dynamic_flow_f32": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "liso_odom_inverse_minus_eye_f64": (_i, [_vp, _i, _vp, _vp]),
     "liso_fit_box_z_workspace_bytes": (_sz, [_i, _i]),
     "liso_fit_box_z_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_dbscan_components": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liso_dbscan_labels": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "liso_dbscan_workspace_bytes": (_sz, [_vp]),
+    "liso_dbscan_components_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "liso_dbscan_labels_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_region_props": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "liso_region_props_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "liso_region_props_ws": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -1,7 +1,9 @@
 // Flow -> pseudo-box helper stages for gfx950 (MI355X).  C ABI + reference lines: include/liso_flow_cluster.h.
 //
-//   bev_scatter_kernel   one thread per point: nonrigid flow in fp64, then 4 order-independent 64-bit fixed-point
-//                        atomics + 1 count atomic into the pillar grid (the cloud is read once: 12+12+8+1 B/point)
+//   bev_scatter_kernel   one block per 1024 consecutive points: nonrigid flow in fp64, 4 order-independent 64-bit fixed-point sums +
+//                        1 count per pillar, merged per block in an LDS table (512 slots, open addressing on the pillar) and added to
+//                        the pillar grid once per distinct pillar of the block; a pillar without a slot adds directly (the cloud is
+//                        read once: 12+12+8+1 B/point).  A pillar's sums and count form one 40-byte record when the workspace allows
 //   bev_mean_kernel      one thread per pillar: fixed point -> fp32, divide where count > 1
 //   fit_z_kernel         lanes = boxes, every lane walks the point tile from LDS (broadcast reads) keeping count /
 //                        min / max of the in-box z in registers: no [N,K,4] fp64 tensor (192 MB at N=120k, K=50)
@@ -21,75 +23,134 @@ using liso_dev::check_launch;
 
 constexpr double kFix = 16777216.0;  // 2^24 fixed-point scale: 6e-8 m resolution, |sum| < 5e11 m fits int64
 
-__global__ __launch_bounds__(256) void bev_scatter_kernel(const float* __restrict__ points, int ps, const uint8_t* __restrict__ valid,
+// The accumulators of the pillar grid, in one of two layouts (nothing outside this file reads them):
+//   kRecord   acc[cell][5] 64-bit words: the four sums and, in the low half of the fifth, the count -- the five atomics of a cell fall
+//             into one 40-byte record (liso_bev_dynamic_flow_record_workspace_bytes)
+//   planar    acc[cells][4] sums, then counts[cells] ints: the layout of liso_bev_dynamic_flow_workspace_bytes, 4 bytes per cell smaller,
+//             kept for callers that bring a workspace of that size
+template <bool kRecord>
+struct BevAcc {
+    unsigned long long* acc;
+    int* counts;
+    __device__ __forceinline__ unsigned long long* sum(long long cell) const { return acc + cell * (kRecord ? 5 : 4); }
+    __device__ __forceinline__ int* count(long long cell) const { return kRecord ? (int*)(acc + cell * 5 + 4) : counts + cell; }
+    __device__ __forceinline__ void add(long long cell, const long long (&q)[4], int cnt) const {
+        unsigned long long* s = sum(cell);
+        atomicAdd(s + 0, (unsigned long long)q[0]);
+        atomicAdd(s + 1, (unsigned long long)q[1]);
+        atomicAdd(s + 2, (unsigned long long)q[2]);
+        atomicAdd(s + 3, (unsigned long long)q[3]);
+        atomicAdd(count(cell), cnt);
+    }
+};
+
+// A block takes kScChunk consecutive points.  Their cells repeat without being neighbours (the returns of a few pillars interleave in
+// ring order), so the block first merges equal cells in an LDS table -- open addressing on the cell id, kScProbes linear probes, integer
+// LDS adds -- and then issues ONE set of global atomics per distinct cell of the chunk.  A cell that finds no slot within its probes adds
+// to global memory directly: integer sums, any grouping gives the same bits.
+constexpr int kScThreads = 256, kScChunk = 1024, kScSlotBits = 9, kScSlots = 1 << kScSlotBits, kScProbes = 16;
+constexpr unsigned long long kScEmpty = ~0ull;
+
+template <bool kRecord>
+__global__ __launch_bounds__(kScThreads) void bev_scatter_kernel(const float* __restrict__ points, int ps, const uint8_t* __restrict__ valid,
                                    const int32_t* __restrict__ coors, const float* __restrict__ flow, int fs,
-                                   const double* __restrict__ ome, int batch, int n, int h, int w,
-                                   long long* __restrict__ sums, int* __restrict__ counts) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+                                   const double* __restrict__ ome, int batch, int n, int h, int w, BevAcc<kRecord> out) {
+    __shared__ unsigned long long s_key[kScSlots];
+    __shared__ unsigned long long s_sum[kScSlots][4];
+    __shared__ int s_cnt[kScSlots];
+    for (int s = threadIdx.x; s < kScSlots; s += kScThreads) {
+        s_key[s] = kScEmpty;
+        s_sum[s][0] = s_sum[s][1] = s_sum[s][2] = s_sum[s][3] = 0ull;
+        s_cnt[s] = 0;
+    }
+    __syncthreads();
     const int lane = threadIdx.x & 63;
-    long long cell = -1;
-    long long q[4] = {0, 0, 0, 0};
-    if (i < (size_t)batch * n && valid[i]) {  // masked_scatter_mean_2d only scatters valid rows (:63-66)
-        const int b = (int)(i / n);
-        const int r = coors[i * 2 + 0], c = coors[i * 2 + 1];
-        if (r >= 0 && r < h && c >= 0 && c < w) {
-            const float* p = points + i * ps;
-            const float* f = flow + i * fs;
-            const double* M = ome + (size_t)b * 16;
-            const double x = p[0], y = p[1], z = p[2];
-            float nr[3];
+    for (int part = 0; part < kScChunk / kScThreads; part++) {
+        const size_t i = (size_t)blockIdx.x * kScChunk + (size_t)part * kScThreads + threadIdx.x;
+        long long cell = -1;
+        long long q[4] = {0, 0, 0, 0};
+        if (i < (size_t)batch * n && valid[i]) {  // masked_scatter_mean_2d only scatters valid rows (:63-66)
+            const int b = (int)(i / n);
+            const int r = coors[i * 2 + 0], c = coors[i * 2 + 1];
+            if (r >= 0 && r < h && c >= 0 && c < w) {
+                const float* p = points + i * ps;
+                const float* f = flow + i * fs;
+                const double* M = ome + (size_t)b * 16;
+                const double x = p[0], y = p[1], z = p[2];
+                float nr[3];
 #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                // bev_flow_utils.py:28-41: static flow = ((inv(odom) - I) [x y z 1])[:3] in fp64, cast to fp32, subtracted in fp32
-                const float stat = (float)(M[k * 4 + 0] * x + M[k * 4 + 1] * y + M[k * 4 + 2] * z + M[k * 4 + 3]);
-                nr[k] = f[k] - stat;
+                for (int k = 0; k < 3; k++) {
+                    // bev_flow_utils.py:28-41: static flow = ((inv(odom) - I) [x y z 1])[:3] in fp64, cast to fp32, subtracted in fp32
+                    const float stat = (float)(M[k * 4 + 0] * x + M[k * 4 + 1] * y + M[k * 4 + 2] * z + M[k * 4 + 3]);
+                    nr[k] = f[k] - stat;
+                }
+                // torch.linalg.norm (fp32)
+                const float len = sqrtf(nr[0] * nr[0] + nr[1] * nr[1] + nr[2] * nr[2]);
+                cell = (long long)(((size_t)b * h + r) * w + c);
+                q[0] = llrint((double)len * kFix);
+                q[1] = llrint((double)nr[0] * kFix);
+                q[2] = llrint((double)nr[1] * kFix);
+                q[3] = llrint((double)nr[2] * kFix);
             }
-            // torch.linalg.norm (fp32)
-            const float len = sqrtf(nr[0] * nr[0] + nr[1] * nr[1] + nr[2] * nr[2]);
-            cell = (long long)(((size_t)b * h + r) * w + c);
-            q[0] = llrint((double)len * kFix);
-            q[1] = llrint((double)nr[0] * kFix);
-            q[2] = llrint((double)nr[1] * kFix);
-            q[3] = llrint((double)nr[2] * kFix);
+        }
+        // consecutive returns of one ring fall into the same pillar: the lanes of a RUN of equal cells add up in the wave (integer sums:
+        // any grouping gives the same bits) and the run's first lane carries the sum on.  A wave without such a run (every lane a head)
+        // skips the 54 shuffles.
+        const long long prev = __shfl_up(cell, 1);
+        const bool head = lane == 0 || prev != cell;
+        const unsigned long long heads = __ballot(head);
+        int cnt = cell >= 0 ? 1 : 0;
+        if (heads != ~0ull) {
+            const int run = __popcll(heads & ((2ull << lane) - 1ull));  // run index of this lane (1-based)
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int other_run = __shfl_down(run, o);
+                const bool take = lane + o < 64 && other_run == run;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const long long v = __shfl_down(q[k], o);
+                    if (take) q[k] += v;
+                }
+                const int vc = __shfl_down(cnt, o);
+                if (take) cnt += vc;
+            }
+        }
+        if (head && cell >= 0) {
+            // the cell's slot: its own, or the first free one within kScProbes of its hash
+            unsigned s = ((unsigned)cell * 2654435761u) >> (32 - kScSlotBits);
+            bool placed = false;
+            for (int probe = 0; probe < kScProbes; probe++) {
+                const unsigned long long old = atomicCAS(&s_key[s], kScEmpty, (unsigned long long)cell);
+                if (old == kScEmpty || old == (unsigned long long)cell) { placed = true; break; }
+                s = (s + 1) & (kScSlots - 1);
+            }
+            if (placed) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) atomicAdd(&s_sum[s][k], (unsigned long long)q[k]);
+                atomicAdd(&s_cnt[s], cnt);
+            } else {
+                out.add(cell, q, cnt);
+            }
         }
     }
-    // consecutive returns of one ring fall into the same pillar: the lanes of a RUN of equal cells add up in the wave (integer sums:
-    // any grouping gives the same bits) and the run's first lane issues the five atomics for all of them
-    const long long prev = __shfl_up(cell, 1);
-    const bool head = lane == 0 || prev != cell;
-    const unsigned long long heads = __ballot(head);
-    const int run = __popcll(heads & ((2ull << lane) - 1ull));  // run index of this lane (1-based)
-    int cnt = cell >= 0 ? 1 : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int other_run = __shfl_down(run, o);
-        const bool take = lane + o < 64 && other_run == run;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const long long v = __shfl_down(q[k], o);
-            if (take) q[k] += v;
-        }
-        const int vc = __shfl_down(cnt, o);
-        if (take) cnt += vc;
+    __syncthreads();
+    for (int s = threadIdx.x; s < kScSlots; s += kScThreads) {
+        if (s_key[s] == kScEmpty) continue;
+        const long long q[4] = {(long long)s_sum[s][0], (long long)s_sum[s][1], (long long)s_sum[s][2], (long long)s_sum[s][3]};
+        out.add((long long)s_key[s], q, s_cnt[s]);
     }
-    if (!head || cell < 0) return;
-    unsigned long long* s = (unsigned long long*)(sums + cell * 4);
-    atomicAdd(s + 0, (unsigned long long)q[0]);
-    atomicAdd(s + 1, (unsigned long long)q[1]);
-    atomicAdd(s + 2, (unsigned long long)q[2]);
-    atomicAdd(s + 3, (unsigned long long)q[3]);
-    atomicAdd(&counts[cell], cnt);
 }
 
-__global__ void bev_mean_kernel(const long long* __restrict__ sums, const int* __restrict__ counts, size_t cells,
-                                float* __restrict__ dyn, float* __restrict__ nrflow) {
+template <bool kRecord>
+__global__ void bev_mean_kernel(BevAcc<kRecord> in, size_t cells, float* __restrict__ dyn, float* __restrict__ nrflow) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cells) return;
-    const int cnt = counts[i];
+    const int cnt = *in.count((long long)i);
+    const long long* sums = (const long long*)in.sum((long long)i);
     float v[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        v[k] = (float)((double)sums[i * 4 + k] / kFix);
+        v[k] = (float)((double)sums[k] / kFix);
         if (cnt > 1) v[k] = v[k] / (float)cnt;  // torch_differentiable_forward_scatter.py:84-86
     }
     dyn[i] = v[0];
@@ -251,6 +312,11 @@ size_t liso_bev_dynamic_flow_workspace_bytes(int batch, int h, int w) {
     return (size_t)batch * h * w * (4 * sizeof(long long) + sizeof(int));
 }
 
+size_t liso_bev_dynamic_flow_record_workspace_bytes(int batch, int h, int w) {
+    if (batch <= 0 || h <= 0 || w <= 0) return 0;
+    return (size_t)batch * h * w * (5 * sizeof(long long));
+}
+
 int liso_bev_dynamic_flow_f32(const float* points, int point_stride, const uint8_t* valid, const int32_t* pillar_coors,
                               const float* flow, int flow_stride, const double* odom_minus_eye, int batch, int n, int h,
                               int w, float* dynamicness, float* nonrigid_flow, void* workspace, size_t workspace_bytes,
@@ -262,15 +328,25 @@ int liso_bev_dynamic_flow_f32(const float* points, int point_stride, const uint8
     if (workspace_bytes < need) return LISO_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const size_t cells = (size_t)batch * h * w;
-    long long* sums = (long long*)workspace;
-    int* counts = (int*)(sums + cells * 4);
-    if (liso_zero::zero_async(workspace, need, st) != hipSuccess) return LISO_ELAUNCH;
     const size_t total = (size_t)batch * n;
-    if (total > 0)
-        bev_scatter_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(points, point_stride, valid, pillar_coors, flow,
-                                                                          flow_stride, odom_minus_eye, batch, n, h, w, sums,
-                                                                          counts);
-    bev_mean_kernel<<<(unsigned)((cells + 255) / 256), 256, 0, st>>>(sums, counts, cells, dynamicness, nonrigid_flow);
+    const unsigned chunks = (unsigned)((total + kScChunk - 1) / kScChunk), mean_blocks = (unsigned)((cells + 255) / 256);
+    unsigned long long* acc = (unsigned long long*)workspace;
+    const size_t record_need = liso_bev_dynamic_flow_record_workspace_bytes(batch, h, w);
+    if (workspace_bytes >= record_need) {  // one record per cell
+        const BevAcc<true> a{acc, nullptr};
+        if (liso_zero::zero_async(workspace, record_need, st) != hipSuccess) return LISO_ELAUNCH;
+        if (total > 0)
+            bev_scatter_kernel<true><<<chunks, kScThreads, 0, st>>>(points, point_stride, valid, pillar_coors, flow, flow_stride,
+                                                                    odom_minus_eye, batch, n, h, w, a);
+        bev_mean_kernel<true><<<mean_blocks, 256, 0, st>>>(a, cells, dynamicness, nonrigid_flow);
+    } else {
+        const BevAcc<false> a{acc, (int*)(acc + cells * 4)};
+        if (liso_zero::zero_async(workspace, need, st) != hipSuccess) return LISO_ELAUNCH;
+        if (total > 0)
+            bev_scatter_kernel<false><<<chunks, kScThreads, 0, st>>>(points, point_stride, valid, pillar_coors, flow, flow_stride,
+                                                                     odom_minus_eye, batch, n, h, w, a);
+        bev_mean_kernel<false><<<mean_blocks, 256, 0, st>>>(a, cells, dynamicness, nonrigid_flow);
+    }
     return check_launch();
 }
 

@@ -12,6 +12,9 @@
 //   dbscan_label    one thread per dynamic cell: core -> rank of its root; border -> smallest rank among its core
 //                   eps-neighbours; no core neighbour -> 0 (noise).  rank = 1-based position of the root among all
 //                   roots in row-major order (an inclusive scan of the root flags, done by the caller).
+//   dyn_count / dyn_list / dbscan_core_list / dbscan_label_list (the *_ws entry points): the dynamic cells listed in row-major order,
+//                   then the core count and the labelling with one wave per LISTED cell on a fixed grid -- the same bits as the
+//                   dense passes for every mask; the union stays on its tiles (16 waves per tile)
 // Why this equals sklearn's labelling: sklearn visits points in input (row-major) order, starts cluster k at the k-th
 // still unlabelled core point and grows it completely (depth-first over core points, labelling every neighbour) before
 // it moves on -- so clusters are the connected components of the core graph numbered by their smallest member, and a
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(256) void dbscan_union_kernel(Cfg c, const uint8_t*
 // smallest cell of the local component, the order the global forest uses), and then every core cell of the region is hooked ONCE in
 // the global array: with its local root.  Each eps edge lies inside the region of the tile that holds its larger end, so the global
 // forest connects exactly the components of the core graph; tiles without a core cell (almost all of them) leave after one load.
-constexpr int kTR = 16, kTC = 32, kUfThreads = 256, kMaxWin = 8;
+constexpr int kTR = 16, kTC = 32, kUfThreads = 1024, kMaxWin = 8;
 constexpr int kRegMax = (kTR + 2 * kMaxWin) * (kTC + 2 * kMaxWin);
 
 __device__ __forceinline__ int lds_find(const int* par, int l, int r0, int c0, int RW, int gy) {
@@ -362,6 +365,116 @@ __global__ void dbscan_label_kernel(Cfg c, const uint8_t* __restrict__ dyn, cons
     labels[i] = label;
 }
 
+// ---- the same passes on the LIST of dynamic cells (liso_dbscan_components_ws / liso_dbscan_labels_ws) ------------------------------------
+// A few thousand of the 512 x 512 cells are dynamic, in blobs: with one thread per cell of the dense grid the handful of waves that
+// hold a blob walk up to kDenseWave flagged cells one after the other while 99 % of the waves leave at once, and the launch lasts as
+// long as its busiest wave.  Here the dynamic cells are listed first, in row-major order (block counts, then every block places its
+// cells behind the blocks in front of it: the same list whatever the schedule), and a fixed grid of waves takes the listed cells one
+// per wave, so a blob spreads over the chip.  The per-cell arithmetic is wave_for_each_neighbour's, the results are per cell: the
+// outputs have the bits of the dense kernels for every mask, a fully dynamic grid included (the list then names every cell).
+constexpr int kListThreads = 256, kListPasses = 8, kListTile = kListThreads * kListPasses;  // cells per block of the two list passes
+constexpr int kListGrid = 1024;                                                             // blocks of 4 waves that walk the list
+
+__global__ __launch_bounds__(kListThreads) void dyn_count_kernel(const uint8_t* __restrict__ dyn, unsigned total, int* __restrict__ block_cnt) {
+    __shared__ int wsum[kListThreads / 64];
+    const unsigned base = blockIdx.x * (unsigned)kListTile;
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < kListPasses; k++) {
+        const unsigned i = base + k * kListThreads + threadIdx.x;
+        n += (i < total && dyn[i]) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// list[rank of the cell among the dynamic cells] = cell (index into the whole batch); the cells that are not dynamic get the core flag and
+// the parent the dense core kernel gives them (0, -1); *n_list = number of dynamic cells
+__global__ __launch_bounds__(kListThreads) void dyn_list_kernel(const uint8_t* __restrict__ dyn, unsigned total, const int* __restrict__ block_cnt,
+                                                                int* __restrict__ list, int* __restrict__ n_list, uint8_t* __restrict__ core,
+                                                                int* __restrict__ parent) {
+    __shared__ int s_red[kListThreads / 64];
+    __shared__ int s_seg[kListPasses][kListThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int before = 0;  // dynamic cells in the blocks in front of this one
+    for (int q = threadIdx.x; q < (int)blockIdx.x; q += kListThreads) before += block_cnt[q];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
+    if (lane == 0) s_red[wave] = before;
+    const unsigned base = blockIdx.x * (unsigned)kListTile;
+    unsigned long long mine[kListPasses];
+#pragma unroll
+    for (int k = 0; k < kListPasses; k++) {
+        const unsigned i = base + k * kListThreads + threadIdx.x;
+        const bool d = i < total && dyn[i];
+        mine[k] = __ballot(d);
+        if (lane == 0) s_seg[k][wave] = __popcll(mine[k]);
+        if (i < total && !d) { core[i] = 0; parent[i] = -1; }
+    }
+    __syncthreads();
+    int pos = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+#pragma unroll
+    for (int k = 0; k < kListPasses; k++) {
+        // (cells of pass k, wave w come behind all passes < k and the waves < w of pass k: row-major order)
+        if ((mine[k] >> lane) & 1ull) {
+            int p = pos + __popcll(mine[k] & ((1ull << lane) - 1ull));
+            for (int w = 0; w < wave; w++) p += s_seg[k][w];
+            list[p] = (int)(base + k * kListThreads + threadIdx.x);
+        }
+        pos += (s_seg[k][0] + s_seg[k][1]) + (s_seg[k][2] + s_seg[k][3]);
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_list = pos;
+}
+
+__global__ __launch_bounds__(256) void dbscan_core_list_kernel(Cfg c, const uint8_t* __restrict__ dyn, const float* __restrict__ xs,
+                                                               const float* __restrict__ ys, const float* __restrict__ flow,
+                                                               const int* __restrict__ list, const int* __restrict__ n_list,
+                                                               uint8_t* __restrict__ core, int* __restrict__ parent) {
+    const int lane = threadIdx.x & 63, n = *n_list;
+    const size_t per = (size_t)c.gx * c.gy;
+    for (int e = blockIdx.x * 4 + (threadIdx.x >> 6); e < n; e += gridDim.x * 4) {
+        const size_t cell = (size_t)list[e];
+        int count = 0;
+        wave_for_each_neighbour(c, dyn, xs, ys, flow, cell, lane, [&](size_t) { count++; });
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) count += __shfl_xor(count, o);
+        if (lane == 0) {
+            const int is_core = count >= c.min_samples;
+            core[cell] = (uint8_t)is_core;
+            parent[cell] = is_core ? (int)(cell % per) : -1;  // per-sample cell index
+        }
+    }
+}
+
+// labels of the listed cells (the others were zero-filled): core -> rank of its root; border -> smallest rank among its core eps-neighbours
+__global__ __launch_bounds__(256) void dbscan_label_list_kernel(Cfg c, const uint8_t* __restrict__ dyn, const uint8_t* __restrict__ core,
+                                                                const float* __restrict__ xs, const float* __restrict__ ys,
+                                                                const float* __restrict__ flow, const int* __restrict__ parent,
+                                                                const int* __restrict__ root_rank, const int* __restrict__ list,
+                                                                const int* __restrict__ n_list, int* __restrict__ labels) {
+    const int lane = threadIdx.x & 63, n = *n_list;
+    const size_t per = (size_t)c.gx * c.gy;
+    for (int e = blockIdx.x * 4 + (threadIdx.x >> 6); e < n; e += gridDim.x * 4) {
+        const size_t cell = (size_t)list[e];
+        const int* par = parent + (cell / per) * per;
+        const int* rank = root_rank + (cell / per) * per;
+        int best = 0x7fffffff;
+        if (core[cell]) {  // (the same cell in every lane: a wave-uniform branch)
+            best = rank[find_root(par, (int)(cell % per))];
+        } else {
+            wave_for_each_neighbour(c, dyn, xs, ys, flow, cell, lane, [&](size_t nb) {
+                if (core[nb]) best = min(best, rank[find_root(par, (int)(nb % per))]);
+            });
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
+        }
+        if (lane == 0) labels[cell] = best == 0x7fffffff ? 0 : best;
+    }
+}
+
 // Integer moments of every labelled region.  A wave covers 64 consecutive cells, which carry at most a few distinct labels:
 // the wave reduces the six sums per label (butterfly) and ONE lane issues the atomics -- 6 per (wave, label) instead of 6 per
 // cell, which serialised on the few dozen label rows (243 us at 512 x 512).  Integer sums: any order gives the same bits.
@@ -485,6 +598,21 @@ inline Cfg to_cfg(const liso_dbscan_cfg* c) {
     return k;
 }
 
+// the list workspace: list[total] | block_cnt[blocks] | n_list
+struct ListWs {
+    int *list, *block_cnt, *n_list;
+    unsigned blocks;
+};
+inline size_t carve_list(void* base, size_t total, ListWs& w) {
+    liso_dev::Carver cv{base};
+    w.blocks = (unsigned)((total + kListTile - 1) / kListTile);
+    w.list = cv.take<int>(total);
+    w.block_cnt = cv.take<int>(w.blocks);
+    w.n_list = cv.take<int>(1);
+    return cv.bytes;
+}
+inline unsigned list_grid(size_t total) { return (unsigned)(total / 4 + 1 < (size_t)kListGrid ? total / 4 + 1 : (size_t)kListGrid); }
+
 }  // namespace
 
 extern "C" {
@@ -518,6 +646,58 @@ int liso_dbscan_labels(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, 
     const size_t total = (size_t)c.batch * c.gx * c.gy;
     dbscan_label_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(c, dynamic_mask, core, row_coords,
                                                                                        col_coords, flow, parent, root_rank, labels);
+    return check_launch();
+}
+
+size_t liso_dbscan_workspace_bytes(const liso_dbscan_cfg* cfg) {
+    if (!cfg_ok(cfg) || (size_t)cfg->batch * cfg->gx * cfg->gy >= (1ull << 31)) return 0;
+    ListWs w{};
+    return carve_list(nullptr, (size_t)cfg->batch * cfg->gx * cfg->gy, w);
+}
+
+int liso_dbscan_components_ws(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords,
+                              const float* col_coords, const float* flow, uint8_t* core, int32_t* parent, int32_t* is_root,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cfg_ok(cfg) || !dynamic_mask || !row_coords || !col_coords || !flow || !core || !parent || !is_root) return LISO_EINVAL;
+    const size_t need = liso_dbscan_workspace_bytes(cfg);
+    if (need == 0) return LISO_EINVAL;  // (2^31 cells or more: liso_dbscan_components)
+    if (!workspace || workspace_bytes < need) return LISO_EWORKSPACE;
+    const Cfg c = to_cfg(cfg);
+    const size_t total = (size_t)c.batch * c.gx * c.gy;
+    ListWs w{};
+    carve_list(workspace, total, w);
+    hipStream_t st = (hipStream_t)stream;
+    dyn_count_kernel<<<w.blocks, kListThreads, 0, st>>>(dynamic_mask, (unsigned)total, w.block_cnt);
+    dyn_list_kernel<<<w.blocks, kListThreads, 0, st>>>(dynamic_mask, (unsigned)total, w.block_cnt, w.list, w.n_list, core, parent);
+    dbscan_core_list_kernel<<<list_grid(total), 256, 0, st>>>(c, dynamic_mask, row_coords, col_coords, flow, w.list, w.n_list, core,
+                                                             parent);
+    if (c.win <= kMaxWin) {
+        const int tiles_r = (c.gx + kTR - 1) / kTR, tiles_c = (c.gy + kTC - 1) / kTC;
+        dbscan_union_tiled_kernel<<<dim3(tiles_r * tiles_c, c.batch), kUfThreads, 0, st>>>(c, dynamic_mask, core, row_coords, col_coords,
+                                                                                         flow, parent, tiles_r, tiles_c);
+    } else {
+        dbscan_union_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(c, dynamic_mask, core, row_coords, col_coords, flow, parent);
+    }
+    dbscan_flatten_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(c, core, parent, is_root);
+    return check_launch();
+}
+
+int liso_dbscan_labels_ws(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords, const float* col_coords,
+                          const float* flow, const uint8_t* core, const int32_t* parent, const int32_t* root_rank, int32_t* labels,
+                          const void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cfg_ok(cfg) || !dynamic_mask || !row_coords || !col_coords || !flow || !core || !parent || !root_rank || !labels)
+        return LISO_EINVAL;
+    const size_t need = liso_dbscan_workspace_bytes(cfg);
+    if (need == 0) return LISO_EINVAL;
+    if (!workspace || workspace_bytes < need) return LISO_EWORKSPACE;
+    const Cfg c = to_cfg(cfg);
+    const size_t total = (size_t)c.batch * c.gx * c.gy;
+    ListWs w{};
+    carve_list((void*)workspace, total, w);
+    hipStream_t st = (hipStream_t)stream;
+    if (liso_zero::zero_async(labels, total * sizeof(int32_t), st) != hipSuccess) return LISO_ELAUNCH;
+    dbscan_label_list_kernel<<<list_grid(total), 256, 0, st>>>(c, dynamic_mask, core, row_coords, col_coords, flow, parent, root_rank,
+                                                              w.list, w.n_list, labels);
     return check_launch();
 }
 

@@ -296,6 +296,37 @@ __device__ void jacobi_svd3(const double A[3][3], Svd3& o) {
     }
 }
 
+// Sum of one row (slot) of the block partials over the sample's blocks, in fp64: lane l adds the blocks l, l + 64, ... in that order and
+// a butterfly combines the lanes -- the order is part of the result's bits.  The loads of kRowsAhead blocks are issued together before
+// any of them is added: the loop used to wait for memory once per block (8 dependent round trips at 512 blocks).
+constexpr int kRowsAhead = 8;
+__device__ __forceinline__ void reduce_rows(const float* __restrict__ partials, int b, int nblk, int S, int row, int lane,
+                                            double (&m)[NM]) {
+#pragma unroll
+    for (int k = 0; k < NM; k++) m[k] = 0.0;
+    for (int blk0 = lane; blk0 < nblk; blk0 += 64 * kRowsAhead) {
+        float v[kRowsAhead][NM];
+#pragma unroll
+        for (int j = 0; j < kRowsAhead; j++) {
+            const int blk = blk0 + 64 * j;
+            if (blk < nblk) {
+                const float* p = partials + (((size_t)b * nblk + blk) * (S + 2) + row) * NM;
+#pragma unroll
+                for (int k = 0; k < NM; k++) v[j][k] = p[k];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kRowsAhead; j++)
+            if (blk0 + 64 * j < nblk) {
+#pragma unroll
+                for (int k = 0; k < NM; k++) m[k] += (double)v[j][k];
+            }
+    }
+#pragma unroll
+    for (int k = 0; k < NM; k++)
+        for (int o = 32; o > 0; o >>= 1) m[k] += __shfl_xor(m[k], o);
+}
+
 // per (sample, slot): reduce, epsilon rule, centre, solve, compose T.  One wave per slot, lanes split the blocks.
 __global__ __launch_bounds__(64) void kabsch_solve_kernel(liso_kabsch_cfg cfg, const float* __restrict__ partials,
                                                           int nblk, const float* __restrict__ box_pos,
@@ -303,24 +334,17 @@ __global__ __launch_bounds__(64) void kabsch_solve_kernel(liso_kabsch_cfg cfg, c
     const int S = cfg.n_slots;
     const int b = blockIdx.y, slot = blockIdx.x;  // slot in [0, S]  (S = background)
     const int lane = threadIdx.x;
-    double m[NM], u[NM];
-#pragma unroll
-    for (int k = 0; k < NM; k++) m[k] = u[k] = 0.0;
-    for (int blk = lane; blk < nblk; blk += 64) {
-        const float* p = partials + ((size_t)b * nblk + blk) * (S + 2) * NM;
-#pragma unroll
-        for (int k = 0; k < NM; k++) { m[k] += (double)p[slot * NM + k]; u[k] += (double)p[(S + 1) * NM + k]; }
-    }
-#pragma unroll
-    for (int k = 0; k < NM; k++)
-        for (int o = 32; o > 0; o >>= 1) { m[k] += __shfl_xor(m[k], o); u[k] += __shfl_xor(u[k], o); }
-    if (lane != 0) return;
+    double m[NM];
+    reduce_rows(partials, b, nblk, S, slot, lane, m);
     double cx = 0.0, cy = 0.0;  // the shift used while accumulating this slot
     if (slot < S) { cx = (double)box_pos[((size_t)b * S + slot) * 3 + 0]; cy = (double)box_pos[((size_t)b * S + slot) * 3 + 1]; }
     // cum_wts is an fp32 sum in the reference (kabsch_mask.py:453); the epsilon rule (:454-470) compares it to 1e-12
-    double W = m[0];
+    double W = m[0];  // (the butterfly leaves the same bits in every lane: the branch below is wave-uniform)
     if ((float)W < 1e-12f) {
-        // every one of the N rows (padding included, mapped to the origin) gets weight 1e-12
+        // every one of the N rows (padding included, mapped to the origin) gets weight 1e-12.  Only such a slot needs the uniform
+        // moments (row S + 1), the same numbers for every slot of the sample: reduced here, in the order every slot used to
+        double u[NM];
+        reduce_rows(partials, b, nblk, S, S + 1, lane, u);
         const double eps = (double)1e-12f;
         for (int k = 0; k < NM; k++) m[k] = eps * u[k];
         // the uniform slot was accumulated unshifted; padded rows contribute zero vectors but count in N
@@ -328,6 +352,7 @@ __global__ __launch_bounds__(64) void kabsch_solve_kernel(liso_kabsch_cfg cfg, c
         W = m[0];
         cx = 0.0; cy = 0.0;
     }
+    if (lane != 0) return;
     const double mx0 = m[1] / W, mx1 = m[2] / W, my0 = m[3] / W, my1 = m[4] / W;  // relative to the shift
     double A[3][3] = {{m[5] / W - my0 * mx0, m[6] / W - my0 * mx1, 0.0},
                       {m[7] / W - my1 * mx0, m[8] / W - my1 * mx1, 0.0},

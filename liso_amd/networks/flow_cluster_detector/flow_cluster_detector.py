@@ -59,15 +59,17 @@ def cluster_dynamic_pillars(dynamic_mask, bev_nonrigid_flow, row_coords_m, col_c
     labels = torch.empty((B, gx, gy), dtype=torch.int32, device=dev)
     lib = L.lib()
     import ctypes
+    nbytes = lib.liso_dbscan_workspace_bytes(ctypes.byref(cfg))  # the list of dynamic pillars (0: 2^31 cells or more -> the dense passes)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        L.check(L.TIMER.launch("dbscan_components", lambda: lib.liso_dbscan_components(
-            ctypes.byref(cfg), L.ptr(dyn), L.ptr(xs), L.ptr(ys), L.ptr(flow), L.ptr(core), L.ptr(parent), L.ptr(is_root),
-            L.stream_ptr())), "dbscan_components")
+        args = (ctypes.byref(cfg), L.ptr(dyn), L.ptr(xs), L.ptr(ys), L.ptr(flow), L.ptr(core), L.ptr(parent), L.ptr(is_root))
+        L.check(L.TIMER.launch("dbscan_components", lambda: lib.liso_dbscan_components_ws(*args, L.ptr(ws), nbytes, L.stream_ptr())
+                               if nbytes else lib.liso_dbscan_components(*args, L.stream_ptr())), "dbscan_components")
         from liso_amd.networks.flow_cluster_detector.mining_ops import inclusive_scan_i32
         rank = inclusive_scan_i32(is_root.view(B, -1)).view(B, gx, gy)  # (own scan: no memset node when captured into a hipGraph)
-        L.check(L.TIMER.launch("dbscan_labels", lambda: lib.liso_dbscan_labels(
-            ctypes.byref(cfg), L.ptr(dyn), L.ptr(xs), L.ptr(ys), L.ptr(flow), L.ptr(core), L.ptr(parent), L.ptr(rank),
-            L.ptr(labels), L.stream_ptr())), "dbscan_labels")
+        largs = (ctypes.byref(cfg), L.ptr(dyn), L.ptr(xs), L.ptr(ys), L.ptr(flow), L.ptr(core), L.ptr(parent), L.ptr(rank), L.ptr(labels))
+        L.check(L.TIMER.launch("dbscan_labels", lambda: lib.liso_dbscan_labels_ws(*largs, L.ptr(ws), nbytes, L.stream_ptr())
+                               if nbytes else lib.liso_dbscan_labels(*largs, L.stream_ptr())), "dbscan_labels")
     return labels, rank.view(B, -1)[:, -1].long()
 
 
