@@ -58,7 +58,7 @@ typedef struct {
  *   -> pos fp32 [B,K,3], dims fp64 [B,K,3], rot fp64 [B,K,1], probs fp64 [B,K,1] (1 for survivors), velo fp64 [B,K,1] (0),
  *      valid uint8 [B,K], class_id int32 [B,K,1], difficulty int32 [B,K,1] (unknown-class / invalid ids of shape_utils.py:15-16),
  *      counts int32 [B]; unused slots hold zeros.  kabsch_pos fp32 [B,K,3], kabsch_dims fp32 [B,K,3], kabsch_rot fp32 [B,K]:
- *      fp32 copies for liso_kabsch_trafos_f32 (unused slots parked when cfg->park_invalid). */
+ *      fp32 copies for liso_kabsch_trafos_counted_f32 (unused slots parked when cfg->park_invalid). */
 int liso_mine_filter_compact(const liso_mine_filter_cfg* cfg, const int64_t* num_labels, const float* center, const double* dims2,
                              const double* rot_in, const int64_t* num_pts, const float* fit_z, const float* fit_h, float* pos,
                              double* dims, double* rot, double* probs, double* velo, uint8_t* valid, int32_t* class_id,
@@ -66,7 +66,7 @@ int liso_mine_filter_compact(const liso_mine_filter_cfg* cfg, const int64_t* num
                              void* stream);
 
 /* Heading and speed of every box from its Kabsch transform (:312-331):
- *   trafos fp64 [B, S+1, 4, 4]: slots 0..S-1 the per-box transforms, slot S the background transform (liso_kabsch_trafos_f32);
+ *   trafos fp64 [B, S+1, 4, 4]: slots 0..S-1 the per-box transforms, slot S the background transform (liso_kabsch_trafos_counted_f32);
  *   pos fp32 [B,S,3]; rot fp64 [B,S,1] in/out: rot += atan2(t_y, t_x); velo fp64 [B,S,1] out = |t|, where t is the translation of
  *   inv(T_box) inv(T_bg) (T_fg T_box), T_box = translation(pos) * rotation_z(rot), all fp64. */
 int liso_mine_box_motion(const double* trafos, int batch, int s, const float* pos, double* rot, double* velo, void* stream);

@@ -290,10 +290,6 @@ int liso_sparse_conv_forward_rows(const void* rows, long row_stride, int is_bf16
 int liso_sparse_conv_dgrad(const void* dy, long dy_pix_stride, int is_bf16, const float* occupancy, const void* w_packed_dgrad, int batch,
                            int hi, int wi, int k, int co, int max_cells_per_sample, void* dx, long dx_pix_stride, int* overflow,
                            void* workspace, size_t workspace_bytes, int reuse_lists, void* stream);
-size_t liso_sparse_stem_workspace_bytes(int batch, int hi, int wi, int max_cells_per_sample);
-int liso_sparse_stem_forward_f32(const float* x, long x_pix_stride, const float* occupancy, const void* w_packed, const float* bias,
-                                 int batch, int hi, int wi, int max_cells_per_sample, int relu, float* y, float* stats_partial,
-                                 int* overflow, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,13 +17,9 @@
 extern "C" {
 #endif
 
-/* bytes of scratch for liso_bev_dynamic_flow_f32: int64 fixed-point sums [B,H,W,4] + int32 counts [B,H,W] */
+/* bytes of scratch for liso_bev_dynamic_flow_f32: 40 * B * H * W, one record per pillar (four int64 fixed-point sums and the count,
+ * side by side: the five atomics of a pillar fall into one place).  Fewer bytes are refused with LISO_EWORKSPACE. */
 size_t liso_bev_dynamic_flow_workspace_bytes(int batch, int h, int w);
-
-/* bytes of scratch with which liso_bev_dynamic_flow_f32 keeps a pillar's four sums and its count in one 40-byte record (the five
- * atomics of a pillar then fall into one place); with fewer bytes, but at least liso_bev_dynamic_flow_workspace_bytes, it keeps the
- * sums and the counts in two arrays.  The results are the same bits either way. */
-size_t liso_bev_dynamic_flow_record_workspace_bytes(int batch, int h, int w);
 
 /* Per point: nonrigid flow = point flow - (inv(odom) - I) p (fp64, bev_flow_utils.py:28-41), then the per-pillar mean
  * of |nonrigid| and of nonrigid (divided only where count > 1, torch_differentiable_forward_scatter.py:84-86).
@@ -73,45 +69,33 @@ typedef struct {
     float flow_weight; /* 2.0 (flow_cluster_detector.py:154-160) */
 } liso_dbscan_cfg;
 
+/* bytes of scratch for the two steps below: the list of dynamic pillars.  0: a bad cfg, or 2^31 cells or more in the batch (the
+ * steps then return LISO_EINVAL). */
+size_t liso_dbscan_workspace_bytes(const liso_dbscan_cfg* cfg);
+
 /* step 1: core flags uint8 [B,gx,gy], union-find parents int32 [B,gx,gy] (per-sample cell index, -1 for non-core) and
- * is_root int32 [B,gx,gy] (1 where a core pillar is the smallest member of its component). */
+ * is_root int32 [B,gx,gy] (1 where a core pillar is the smallest member of its component).  Lists the dynamic pillars in row-major
+ * order in the workspace (no host read, fixed grids) and counts neighbours with one wavefront per listed pillar. */
 int liso_dbscan_components(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords,
                            const float* col_coords, const float* flow, uint8_t* core, int32_t* parent, int32_t* is_root,
-                           void* stream);
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* step 2: root_rank int32 [B,gx,gy] = per-sample inclusive scan of is_root (the caller's scan; 1-based label of a root)
- * -> labels int32 [B,gx,gy]: 0 = background / noise, k >= 1 = sklearn label k-1 (flow_cluster_detector.py:169-172). */
+ * -> labels int32 [B,gx,gy]: 0 = background / noise, k >= 1 = sklearn label k-1 (flow_cluster_detector.py:169-172).  Labels the
+ * listed pillars and zero-fills the rest: it must get the workspace that step 1 filled for the same cfg and dynamic_mask. */
 int liso_dbscan_labels(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords, const float* col_coords,
-                       const float* flow, const uint8_t* core, const int32_t* parent, const int32_t* root_rank,
-                       int32_t* labels, void* stream);
-
-/* The two steps on the LIST of dynamic pillars: the same outputs, bit for bit, for every mask.  liso_dbscan_components_ws lists the
- * dynamic pillars in row-major order in the workspace (no host read, fixed grids) and counts neighbours with one wavefront per listed
- * pillar; liso_dbscan_labels_ws labels the listed pillars and zero-fills the rest.  It must get the workspace that
- * liso_dbscan_components_ws filled for the same cfg and dynamic_mask.  0 bytes from the query: a bad cfg, or 2^31 cells or more
- * (then use the calls above). */
-size_t liso_dbscan_workspace_bytes(const liso_dbscan_cfg* cfg);
-int liso_dbscan_components_ws(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords,
-                              const float* col_coords, const float* flow, uint8_t* core, int32_t* parent, int32_t* is_root,
-                              void* workspace, size_t workspace_bytes, void* stream);
-int liso_dbscan_labels_ws(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords, const float* col_coords,
-                          const float* flow, const uint8_t* core, const int32_t* parent, const int32_t* root_rank, int32_t* labels,
-                          const void* workspace, size_t workspace_bytes, void* stream);
+                       const float* flow, const uint8_t* core, const int32_t* parent, const int32_t* root_rank, int32_t* labels,
+                       const void* workspace, size_t workspace_bytes, void* stream);
 
 /* regionprops of a label image: moments uint64 [B,max_labels,6] scratch (n, sum r, sum c, sum r^2, sum c^2, sum rc) ->
  * props float64 [B,max_labels,5] = (centroid_row, centroid_col, orientation, axis_major_length, axis_minor_length);
- * labels above max_labels are ignored, absent labels give zeros. */
-int liso_region_props(const int32_t* labels, int batch, int gx, int gy, int max_labels, uint64_t* moments, double* props,
-                      void* stream);
-
-/* The same results (bit for bit: the moments are integers) without global atomics: per-block sums in LDS, written to
- * workspace[batch][blocks][max_labels][6] and added per region by a second launch.  For label maps whose labelled cells are scattered
- * over the grid (round 5: 4 306 labelled pillars of an untrained flow network's output in 30 clusters -> 75 us through the atomics of
- * liso_region_props, 26 k of them on 180 addresses; here ~10 us).  0 bytes from the query (more than 1024 labels): the call forwards to
- * liso_region_props. */
+ * labels above max_labels are ignored, absent labels give zeros.  The moments are exact integer sums: per-block sums in LDS, written
+ * to workspace[batch][blocks][max_labels][6] and added per region by a second launch (no global atomics: the labelled cells of an
+ * untrained flow network's output are scattered over the grid).  0 bytes from the query (more than 1024 labels): global 64-bit atomics
+ * instead, the same bits, and the workspace arguments are ignored.  2^31 cells or more in the batch: LISO_EINVAL. */
 size_t liso_region_props_workspace_bytes(int batch, int gx, int gy, int max_labels);
-int liso_region_props_ws(const int32_t* labels, int batch, int gx, int gy, int max_labels, uint64_t* moments, double* props,
-                         void* workspace, size_t workspace_bytes, void* stream);
+int liso_region_props(const int32_t* labels, int batch, int gx, int gy, int max_labels, uint64_t* moments, double* props,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,7 +33,7 @@ typedef struct {
     int softness;                 /* 0 = cauchy (0.5 + atan(x)/pi), 1 = sigmoid */
 } liso_kabsch_cfg;
 
-/* scratch for liso_kabsch_trafos_f32 */
+/* scratch for liso_kabsch_trafos_counted_f32 */
 size_t liso_kabsch_workspace_bytes(const liso_kabsch_cfg* cfg);
 
 /* points [B,N,point_stride] (padding rows may hold NaN), valid [B,N] (uint8), flow [B,N,flow_stride],
@@ -43,22 +43,20 @@ size_t liso_kabsch_workspace_bytes(const liso_kabsch_cfg* cfg);
  *   fg_weights float32 [B, S, N] or NULL (kabsch_mask.py:353-360; invalid points get weight 0, :417-419)
  * Semantics: z of the aligned clouds is zeroed (:413), background weight = 1 - screen(fg masks at scale_bg)
  * (:362-372), slots whose total weight is < 1e-12 fall back to uniform weights 1e-12 (:452-470),
- * R = U Vh without reflection fix (:489-492). */
-int liso_kabsch_trafos_f32(const liso_kabsch_cfg* cfg, const float* points, const uint8_t* valid, const float* flow,
-                           const float* box_pos, const float* box_dims, const float* box_rot, double* trafos,
-                           float* cum_wts, float* fg_weights, void* workspace, size_t workspace_bytes, void* stream);
-
-/* The same for callers with a FIXED number of slots of which only the first slot_count[b] (int32 [B], device) hold boxes (the LISO
- * loop's box mining: 64 slots, 15-30 boxes; the other slots are parked where their soft mask is 0 in fp32).  The parked slots are not
+ * R = U Vh without reflection fix (:489-492).
+ *
+ * slot_count == NULL: all n_slots slots hold boxes.  Otherwise the number of slots is FIXED and only the first slot_count[b]
+ * (int32 [B], device) hold boxes (the LISO loop's box mining: 64 slots, 15-30 boxes; the other slots are parked where their soft
+ * mask is 0 in fp32).  The parked slots are not
  * evaluated -- 7.7 M box-mask evaluations (3 atan each) per 120k-point cloud at 64 slots, the kernel is bound by them -- and the lanes
  * are re-dealt over the boxes that exist (16 / 32 / 64 slot lanes x 4 / 2 / 1 point sub-lanes per wave, chosen from slot_count[b]).
  * Skipping a parked slot changes no output bit (it is a factor of exactly 1 in the background product and its moments fall under the
  * 1e-12 rule above; fg_weights of parked slots: exact zeros instead of ~1e-23), but the re-deal changes the ORDER in which a slot's
- * fp32 moment sums are added: the transforms equal liso_kabsch_trafos_f32's for the parked arrangement to fp32-summation tolerance
+ * fp32 moment sums are added: the transforms equal those of slot_count == NULL for the parked arrangement to fp32-summation tolerance
  * (1e-6 relative, what tests/test_gpu_kabsch.py asserts), not bitwise, and they depend bitwise on which of the three deals
  * slot_count[b] selects.  For a fixed slot_count every output is run-to-run bitwise reproducible.
- * slot_count == NULL: all n_slots slots hold boxes; the deal is chosen from n_slots, so liso_kabsch_trafos_f32 on exactly k boxes
- * and this call on more slots with slot_count[b] = k use the same deal and give the same bits for those boxes. */
+ * With slot_count == NULL the deal is chosen from n_slots, so that call on exactly k boxes and a call on more slots with
+ * slot_count[b] = k use the same deal and give the same bits for those boxes. */
 int liso_kabsch_trafos_counted_f32(const liso_kabsch_cfg* cfg, const float* points, const uint8_t* valid, const float* flow,
                                    const float* box_pos, const float* box_dims, const float* box_rot, const int32_t* slot_count,
                                    double* trafos, float* cum_wts, float* fg_weights, void* workspace, size_t workspace_bytes,

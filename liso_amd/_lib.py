@@ -157,7 +157,6 @@ SIGNATURES = {
     "liso_pfn_backward_sub": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     # include/liso_kabsch.h
     "liso_kabsch_workspace_bytes": (_sz, [_vp]),
-    "liso_kabsch_trafos_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_kabsch_trafos_counted_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_symm_ortho_fwd_f64": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "liso_symm_ortho_bwd_f64": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -166,19 +165,15 @@ SIGNATURES = {
     "liso_weighted_moments_bwd_f32": (_i, [_vp, _vp, _vp, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _vp]),
     # include/liso_flow_cluster.h
     "liso_bev_dynamic_flow_workspace_bytes": (_sz, [_i, _i, _i]),
-    "liso_bev_dynamic_flow_record_workspace_bytes": (_sz, [_i, _i, _i]),
     "liso_bev_dynamic_flow_f32": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "liso_odom_inverse_minus_eye_f64": (_i, [_vp, _i, _vp, _vp]),
     "liso_fit_box_z_workspace_bytes": (_sz, [_i, _i]),
     "liso_fit_box_z_f32": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "liso_dbscan_components": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "liso_dbscan_labels": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "liso_dbscan_workspace_bytes": (_sz, [_vp]),
-    "liso_dbscan_components_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "liso_dbscan_labels_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "liso_region_props": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "liso_dbscan_components": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "liso_dbscan_labels": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_region_props_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "liso_region_props_ws": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "liso_region_props": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     # include/liso_slim.h
     "liso_corr_lookup_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "liso_corr_lookup_fwd_tiled_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -296,8 +291,6 @@ SIGNATURES = {
     "liso_sparse_conv_forward_rows": (_i, [_vp, ctypes.c_long, _i, _vp, ctypes.c_long, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                            _sz, _vp]),
     "liso_sparse_conv_dgrad": (_i, [_vp, ctypes.c_long, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, ctypes.c_long, _vp, _vp, _sz, _i, _vp]),
-    "liso_sparse_stem_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "liso_sparse_stem_forward_f32": (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_conv_bn_finalize": (_i, [_vp, _i, _i, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp]),
     "liso_conv_bn_finalize_merged": (_i, [_vp, _i, _i, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _i, _vp]),
     # include/liso_tracking.h

@@ -3,7 +3,7 @@
 //   bev_scatter_kernel   one block per 1024 consecutive points: nonrigid flow in fp64, 4 order-independent 64-bit fixed-point sums +
 //                        1 count per pillar, merged per block in an LDS table (512 slots, open addressing on the pillar) and added to
 //                        the pillar grid once per distinct pillar of the block; a pillar without a slot adds directly (the cloud is
-//                        read once: 12+12+8+1 B/point).  A pillar's sums and count form one 40-byte record when the workspace allows
+//                        read once: 12+12+8+1 B/point).  A pillar's sums and count form one 40-byte record
 //   bev_mean_kernel      one thread per pillar: fixed point -> fp32, divide where count > 1
 //   fit_z_kernel         lanes = boxes, every lane walks the point tile from LDS (broadcast reads) keeping count /
 //                        min / max of the in-box z in registers: no [N,K,4] fp64 tensor (192 MB at N=120k, K=50)
@@ -23,26 +23,17 @@ using liso_dev::check_launch;
 
 constexpr double kFix = 16777216.0;  // 2^24 fixed-point scale: 6e-8 m resolution, |sum| < 5e11 m fits int64
 
-// The accumulators of the pillar grid, in one of two layouts (nothing outside this file reads them):
-//   kRecord   acc[cell][5] 64-bit words: the four sums and, in the low half of the fifth, the count -- the five atomics of a cell fall
-//             into one 40-byte record (liso_bev_dynamic_flow_record_workspace_bytes)
-//   planar    acc[cells][4] sums, then counts[cells] ints: the layout of liso_bev_dynamic_flow_workspace_bytes, 4 bytes per cell smaller,
-//             kept for callers that bring a workspace of that size
-template <bool kRecord>
-struct BevAcc {
-    unsigned long long* acc;
-    int* counts;
-    __device__ __forceinline__ unsigned long long* sum(long long cell) const { return acc + cell * (kRecord ? 5 : 4); }
-    __device__ __forceinline__ int* count(long long cell) const { return kRecord ? (int*)(acc + cell * 5 + 4) : counts + cell; }
-    __device__ __forceinline__ void add(long long cell, const long long (&q)[4], int cnt) const {
-        unsigned long long* s = sum(cell);
-        atomicAdd(s + 0, (unsigned long long)q[0]);
-        atomicAdd(s + 1, (unsigned long long)q[1]);
-        atomicAdd(s + 2, (unsigned long long)q[2]);
-        atomicAdd(s + 3, (unsigned long long)q[3]);
-        atomicAdd(count(cell), cnt);
-    }
-};
+// The accumulators of the pillar grid (nothing outside this file reads them): acc[cell][5] 64-bit words, the four sums and, in the low
+// half of the fifth, the count -- the five atomics of a cell fall into one 40-byte record
+constexpr int kAccWords = 5;
+__device__ __forceinline__ void bev_add(unsigned long long* acc, long long cell, const long long (&q)[4], int cnt) {
+    unsigned long long* s = acc + cell * kAccWords;
+    atomicAdd(s + 0, (unsigned long long)q[0]);
+    atomicAdd(s + 1, (unsigned long long)q[1]);
+    atomicAdd(s + 2, (unsigned long long)q[2]);
+    atomicAdd(s + 3, (unsigned long long)q[3]);
+    atomicAdd((int*)(s + 4), cnt);
+}
 
 // A block takes kScChunk consecutive points.  Their cells repeat without being neighbours (the returns of a few pillars interleave in
 // ring order), so the block first merges equal cells in an LDS table -- open addressing on the cell id, kScProbes linear probes, integer
@@ -51,10 +42,9 @@ struct BevAcc {
 constexpr int kScThreads = 256, kScChunk = 1024, kScSlotBits = 9, kScSlots = 1 << kScSlotBits, kScProbes = 16;
 constexpr unsigned long long kScEmpty = ~0ull;
 
-template <bool kRecord>
 __global__ __launch_bounds__(kScThreads) void bev_scatter_kernel(const float* __restrict__ points, int ps, const uint8_t* __restrict__ valid,
                                    const int32_t* __restrict__ coors, const float* __restrict__ flow, int fs,
-                                   const double* __restrict__ ome, int batch, int n, int h, int w, BevAcc<kRecord> out) {
+                                   const double* __restrict__ ome, int batch, int n, int h, int w, unsigned long long* acc) {
     __shared__ unsigned long long s_key[kScSlots];
     __shared__ unsigned long long s_sum[kScSlots][4];
     __shared__ int s_cnt[kScSlots];
@@ -129,7 +119,7 @@ __global__ __launch_bounds__(kScThreads) void bev_scatter_kernel(const float* __
                 for (int k = 0; k < 4; k++) atomicAdd(&s_sum[s][k], (unsigned long long)q[k]);
                 atomicAdd(&s_cnt[s], cnt);
             } else {
-                out.add(cell, q, cnt);
+                bev_add(acc, cell, q, cnt);
             }
         }
     }
@@ -137,16 +127,16 @@ __global__ __launch_bounds__(kScThreads) void bev_scatter_kernel(const float* __
     for (int s = threadIdx.x; s < kScSlots; s += kScThreads) {
         if (s_key[s] == kScEmpty) continue;
         const long long q[4] = {(long long)s_sum[s][0], (long long)s_sum[s][1], (long long)s_sum[s][2], (long long)s_sum[s][3]};
-        out.add((long long)s_key[s], q, s_cnt[s]);
+        bev_add(acc, (long long)s_key[s], q, s_cnt[s]);
     }
 }
 
-template <bool kRecord>
-__global__ void bev_mean_kernel(BevAcc<kRecord> in, size_t cells, float* __restrict__ dyn, float* __restrict__ nrflow) {
+__global__ void bev_mean_kernel(const unsigned long long* acc, size_t cells, float* __restrict__ dyn,
+                                float* __restrict__ nrflow) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cells) return;
-    const int cnt = *in.count((long long)i);
-    const long long* sums = (const long long*)in.sum((long long)i);
+    const long long* sums = (const long long*)(acc + i * kAccWords);
+    const int cnt = *(const int*)(sums + 4);
     float v[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -309,12 +299,7 @@ extern "C" {
 
 size_t liso_bev_dynamic_flow_workspace_bytes(int batch, int h, int w) {
     if (batch <= 0 || h <= 0 || w <= 0) return 0;
-    return (size_t)batch * h * w * (4 * sizeof(long long) + sizeof(int));
-}
-
-size_t liso_bev_dynamic_flow_record_workspace_bytes(int batch, int h, int w) {
-    if (batch <= 0 || h <= 0 || w <= 0) return 0;
-    return (size_t)batch * h * w * (5 * sizeof(long long));
+    return (size_t)batch * h * w * (kAccWords * sizeof(long long));
 }
 
 int liso_bev_dynamic_flow_f32(const float* points, int point_stride, const uint8_t* valid, const int32_t* pillar_coors,
@@ -331,22 +316,11 @@ int liso_bev_dynamic_flow_f32(const float* points, int point_stride, const uint8
     const size_t total = (size_t)batch * n;
     const unsigned chunks = (unsigned)((total + kScChunk - 1) / kScChunk), mean_blocks = (unsigned)((cells + 255) / 256);
     unsigned long long* acc = (unsigned long long*)workspace;
-    const size_t record_need = liso_bev_dynamic_flow_record_workspace_bytes(batch, h, w);
-    if (workspace_bytes >= record_need) {  // one record per cell
-        const BevAcc<true> a{acc, nullptr};
-        if (liso_zero::zero_async(workspace, record_need, st) != hipSuccess) return LISO_ELAUNCH;
-        if (total > 0)
-            bev_scatter_kernel<true><<<chunks, kScThreads, 0, st>>>(points, point_stride, valid, pillar_coors, flow, flow_stride,
-                                                                    odom_minus_eye, batch, n, h, w, a);
-        bev_mean_kernel<true><<<mean_blocks, 256, 0, st>>>(a, cells, dynamicness, nonrigid_flow);
-    } else {
-        const BevAcc<false> a{acc, (int*)(acc + cells * 4)};
-        if (liso_zero::zero_async(workspace, need, st) != hipSuccess) return LISO_ELAUNCH;
-        if (total > 0)
-            bev_scatter_kernel<false><<<chunks, kScThreads, 0, st>>>(points, point_stride, valid, pillar_coors, flow, flow_stride,
-                                                                     odom_minus_eye, batch, n, h, w, a);
-        bev_mean_kernel<false><<<mean_blocks, 256, 0, st>>>(a, cells, dynamicness, nonrigid_flow);
-    }
+    if (liso_zero::zero_async(workspace, need, st) != hipSuccess) return LISO_ELAUNCH;
+    if (total > 0)
+        bev_scatter_kernel<<<chunks, kScThreads, 0, st>>>(points, point_stride, valid, pillar_coors, flow, flow_stride, odom_minus_eye,
+                                                          batch, n, h, w, acc);
+    bev_mean_kernel<<<mean_blocks, 256, 0, st>>>(acc, cells, dynamicness, nonrigid_flow);
     return check_launch();
 }
 

@@ -5,23 +5,22 @@
 // (eps 1 m, min_samples 5) on the host.  eps bounds the BEV distance, so every eps-neighbour of a pillar lies inside a
 // (2R+1)^2 window of the dense grid (R = 6 at 0.195 m pillars): no neighbour lists, no KD-tree, no M^2 pairs.
 //
-//   dbscan_core     one thread per cell: counts eps-neighbours in the window (self included) -> core flag
-//   dbscan_union    one thread per core cell: lock-free union-find (always link the larger root under the smaller:
-//                   atomicMin on the parent) with every core eps-neighbour of smaller index
+//   dyn_count / dyn_place  the dynamic cells listed in row-major order in the workspace (no host read, fixed grids)
+//   dbscan_core     one wave per listed cell: counts eps-neighbours in the window (self included) -> core flag
+//   dbscan_union    lock-free union-find (always link the larger root under the smaller: atomicMin on the parent) of every
+//                   core cell with every core eps-neighbour of smaller index: in LDS per tile (16 waves per tile), then one
+//                   global hook per cell; windows above 8 hook every edge in the global array
 //   dbscan_flatten  one thread per core cell: is_root flag (the root is the smallest cell index of its component)
-//   dbscan_label    one thread per dynamic cell: core -> rank of its root; border -> smallest rank among its core
+//   dbscan_label    one wave per listed cell: core -> rank of its root; border -> smallest rank among its core
 //                   eps-neighbours; no core neighbour -> 0 (noise).  rank = 1-based position of the root among all
 //                   roots in row-major order (an inclusive scan of the root flags, done by the caller).
-//   dyn_count / dyn_list / dbscan_core_list / dbscan_label_list (the *_ws entry points): the dynamic cells listed in row-major order,
-//                   then the core count and the labelling with one wave per LISTED cell on a fixed grid -- the same bits as the
-//                   dense passes for every mask; the union stays on its tiles (16 waves per tile)
 // Why this equals sklearn's labelling: sklearn visits points in input (row-major) order, starts cluster k at the k-th
 // still unlabelled core point and grows it completely (depth-first over core points, labelling every neighbour) before
 // it moves on -- so clusters are the connected components of the core graph numbered by their smallest member, and a
 // border point reachable from several clusters keeps the first one that reached it, i.e. the smallest number.
 //
-//   region_moments  one thread per labelled cell: 6 exact integer moments (n, sum r, sum c, sum r^2, sum c^2, sum rc)
-//                   by 64-bit integer atomics (order independent)
+//   region_moments  6 exact integer moments per label (n, sum r, sum c, sum r^2, sum c^2, sum rc): per-block sums in LDS
+//                   added by a second launch; above 1024 labels 64-bit global atomics (integers: order independent)
 //   region_props    one thread per label: centroid, orientation, axis lengths from the second central moments
 //                   (skimage.measure.regionprops formulas, fp64)
 #include <hip/hip_runtime.h>
@@ -57,29 +56,9 @@ __device__ __forceinline__ double dist_sqr(const float* __restrict__ xs, const f
     return d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3 + d4 * d4;
 }
 
-template <typename F>
-__device__ __forceinline__ void for_each_neighbour(const Cfg& c, const uint8_t* __restrict__ dyn, const float* __restrict__ xs,
-                                                   const float* __restrict__ ys, const float* __restrict__ flow, int b, int r,
-                                                   int col, F&& f) {
-    const size_t base = (size_t)b * c.gx * c.gy;
-    const size_t me = base + (size_t)r * c.gy + col;
-    const int r_lo = max(r - c.win, 0), r_hi = min(r + c.win, c.gx - 1);
-    const int c_lo = max(col - c.win, 0), c_hi = min(col + c.win, c.gy - 1);
-    for (int rr = r_lo; rr <= r_hi; rr++)
-        for (int cc = c_lo; cc <= c_hi; cc++) {
-            const size_t nb = base + (size_t)rr * c.gy + cc;
-            if (!dyn[nb]) continue;
-            if (dist_sqr(xs, ys, flow, c.flow_weight, r, col, me, rr, cc, nb) <= c.eps_sqr) f(nb);
-        }
-}
-
-// Wave-cooperative window walk.  Dynamic pillars are sparse (a few thousand of 512 x 512) and come in blobs a handful of
-// columns wide, so a wave of 64 consecutive cells holds 0-10 of them: instead of every such lane walking its 13 x 13 window
-// alone (169 dependent iterations with 1-10 of 64 lanes busy), the wave takes its flagged cells one after the other and all
-// 64 lanes share the window of that cell (3 iterations, consecutive columns = coalesced reads).  f(nb, leader_lane) runs on the
-// lanes whose window cell is a neighbour (dynamic, within eps) of the flagged cell.
-constexpr int kDenseWave = 20;  // flagged cells per wave above which the per-lane walk (169 iterations, all lanes busy) is cheaper
-
+// Wave-cooperative window walk: the 64 lanes of a wave share the 13 x 13 window of ONE cell `me` (3 iterations, consecutive
+// columns = coalesced reads) instead of one lane walking it alone (169 dependent iterations).  f(nb) runs on the lanes whose
+// window cell nb is a neighbour (dynamic, within eps) of `me`.
 template <typename F>
 __device__ __forceinline__ void wave_for_each_neighbour(const Cfg& c, const uint8_t* __restrict__ dyn, const float* __restrict__ xs,
                                                         const float* __restrict__ ys, const float* __restrict__ flow, size_t me,
@@ -97,37 +76,6 @@ __device__ __forceinline__ void wave_for_each_neighbour(const Cfg& c, const uint
     }
 }
 
-__global__ __launch_bounds__(256) void dbscan_core_kernel(Cfg c, const uint8_t* __restrict__ dyn, const float* __restrict__ xs,
-                                                          const float* __restrict__ ys, const float* __restrict__ flow,
-                                                          uint8_t* __restrict__ core, int* __restrict__ parent) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t per = (size_t)c.gx * c.gy, total = per * c.batch;
-    const int lane = threadIdx.x & 63;
-    const bool flagged = i < total && dyn[i];
-    unsigned long long todo = __ballot(flagged);
-    int is_core = 0;
-    if (__popcll(todo) > kDenseWave) {  // a wave inside a large dynamic region: every lane walks its own window (lanes all busy)
-        if (flagged) {
-            int count = 0;
-            for_each_neighbour(c, dyn, xs, ys, flow, (int)(i / per), (int)((i % per) / c.gy), (int)(i % c.gy), [&](size_t) { count++; });
-            is_core = count >= c.min_samples;
-        }
-        todo = 0ull;
-    }
-    while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        int count = 0;
-        wave_for_each_neighbour(c, dyn, xs, ys, flow, i - lane + src, lane, [&](size_t) { count++; });
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) count += __shfl_xor(count, o);
-        if (lane == src) is_core = count >= c.min_samples;
-    }
-    if (i >= total) return;
-    core[i] = (uint8_t)is_core;
-    parent[i] = is_core ? (int)(i % per) : -1;  // per-sample cell index
-}
-
 // parents only ever move to smaller indices; device-scope loads keep concurrent hooks visible (fewer retries)
 __device__ __forceinline__ int find_root(const int* parent, int x) {
     int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -143,6 +91,22 @@ __device__ __forceinline__ int find_root_compress(int* parent, int x0) {
     return r;
 }
 
+// joins the trees of x and y in the global forest of one sample: the larger root goes under the smaller one
+__device__ __forceinline__ void hook(int* par, int x, int y) {
+    while (true) {
+        x = find_root_compress(par, x);
+        y = find_root_compress(par, y);
+        if (x == y) break;
+        if (x < y) { const int t = x; x = y; y = t; }  // x: larger root, linked under y
+        const int old = atomicMin(&par[x], y);
+        if (old == x) break;  // x was still a root: linked
+        x = old;              // somebody re-parented x meanwhile: retry from there
+    }
+}
+
+// the union for windows above kMaxWin (the tiled kernel's LDS region holds no wider halo): every (core cell, smaller core
+// eps-neighbour) pair is hooked in the global parent array.  A wave takes the core cells among its 64 consecutive cells one after
+// the other and its lanes share the window of that cell.
 __global__ __launch_bounds__(256) void dbscan_union_kernel(Cfg c, const uint8_t* __restrict__ dyn, const uint8_t* __restrict__ core,
                                                            const float* __restrict__ xs, const float* __restrict__ ys,
                                                            const float* __restrict__ flow, int* __restrict__ parent) {
@@ -150,29 +114,6 @@ __global__ __launch_bounds__(256) void dbscan_union_kernel(Cfg c, const uint8_t*
     const size_t per = (size_t)c.gx * c.gy, total = per * c.batch;
     const int lane = threadIdx.x & 63;
     unsigned long long todo = __ballot(i < total && core[i]);
-    if (__popcll(todo) > kDenseWave) {
-        if (i < total && core[i]) {
-            const int b = (int)(i / per), r = (int)((i % per) / c.gy), col = (int)(i % c.gy);
-            int* par = parent + (size_t)b * per;
-            const int me = (int)(i % per);
-            for_each_neighbour(c, dyn, xs, ys, flow, b, r, col, [&](size_t nb) {
-                if (!core[nb]) return;
-                const int other = (int)(nb % per);
-                if (other >= me) return;
-                int x = me, y = other;
-                while (true) {
-                    x = find_root_compress(par, x);
-                    y = find_root_compress(par, y);
-                    if (x == y) break;
-                    if (x < y) { const int t = x; x = y; y = t; }
-                    const int old = atomicMin(&par[x], y);
-                    if (old == x) break;
-                    x = old;
-                }
-            });
-        }
-        return;
-    }
     while (todo) {  // (the final forest -- every tree rooted at its smallest cell -- does not depend on the order of the hooks)
         const int src = __ffsll((long long)todo) - 1;
         todo &= todo - 1;
@@ -180,19 +121,8 @@ __global__ __launch_bounds__(256) void dbscan_union_kernel(Cfg c, const uint8_t*
         int* par = parent + (cell / per) * per;
         const int me = (int)(cell % per);
         wave_for_each_neighbour(c, dyn, xs, ys, flow, cell, lane, [&](size_t nb) {
-            if (!core[nb]) return;
             const int other = (int)(nb % per);
-            if (other >= me) return;  // every undirected edge once
-            int x = me, y = other;
-            while (true) {
-                x = find_root_compress(par, x);
-                y = find_root_compress(par, y);
-                if (x == y) break;
-                if (x < y) { const int t = x; x = y; y = t; }  // x: larger root, linked under y
-                const int old = atomicMin(&par[x], y);
-                if (old == x) break;  // x was still a root: linked
-                x = old;              // somebody re-parented x meanwhile: retry from there
-            }
+            if (core[nb] && other < me) hook(par, me, other);  // every undirected edge once
         });
     }
 }
@@ -298,7 +228,7 @@ __global__ __launch_bounds__(kUfThreads) void dbscan_union_tiled_kernel(Cfg c, c
                 const int old = atomicMin(&s_par[hi], lo_g);  // the larger root under the smaller one
                 if (old == hi_g) break;                       // it was still a root: linked
                 // somebody re-parented it meanwhile, to `old`.  The atomicMin has already stored min(old, lo_g) there, so when
-                // lo_g < old the edge hi -> old is GONE: go on with the pair (old, lo_g), as the global loops do with `x = old`
+                // lo_g < old the edge hi -> old is GONE: go on with the pair (old, lo_g), as hook() does with `x = old`
                 // (walking on from hi would find hi and lo_g joined and leave old's tree cut off)
                 a = (old / c.gy - r0) * RW + (old % c.gy - c0);
                 bq = (lo_g / c.gy - r0) * RW + (lo_g % c.gy - c0);
@@ -313,17 +243,7 @@ __global__ __launch_bounds__(kUfThreads) void dbscan_union_tiled_kernel(Cfg c, c
         const int me = (r0 + l / RW) * c.gy + (c0 + l % RW);
         const int lr = lds_find(s_par, l, r0, c0, RW, c.gy);
         const int root = (r0 + lr / RW) * c.gy + (c0 + lr % RW);
-        if (root == me) continue;
-        int x = me, y = root;
-        while (true) {
-            x = find_root_compress(par, x);
-            y = find_root_compress(par, y);
-            if (x == y) break;
-            if (x < y) { const int t = x; x = y; y = t; }
-            const int old = atomicMin(&par[x], y);
-            if (old == x) break;
-            x = old;
-        }
+        if (root != me) hook(par, me, root);
     }
 }
 
@@ -341,37 +261,12 @@ __global__ void dbscan_flatten_kernel(Cfg c, const uint8_t* __restrict__ core, i
     is_root[i] = root_flag;
 }
 
-__global__ void dbscan_label_kernel(Cfg c, const uint8_t* __restrict__ dyn, const uint8_t* __restrict__ core,
-                                    const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ flow,
-                                    const int* __restrict__ parent, const int* __restrict__ root_rank, int* __restrict__ labels) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t per = (size_t)c.gx * c.gy;
-    if (i >= per * c.batch) return;
-    int label = 0;
-    if (dyn[i]) {
-        const int b = (int)(i / per), r = (int)((i % per) / c.gy), col = (int)(i % c.gy);
-        const int* par = parent + (size_t)b * per;
-        const int* rank = root_rank + (size_t)b * per;
-        if (core[i]) {
-            label = rank[find_root(par, (int)(i % per))];
-        } else {
-            int best = 0x7fffffff;
-            for_each_neighbour(c, dyn, xs, ys, flow, b, r, col, [&](size_t nb) {
-                if (core[nb]) best = min(best, rank[find_root(par, (int)(nb % per))]);
-            });
-            label = best == 0x7fffffff ? 0 : best;
-        }
-    }
-    labels[i] = label;
-}
-
-// ---- the same passes on the LIST of dynamic cells (liso_dbscan_components_ws / liso_dbscan_labels_ws) ------------------------------------
-// A few thousand of the 512 x 512 cells are dynamic, in blobs: with one thread per cell of the dense grid the handful of waves that
-// hold a blob walk up to kDenseWave flagged cells one after the other while 99 % of the waves leave at once, and the launch lasts as
-// long as its busiest wave.  Here the dynamic cells are listed first, in row-major order (block counts, then every block places its
-// cells behind the blocks in front of it: the same list whatever the schedule), and a fixed grid of waves takes the listed cells one
-// per wave, so a blob spreads over the chip.  The per-cell arithmetic is wave_for_each_neighbour's, the results are per cell: the
-// outputs have the bits of the dense kernels for every mask, a fully dynamic grid included (the list then names every cell).
+// ---- the list of dynamic cells, and the core count and the labelling that walk it --------------------------------------------------------
+// A few thousand of the 512 x 512 cells are dynamic, in blobs: with one thread (or wave) per stretch of the dense grid the handful of
+// waves that hold a blob do all the work while 99 % of the waves leave at once, and the launch lasts as long as its busiest wave.  So
+// the dynamic cells are listed first, in row-major order (block counts, then every block places its cells behind the blocks in front
+// of it: the same list whatever the schedule), and a fixed grid of waves takes the listed cells one per wave, so a blob spreads over
+// the chip.  The results are per cell: they do not depend on which wave takes which cell.
 constexpr int kListThreads = 256, kListPasses = 8, kListTile = kListThreads * kListPasses;  // cells per block of the two list passes
 constexpr int kListGrid = 1024;                                                             // blocks of 4 waves that walk the list
 
@@ -391,11 +286,11 @@ __global__ __launch_bounds__(kListThreads) void dyn_count_kernel(const uint8_t* 
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
-// list[rank of the cell among the dynamic cells] = cell (index into the whole batch); the cells that are not dynamic get the core flag and
-// the parent the dense core kernel gives them (0, -1); *n_list = number of dynamic cells
-__global__ __launch_bounds__(kListThreads) void dyn_list_kernel(const uint8_t* __restrict__ dyn, unsigned total, const int* __restrict__ block_cnt,
-                                                                int* __restrict__ list, int* __restrict__ n_list, uint8_t* __restrict__ core,
-                                                                int* __restrict__ parent) {
+// list[rank of the cell among the dynamic cells] = cell (index into the whole batch); the cells that are not dynamic get their core flag and
+// parent here (0, -1); *n_list = number of dynamic cells
+__global__ __launch_bounds__(kListThreads) void dyn_place_kernel(const uint8_t* __restrict__ dyn, unsigned total, const int* __restrict__ block_cnt,
+                                                                 int* __restrict__ list, int* __restrict__ n_list, uint8_t* __restrict__ core,
+                                                                 int* __restrict__ parent) {
     __shared__ int s_red[kListThreads / 64];
     __shared__ int s_seg[kListPasses][kListThreads / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -429,10 +324,11 @@ __global__ __launch_bounds__(kListThreads) void dyn_list_kernel(const uint8_t* _
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_list = pos;
 }
 
-__global__ __launch_bounds__(256) void dbscan_core_list_kernel(Cfg c, const uint8_t* __restrict__ dyn, const float* __restrict__ xs,
-                                                               const float* __restrict__ ys, const float* __restrict__ flow,
-                                                               const int* __restrict__ list, const int* __restrict__ n_list,
-                                                               uint8_t* __restrict__ core, int* __restrict__ parent) {
+// core flag and initial parent of the listed cells: eps-neighbours in the window, the cell itself included, counted by one wave
+__global__ __launch_bounds__(256) void dbscan_core_kernel(Cfg c, const uint8_t* __restrict__ dyn, const float* __restrict__ xs,
+                                                          const float* __restrict__ ys, const float* __restrict__ flow,
+                                                          const int* __restrict__ list, const int* __restrict__ n_list,
+                                                          uint8_t* __restrict__ core, int* __restrict__ parent) {
     const int lane = threadIdx.x & 63, n = *n_list;
     const size_t per = (size_t)c.gx * c.gy;
     for (int e = blockIdx.x * 4 + (threadIdx.x >> 6); e < n; e += gridDim.x * 4) {
@@ -450,11 +346,11 @@ __global__ __launch_bounds__(256) void dbscan_core_list_kernel(Cfg c, const uint
 }
 
 // labels of the listed cells (the others were zero-filled): core -> rank of its root; border -> smallest rank among its core eps-neighbours
-__global__ __launch_bounds__(256) void dbscan_label_list_kernel(Cfg c, const uint8_t* __restrict__ dyn, const uint8_t* __restrict__ core,
-                                                                const float* __restrict__ xs, const float* __restrict__ ys,
-                                                                const float* __restrict__ flow, const int* __restrict__ parent,
-                                                                const int* __restrict__ root_rank, const int* __restrict__ list,
-                                                                const int* __restrict__ n_list, int* __restrict__ labels) {
+__global__ __launch_bounds__(256) void dbscan_label_kernel(Cfg c, const uint8_t* __restrict__ dyn, const uint8_t* __restrict__ core,
+                                                           const float* __restrict__ xs, const float* __restrict__ ys,
+                                                           const float* __restrict__ flow, const int* __restrict__ parent,
+                                                           const int* __restrict__ root_rank, const int* __restrict__ list,
+                                                           const int* __restrict__ n_list, int* __restrict__ labels) {
     const int lane = threadIdx.x & 63, n = *n_list;
     const size_t per = (size_t)c.gx * c.gy;
     for (int e = blockIdx.x * 4 + (threadIdx.x >> 6); e < n; e += gridDim.x * 4) {
@@ -613,19 +509,39 @@ inline size_t carve_list(void* base, size_t total, ListWs& w) {
 }
 inline unsigned list_grid(size_t total) { return (unsigned)(total / 4 + 1 < (size_t)kListGrid ? total / 4 + 1 : (size_t)kListGrid); }
 
+// the checks the two DBSCAN calls share (their pointers apart): *total = cells of the batch, w = the carved workspace
+inline int open_list(const liso_dbscan_cfg* cfg, void* workspace, size_t workspace_bytes, size_t* total, ListWs& w) {
+    const size_t need = liso_dbscan_workspace_bytes(cfg);
+    if (need == 0) return LISO_EINVAL;  // a bad cfg, or 2^31 cells or more
+    if (!workspace || workspace_bytes < need) return LISO_EWORKSPACE;
+    *total = (size_t)cfg->batch * cfg->gx * cfg->gy;
+    carve_list(workspace, *total, w);
+    return LISO_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
+size_t liso_dbscan_workspace_bytes(const liso_dbscan_cfg* cfg) {
+    if (!cfg_ok(cfg) || (size_t)cfg->batch * cfg->gx * cfg->gy >= (1ull << 31)) return 0;
+    ListWs w{};
+    return carve_list(nullptr, (size_t)cfg->batch * cfg->gx * cfg->gy, w);
+}
+
 int liso_dbscan_components(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords,
                            const float* col_coords, const float* flow, uint8_t* core, int32_t* parent, int32_t* is_root,
-                           void* stream) {
-    if (!cfg_ok(cfg) || !dynamic_mask || !row_coords || !col_coords || !flow || !core || !parent || !is_root) return LISO_EINVAL;
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (!dynamic_mask || !row_coords || !col_coords || !flow || !core || !parent || !is_root) return LISO_EINVAL;
+    size_t total;
+    ListWs w{};
+    if (const int rc = open_list(cfg, workspace, workspace_bytes, &total, w)) return rc;
     const Cfg c = to_cfg(cfg);
-    const size_t total = (size_t)c.batch * c.gx * c.gy;
     const unsigned blocks = (unsigned)((total + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
-    dbscan_core_kernel<<<blocks, 256, 0, st>>>(c, dynamic_mask, row_coords, col_coords, flow, core, parent);
+    dyn_count_kernel<<<w.blocks, kListThreads, 0, st>>>(dynamic_mask, (unsigned)total, w.block_cnt);
+    dyn_place_kernel<<<w.blocks, kListThreads, 0, st>>>(dynamic_mask, (unsigned)total, w.block_cnt, w.list, w.n_list, core, parent);
+    dbscan_core_kernel<<<list_grid(total), 256, 0, st>>>(c, dynamic_mask, row_coords, col_coords, flow, w.list, w.n_list, core, parent);
     if (c.win <= kMaxWin) {
         const int tiles_r = (c.gx + kTR - 1) / kTR, tiles_c = (c.gy + kTC - 1) / kTC;
         dbscan_union_tiled_kernel<<<dim3(tiles_r * tiles_c, c.batch), kUfThreads, 0, st>>>(c, dynamic_mask, core, row_coords, col_coords,
@@ -638,80 +554,17 @@ int liso_dbscan_components(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_ma
 }
 
 int liso_dbscan_labels(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords, const float* col_coords,
-                       const float* flow, const uint8_t* core, const int32_t* parent, const int32_t* root_rank,
-                       int32_t* labels, void* stream) {
-    if (!cfg_ok(cfg) || !dynamic_mask || !row_coords || !col_coords || !flow || !core || !parent || !root_rank || !labels)
-        return LISO_EINVAL;
-    const Cfg c = to_cfg(cfg);
-    const size_t total = (size_t)c.batch * c.gx * c.gy;
-    dbscan_label_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(c, dynamic_mask, core, row_coords,
-                                                                                       col_coords, flow, parent, root_rank, labels);
-    return check_launch();
-}
-
-size_t liso_dbscan_workspace_bytes(const liso_dbscan_cfg* cfg) {
-    if (!cfg_ok(cfg) || (size_t)cfg->batch * cfg->gx * cfg->gy >= (1ull << 31)) return 0;
+                       const float* flow, const uint8_t* core, const int32_t* parent, const int32_t* root_rank, int32_t* labels,
+                       const void* workspace, size_t workspace_bytes, void* stream) {
+    if (!dynamic_mask || !row_coords || !col_coords || !flow || !core || !parent || !root_rank || !labels) return LISO_EINVAL;
+    size_t total;
     ListWs w{};
-    return carve_list(nullptr, (size_t)cfg->batch * cfg->gx * cfg->gy, w);
-}
-
-int liso_dbscan_components_ws(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords,
-                              const float* col_coords, const float* flow, uint8_t* core, int32_t* parent, int32_t* is_root,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-    if (!cfg_ok(cfg) || !dynamic_mask || !row_coords || !col_coords || !flow || !core || !parent || !is_root) return LISO_EINVAL;
-    const size_t need = liso_dbscan_workspace_bytes(cfg);
-    if (need == 0) return LISO_EINVAL;  // (2^31 cells or more: liso_dbscan_components)
-    if (!workspace || workspace_bytes < need) return LISO_EWORKSPACE;
+    if (const int rc = open_list(cfg, (void*)workspace, workspace_bytes, &total, w)) return rc;
     const Cfg c = to_cfg(cfg);
-    const size_t total = (size_t)c.batch * c.gx * c.gy;
-    ListWs w{};
-    carve_list(workspace, total, w);
-    hipStream_t st = (hipStream_t)stream;
-    dyn_count_kernel<<<w.blocks, kListThreads, 0, st>>>(dynamic_mask, (unsigned)total, w.block_cnt);
-    dyn_list_kernel<<<w.blocks, kListThreads, 0, st>>>(dynamic_mask, (unsigned)total, w.block_cnt, w.list, w.n_list, core, parent);
-    dbscan_core_list_kernel<<<list_grid(total), 256, 0, st>>>(c, dynamic_mask, row_coords, col_coords, flow, w.list, w.n_list, core,
-                                                             parent);
-    if (c.win <= kMaxWin) {
-        const int tiles_r = (c.gx + kTR - 1) / kTR, tiles_c = (c.gy + kTC - 1) / kTC;
-        dbscan_union_tiled_kernel<<<dim3(tiles_r * tiles_c, c.batch), kUfThreads, 0, st>>>(c, dynamic_mask, core, row_coords, col_coords,
-                                                                                         flow, parent, tiles_r, tiles_c);
-    } else {
-        dbscan_union_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(c, dynamic_mask, core, row_coords, col_coords, flow, parent);
-    }
-    dbscan_flatten_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(c, core, parent, is_root);
-    return check_launch();
-}
-
-int liso_dbscan_labels_ws(const liso_dbscan_cfg* cfg, const uint8_t* dynamic_mask, const float* row_coords, const float* col_coords,
-                          const float* flow, const uint8_t* core, const int32_t* parent, const int32_t* root_rank, int32_t* labels,
-                          const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!cfg_ok(cfg) || !dynamic_mask || !row_coords || !col_coords || !flow || !core || !parent || !root_rank || !labels)
-        return LISO_EINVAL;
-    const size_t need = liso_dbscan_workspace_bytes(cfg);
-    if (need == 0) return LISO_EINVAL;
-    if (!workspace || workspace_bytes < need) return LISO_EWORKSPACE;
-    const Cfg c = to_cfg(cfg);
-    const size_t total = (size_t)c.batch * c.gx * c.gy;
-    ListWs w{};
-    carve_list((void*)workspace, total, w);
     hipStream_t st = (hipStream_t)stream;
     if (liso_zero::zero_async(labels, total * sizeof(int32_t), st) != hipSuccess) return LISO_ELAUNCH;
-    dbscan_label_list_kernel<<<list_grid(total), 256, 0, st>>>(c, dynamic_mask, core, row_coords, col_coords, flow, parent, root_rank,
-                                                              w.list, w.n_list, labels);
-    return check_launch();
-}
-
-int liso_region_props(const int32_t* labels, int batch, int gx, int gy, int max_labels, uint64_t* moments, double* props,
-                      void* stream) {
-    if (!labels || batch < 1 || gx < 1 || gy < 1 || max_labels < 1 || !moments || !props) return LISO_EINVAL;
-    if ((size_t)batch * gx * gy >= (1ull << 31)) return LISO_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t total = (size_t)batch * gx * gy;
-    const long regions = (long)batch * max_labels;
-    if (liso_zero::zero_async(moments, (size_t)regions * 6 * sizeof(uint64_t), st) != hipSuccess) return LISO_ELAUNCH;
-    region_moments_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(labels, batch, gx, gy, max_labels,
-                                                                          (unsigned long long*)moments);
-    region_props_kernel<<<(unsigned)((regions + 255) / 256), 256, 0, st>>>((const unsigned long long*)moments, regions, props);
+    dbscan_label_kernel<<<list_grid(total), 256, 0, st>>>(c, dynamic_mask, core, row_coords, col_coords, flow, parent, root_rank, w.list,
+                                                         w.n_list, labels);
     return check_launch();
 }
 
@@ -723,19 +576,26 @@ size_t liso_region_props_workspace_bytes(int batch, int gx, int gy, int max_labe
     return (size_t)batch * blocks * max_labels * 6 * sizeof(uint64_t);
 }
 
-int liso_region_props_ws(const int32_t* labels, int batch, int gx, int gy, int max_labels, uint64_t* moments, double* props,
-                         void* workspace, size_t workspace_bytes, void* stream) {
+int liso_region_props(const int32_t* labels, int batch, int gx, int gy, int max_labels, uint64_t* moments, double* props,
+                      void* workspace, size_t workspace_bytes, void* stream) {
     if (!labels || batch < 1 || gx < 1 || gy < 1 || max_labels < 1 || !moments || !props) return LISO_EINVAL;
-    const size_t need = liso_region_props_workspace_bytes(batch, gx, gy, max_labels);
-    if (need == 0) return liso_region_props(labels, batch, gx, gy, max_labels, moments, props, stream);  // (> 1024 labels: atomics path)
-    if (!workspace || workspace_bytes < need) return LISO_EWORKSPACE;
+    const size_t total = (size_t)batch * gx * gy;
+    if (total >= (1ull << 31)) return LISO_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int blocks = (int)(((size_t)gx * gy + kRmCells - 1) / kRmCells);
     const long regions = (long)batch * max_labels;
-    region_moments_lds_kernel<<<dim3(blocks, batch), kRmThreads, (size_t)max_labels * 6 * sizeof(uint64_t), st>>>(
-        labels, gx, gy, max_labels, blocks, (unsigned long long*)workspace);
-    region_moments_sum_kernel<<<(unsigned)((regions + 3) / 4), 256, 0, st>>>((const unsigned long long*)workspace, batch, max_labels,
-                                                                            blocks, (unsigned long long*)moments);
+    const size_t need = liso_region_props_workspace_bytes(batch, gx, gy, max_labels);
+    if (need == 0) {  // more than 1024 labels: the atomics path, no workspace
+        if (liso_zero::zero_async(moments, (size_t)regions * 6 * sizeof(uint64_t), st) != hipSuccess) return LISO_ELAUNCH;
+        region_moments_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(labels, batch, gx, gy, max_labels,
+                                                                              (unsigned long long*)moments);
+    } else {
+        if (!workspace || workspace_bytes < need) return LISO_EWORKSPACE;
+        const int blocks = (int)(((size_t)gx * gy + kRmCells - 1) / kRmCells);
+        region_moments_lds_kernel<<<dim3(blocks, batch), kRmThreads, (size_t)max_labels * 6 * sizeof(uint64_t), st>>>(
+            labels, gx, gy, max_labels, blocks, (unsigned long long*)workspace);
+        region_moments_sum_kernel<<<(unsigned)((regions + 3) / 4), 256, 0, st>>>((const unsigned long long*)workspace, batch, max_labels,
+                                                                                blocks, (unsigned long long*)moments);
+    }
     region_props_kernel<<<(unsigned)((regions + 255) / 256), 256, 0, st>>>((const unsigned long long*)moments, regions, props);
     return check_launch();
 }

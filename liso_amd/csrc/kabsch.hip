@@ -440,13 +440,6 @@ size_t liso_kabsch_workspace_bytes(const liso_kabsch_cfg* cfg) {
     return (size_t)cfg->batch * num_blocks(cfg->n_points) * (cfg->n_slots + 2) * NM * sizeof(float);
 }
 
-int liso_kabsch_trafos_f32(const liso_kabsch_cfg* cfg, const float* points, const uint8_t* valid, const float* flow,
-                           const float* box_pos, const float* box_dims, const float* box_rot, double* trafos,
-                           float* cum_wts, float* fg_weights, void* workspace, size_t workspace_bytes, void* stream) {
-    return liso_kabsch_trafos_counted_f32(cfg, points, valid, flow, box_pos, box_dims, box_rot, nullptr, trafos, cum_wts, fg_weights,
-                                          workspace, workspace_bytes, stream);
-}
-
 int liso_kabsch_trafos_counted_f32(const liso_kabsch_cfg* cfg, const float* points, const uint8_t* valid, const float* flow,
                                    const float* box_pos, const float* box_dims, const float* box_rot, const int32_t* slot_count,
                                    double* trafos, float* cum_wts, float* fg_weights, void* workspace, size_t workspace_bytes,

@@ -1,5 +1,5 @@
 // Sparse form of the SLIM encoders' first convolution (7x7, stride 2, padding 3, 64 -> 32 channels, fp32 tensors) for gfx950.
-// C ABI + the reference lines it replaces: include/liso_conv.h (liso_sparse_stem_*).
+// C ABI + the reference lines it replaces: include/liso_conv.h (liso_sparse_conv_*).
 //
 // The input is the pillar canvas: 1-6 % of its 512^2 cells hold a pillar, the rest are exact zeros.  The dense implicit GEMM (with
 // tile skipping) still multiplies every 8 x 32-pixel tile that has one occupied cell in its window: 0.39 ms for 8 sweeps, 500 MB
@@ -591,17 +591,6 @@ int liso_sparse_conv_dgrad(const void* dy, long dy_pix_stride, int is_bf16, cons
     else return LISO_EINVAL;
 #undef LISO_SPARSE_DG
     return hipGetLastError() == hipSuccess ? LISO_OK : LISO_ELAUNCH;
-}
-
-size_t liso_sparse_stem_workspace_bytes(int batch, int hi, int wi, int max_cells_per_sample) {
-    return liso_sparse_conv_workspace_bytes(batch, hi, wi, 7, 32, max_cells_per_sample, 0);
-}
-
-int liso_sparse_stem_forward_f32(const float* x, long x_pix_stride, const float* occupancy, const void* w_packed, const float* bias,
-                                 int batch, int hi, int wi, int max_cells_per_sample, int relu, float* y, float* stats_partial,
-                                 int* overflow, void* workspace, size_t workspace_bytes, void* stream) {
-    return liso_sparse_conv_forward(x, x_pix_stride, 0, occupancy, w_packed, bias, batch, hi, wi, 7, 32, max_cells_per_sample, relu, y,
-                                    stats_partial, nullptr, overflow, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -2,12 +2,27 @@
 (:14-336) and `fit_bev_box_z_and_height_using_points_in_box` (:339-384), built from the device stages BEV dynamicness
 (D1), clustering + region moments (D2), z-fit (D3), Kabsch heading/velocity (D4-D6).  TensorBoard image logging
 (:250-309) is not part of the path."""
+import ctypes
+
 import numpy as np
 import torch
 
 from liso_amd import _lib as L
 from liso_amd.kabsch.shape_utils import Shape, extract_motion_in_pred_box_coordinates
 from liso_amd.utils.bev_flow_utils import get_bev_dynamic_flow_map_from_pcl_flow_and_odom
+
+
+def _fit_box_z_into(pts, pos, dims, rot, box_height, num, fz, fh):
+    """one sample: pts fp32 [N, >= 3] (the kernel reads x, y, z with the row stride), pos [K, 2|3], dims [K, 2|3], rot [K], all
+    fp32 and dense -> the caller's num int64 [K], fz fp32 [K], fh fp32 [K]"""
+    lib = L.lib()
+    K = pos.shape[0]
+    nbytes = lib.liso_fit_box_z_workspace_bytes(pts.shape[0], K)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=pts.device)
+    with torch.cuda.device(pts.device):
+        L.check(L.TIMER.launch("fit_box_z", lambda: lib.liso_fit_box_z_f32(
+            L.ptr(pts), pts.shape[-1], pts.shape[0], L.ptr(pos), pos.shape[-1], L.ptr(dims), dims.shape[-1], L.ptr(rot), K,
+            float(box_height), L.ptr(num), L.ptr(fz), L.ptr(fh), L.ptr(ws), nbytes, L.stream_ptr())), "fit_box_z")
 
 
 @torch.no_grad()
@@ -26,13 +41,7 @@ def fit_bev_box_z_and_height_using_points_in_box(pcl, boxes: Shape, box_height=1
     if K == 0:
         return num, fz, fh
     pos, dims, rot = boxes.pos.float().contiguous(), boxes.dims.float().contiguous(), boxes.rot[..., 0].float().contiguous()
-    lib = L.lib()
-    nbytes = lib.liso_fit_box_z_workspace_bytes(pts.shape[0], K)
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        L.check(L.TIMER.launch("fit_box_z", lambda: lib.liso_fit_box_z_f32(
-            L.ptr(pts), pts.shape[-1], pts.shape[0], L.ptr(pos), pos.shape[-1], L.ptr(dims), dims.shape[-1], L.ptr(rot), K,
-            float(box_height), L.ptr(num), L.ptr(fz), L.ptr(fh), L.ptr(ws), nbytes, L.stream_ptr())), "fit_box_z")
+    _fit_box_z_into(pts, pos, dims, rot, box_height, num, fz, fh)
     return num, fz, fh
 
 
@@ -58,18 +67,19 @@ def cluster_dynamic_pillars(dynamic_mask, bev_nonrigid_flow, row_coords_m, col_c
     is_root = torch.empty((B, gx, gy), dtype=torch.int32, device=dev)
     labels = torch.empty((B, gx, gy), dtype=torch.int32, device=dev)
     lib = L.lib()
-    import ctypes
-    nbytes = lib.liso_dbscan_workspace_bytes(ctypes.byref(cfg))  # the list of dynamic pillars (0: 2^31 cells or more -> the dense passes)
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    nbytes = lib.liso_dbscan_workspace_bytes(ctypes.byref(cfg))  # the list of dynamic pillars
+    if nbytes == 0:
+        raise L.LisoHipError(f"liso_dbscan_workspace_bytes: batch {B} x grid {gx} x {gy} has 2^31 cells or more, or a bad config "
+                             f"(min_samples {min_samples}, eps {eps})")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         args = (ctypes.byref(cfg), L.ptr(dyn), L.ptr(xs), L.ptr(ys), L.ptr(flow), L.ptr(core), L.ptr(parent), L.ptr(is_root))
-        L.check(L.TIMER.launch("dbscan_components", lambda: lib.liso_dbscan_components_ws(*args, L.ptr(ws), nbytes, L.stream_ptr())
-                               if nbytes else lib.liso_dbscan_components(*args, L.stream_ptr())), "dbscan_components")
+        L.check(L.TIMER.launch("dbscan_components", lambda: lib.liso_dbscan_components(*args, L.ptr(ws), nbytes, L.stream_ptr())),
+                "dbscan_components")
         from liso_amd.networks.flow_cluster_detector.mining_ops import inclusive_scan_i32
         rank = inclusive_scan_i32(is_root.view(B, -1)).view(B, gx, gy)  # (own scan: no memset node when captured into a hipGraph)
         largs = (ctypes.byref(cfg), L.ptr(dyn), L.ptr(xs), L.ptr(ys), L.ptr(flow), L.ptr(core), L.ptr(parent), L.ptr(rank), L.ptr(labels))
-        L.check(L.TIMER.launch("dbscan_labels", lambda: lib.liso_dbscan_labels_ws(*largs, L.ptr(ws), nbytes, L.stream_ptr())
-                               if nbytes else lib.liso_dbscan_labels(*largs, L.stream_ptr())), "dbscan_labels")
+        L.check(L.TIMER.launch("dbscan_labels", lambda: lib.liso_dbscan_labels(*largs, L.ptr(ws), nbytes, L.stream_ptr())), "dbscan_labels")
     return labels, rank.view(B, -1)[:, -1].long()
 
 
@@ -86,7 +96,7 @@ def label_region_props(labels, max_labels):
     nbytes = lib.liso_region_props_workspace_bytes(B, gx, gy, max_labels)  # (0: more labels than the LDS path holds -> atomics path)
     ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=lab.device)
     with torch.cuda.device(lab.device):
-        L.check(L.TIMER.launch("region_props", lambda: lib.liso_region_props_ws(
+        L.check(L.TIMER.launch("region_props", lambda: lib.liso_region_props(
             L.ptr(lab), B, gx, gy, max_labels, L.ptr(mom), L.ptr(props), L.ptr(ws), nbytes, L.stream_ptr())), "region_props")
     return props
 
@@ -178,15 +188,9 @@ class FlowClusterDetector(torch.nn.Module):
         num_pts = zbuf[:B * k_max * 8].view(torch.int64).view(B, k_max)
         fit_z = zbuf[B * k_max * 8:B * k_max * 12].view(torch.float32).view(B, k_max)
         fit_h = zbuf[B * k_max * 12:].view(torch.float32).view(B, k_max)
-        lib = L.lib()
         for b in range(B):
-            pts = pcl_w_ground[b].float().contiguous()  # [M, >= 3]: the kernel reads x, y, z with the row stride
-            nbytes = lib.liso_fit_box_z_workspace_bytes(pts.shape[0], k_max)
-            ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                L.check(L.TIMER.launch("fit_box_z", lambda: lib.liso_fit_box_z_f32(
-                    L.ptr(pts), pts.shape[-1], pts.shape[0], L.ptr(center[b]), 2, L.ptr(dims2_f32[b]), 2, L.ptr(rot1_f32[b]), k_max,
-                    1000.0, L.ptr(num_pts[b]), L.ptr(fit_z[b]), L.ptr(fit_h[b]), L.ptr(ws), nbytes, L.stream_ptr())), "fit_box_z")
+            _fit_box_z_into(pcl_w_ground[b].float().contiguous(), center[b], dims2_f32[b], rot1_f32[b], 1000.0, num_pts[b], fit_z[b],
+                            fit_h[b])
         # plausibility filters + dropping the rejected boxes of every sample + zero padding (reference :208-248, :311), one launch
         arr = MO.filter_compact(num_labels, center, dims2, rot1, num_pts, fit_z, fit_h, min_points=self.min_num_pts_per_box,
                                 aspect_ratio_max=self.aspect_ratio_max, max_box_len_m=self.max_box_len_m,

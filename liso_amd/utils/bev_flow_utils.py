@@ -23,7 +23,7 @@ def get_bev_dynamic_flow_map_from_pcl_flow_and_odom(*, pcl_is_valid, pcl, pillar
     dyn = torch.empty((B, h, w, 1), dtype=torch.float32, device=dev)
     nrf = torch.empty((B, h, w, 3), dtype=torch.float32, device=dev)
     lib = L.lib()
-    nbytes = lib.liso_bev_dynamic_flow_record_workspace_bytes(B, h, w)  # one record per pillar: sums and count side by side
+    nbytes = lib.liso_bev_dynamic_flow_workspace_bytes(B, h, w)  # one record per pillar: sums and count side by side
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         L.check(L.TIMER.launch("bev_dynamic_flow", lambda: lib.liso_bev_dynamic_flow_f32(

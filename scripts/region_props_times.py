@@ -39,5 +39,5 @@ for name, nblob, size in (("empty", 0, 0), ("30 blobs of 12x12", 30, 12), ("30 b
     mom = torch.zeros((1, K, 6), dtype=torch.int64, device=dev)
     ws = torch.empty(max(lib.liso_region_props_workspace_bytes(1, G, G, K), 8), dtype=torch.uint8, device=dev)
     props = torch.zeros((1, K, 5), dtype=torch.float64, device=dev)
-    t = timeit(lambda: L.check(lib.liso_region_props_ws(L.ptr(lab), 1, G, G, K, L.ptr(mom), L.ptr(props), L.ptr(ws), ws.numel(), L.stream_ptr()), "rp"))
+    t = timeit(lambda: L.check(lib.liso_region_props(L.ptr(lab), 1, G, G, K, L.ptr(mom), L.ptr(props), L.ptr(ws), ws.numel(), L.stream_ptr()), "rp"))
     print(f"{name:22s}: {t:7.1f} us per call (zero fill + moments + props), labelled cells {int((lab > 0).sum())}")

@@ -5,8 +5,8 @@ patterns where the scatter takes another path: a block merges the equal cells of
 The inputs are chosen so that the host restatement has no rounding of its own to argue about: the odometry is the identity
 (inv(odom) - I = 0, the static flow is exactly 0 whether or not the compiler contracts the fp64 products), and the flow components
 are multiples of 1/16 m up to +-100 m (squares and their sum are exact in fp32, so |flow| is one correctly rounded sqrt).  The
-fixed-point sums are integers: any grouping gives the same bits.  Both workspace layouts (one record per pillar; sums and counts in
-two arrays) must give the same maps.  Every device buffer lies between guard bands (tests/guarded_alloc.py)."""
+fixed-point sums are integers: any grouping gives the same bits.  The workspace holds one 40-byte record per pillar and is exactly
+the size the query names.  Every device buffer lies between guard bands (tests/guarded_alloc.py)."""
 import numpy as np
 import pytest
 import torch
@@ -95,9 +95,8 @@ def reference(valid, rows, cols, flow, B, h, w):
 def test_scatter_means_bit_for_bit(h, w, B):
     L = _L()
     lib = L.lib()
-    record = lib.liso_bev_dynamic_flow_record_workspace_bytes(B, h, w)
-    planar = lib.liso_bev_dynamic_flow_workspace_bytes(B, h, w)
-    assert record == 40 * B * h * w and planar == 36 * B * h * w
+    nbytes = lib.liso_bev_dynamic_flow_workspace_bytes(B, h, w)
+    assert nbytes == 40 * B * h * w
     ome = dev(np.zeros((B, 4, 4), np.float64))
     for n in SIZES:
         rng = np.random.default_rng(1000 * n + 10 * h + B)
@@ -115,14 +114,13 @@ def test_scatter_means_bit_for_bit(h, w, B):
             tag = f"{what}, n={n}"
             with guarded() as gd:
                 args = dev(pts), dev(valid), dev(np.stack([rows, cols], -1)), dev(flow)
-                for layout, nbytes in (("record", record), ("planar", planar)):
-                    dyn, nrf = poisoned((B, h, w, 1), torch.float32), poisoned((B, h, w, 3), torch.float32)
-                    ws = poisoned((nbytes,), torch.uint8)
-                    rc = lib.liso_bev_dynamic_flow_f32(L.ptr(args[0]), 3, L.ptr(args[1]), L.ptr(args[2]), L.ptr(args[3]), 3, L.ptr(ome),
-                                                       B, n, h, w, L.ptr(dyn), L.ptr(nrf), L.ptr(ws), nbytes, L.stream_ptr())
-                    assert rc == 0, (tag, layout, rc)
-                    assert_bits(f"dynamicness ({tag}, {layout})", dyn, want_dyn)
-                    assert_bits(f"nonrigid flow ({tag}, {layout})", nrf, want_nrf)
+                dyn, nrf = poisoned((B, h, w, 1), torch.float32), poisoned((B, h, w, 3), torch.float32)
+                ws = poisoned((nbytes,), torch.uint8)
+                rc = lib.liso_bev_dynamic_flow_f32(L.ptr(args[0]), 3, L.ptr(args[1]), L.ptr(args[2]), L.ptr(args[3]), 3, L.ptr(ome),
+                                                   B, n, h, w, L.ptr(dyn), L.ptr(nrf), L.ptr(ws), nbytes, L.stream_ptr())
+                assert rc == 0, (tag, rc)
+                assert_bits(f"dynamicness ({tag})", dyn, want_dyn)
+                assert_bits(f"nonrigid flow ({tag})", nrf, want_nrf)
                 gd.check()
 
 
@@ -134,12 +132,13 @@ def test_the_patterns_reach_the_paths_they_are_named_for():
     assert np.unique(crowd).size > 8 + PROBES - 1 and np.all((home_slot(crowd) >= 100) & (home_slot(crowd) < 108))
 
 
-def test_a_workspace_below_the_planar_size_is_refused():
+def test_a_workspace_below_the_record_size_is_refused():
     L = _L()
     lib = L.lib()
     B, n, h, w = 1, 4, 8, 8
     z = torch.zeros(64, dtype=torch.float64, device=DEV)
-    nbytes = lib.liso_bev_dynamic_flow_workspace_bytes(B, h, w) - 1
+    nbytes = 40 * B * h * w - 1
+    assert nbytes == lib.liso_bev_dynamic_flow_workspace_bytes(B, h, w) - 1
     ws = torch.zeros(nbytes, dtype=torch.uint8, device=DEV)
     rc = lib.liso_bev_dynamic_flow_f32(L.ptr(z), 3, L.ptr(z), L.ptr(z), L.ptr(z), 3, L.ptr(z), B, n, h, w, L.ptr(z), L.ptr(z),
                                        L.ptr(ws), nbytes, L.stream_ptr())

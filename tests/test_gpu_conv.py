@@ -354,7 +354,7 @@ def test_small_channel_7x7_weight_gradient_matches_fp64(B, ci_true, co, H, W, k)
 @pytest.mark.parametrize("B,H,W,density", [(2, 128, 128, 0.02), (1, 64, 192, 0.3), (3, 512, 512, 0.016), (2, 64, 64, 0.0), (1, 32, 64, 1.0)])
 @pytest.mark.parametrize("norm_kind", ["instance", "none"])
 def test_sparse_stem_convolution_equals_the_dense_kernel(B, H, W, density, norm_kind, monkeypatch):
-    """liso_sparse_stem_forward_f32 (the encoders' 7x7 / 2 stem on the pillar canvas, only occupied cells multiplied) against the dense
+    """liso_sparse_conv_forward with k = 7, co = 32 (the encoders' 7x7 / 2 stem on the pillar canvas, only occupied cells multiplied) against the dense
     F32X3 kernel on the same canvas: same raw output up to the fp32 summation order (the dense kernel adds all taps into one
     accumulator, the sparse one adds per-tap products), pixels whose window is empty equal the bias bit for bit, the pending
     InstanceNorm statistics agree, border cells / odd columns / full and empty canvases included; the overflow flag stays clear"""
