@@ -320,6 +320,8 @@ SIGNATURES = {
     "liso_det_val_match_f32": (_i, [_i, _i, _i] + [_vp] * 10 + [_i, _vp, _i, _vp, _i] + [_vp] * 6),
     "liso_det_val_assign_f32": (_i, [_i, _i, _i] + [_vp] * 8 + [_i, _vp, _i, _vp, _i] + [_vp] * 5),
     "liso_match_assign_f32": (_i, [_vp, ctypes.c_long, _i, _i, _f, _vp, _vp, _vp]),
+    # include/liso_nusc_metrics.h
+    "liso_det_val_nusc_f32": (_i, [_i, _i, _i] + [_vp] * 8 + [_i, _i, _vp, _i] + [_vp] * 6),
     # include/liso_ground.h
     "liso_ground_jcp_workspace_bytes": (_sz, [_vp]),
     "liso_ground_jcp_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),

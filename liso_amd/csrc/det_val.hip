@@ -1,6 +1,7 @@
 // Detector validation matching for gfx950 (MI355X), C ABI in include/liso_det_val.h: the pair matrices of every frame of a padded
 // batch in one launch, run_val's class transfer in one launch, every (job, frame) greedy matching in one launch, and every (job, frame)
-// optimal assignment of the Waymo-style collections in one launch (assign_kernel, further down).
+// optimal assignment of the Waymo-style collections in one launch (assign_kernel, further down); and the per-frame part of the
+// nuScenes detection metrics, every (frame, distance threshold) walk in one launch (nusc_kernel, include/liso_nusc_metrics.h).
 //
 // The work per matching is tiny (tens of boxes) and there are thousands of them per validation batch, so the shape is: one
 // wavefront per (job, frame) cell, the serial walk over the predictions kept short --
@@ -24,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/liso_det_val.h"
+#include "../../include/liso_nusc_metrics.h"
 
 namespace {
 
@@ -175,15 +177,10 @@ __device__ __forceinline__ int greedy_walk(const float* __restrict__ val, bool s
     return m;
 }
 
-// the three true-positive error terms of one match (header), fp32
-__host__ __device__ inline void tp_terms(const float* g, const float* p, float& ate, float& ase, float& aoe) {
-    ate = centre_dist(g, p);
-    const float inter = nan_min(g[3], p[3]) * nan_min(g[4], p[4]) * nan_min(g[5], p[5]);
-    const float uni = g[3] * g[4] * g[5] + p[3] * p[4] * p[5] - inter;
-    const float den = uni < 1e-6f ? 1e-6f : uni;
-    ase = 1.0f - inter / den;
+// the AOE term of one match (header), fp32
+__host__ __device__ inline float orient_term(float yaw_gt, float yaw_pred) {
     const float pi = 3.14159265358979323846f, two_pi = (float)(2.0 * 3.14159265358979323846);
-    float r = fmodf(g[6] - p[6] + pi, two_pi);
+    float r = fmodf(yaw_gt - yaw_pred + pi, two_pi);
     if (r != 0.f) {
         if (r < 0.f) r = r + two_pi;
     } else {
@@ -191,7 +188,17 @@ __host__ __device__ inline void tp_terms(const float* g, const float* p, float& 
     }
     float d = r - pi;
     if (d > pi) d = d - two_pi;
-    aoe = fabsf(d);
+    return fabsf(d);
+}
+
+// the three true-positive error terms of one match (header), fp32
+__host__ __device__ inline void tp_terms(const float* g, const float* p, float& ate, float& ase, float& aoe) {
+    ate = centre_dist(g, p);
+    const float inter = nan_min(g[3], p[3]) * nan_min(g[4], p[4]) * nan_min(g[5], p[5]);
+    const float uni = g[3] * g[4] * g[5] + p[3] * p[4] * p[5] - inter;
+    const float den = uni < 1e-6f ? 1e-6f : uni;
+    ase = 1.0f - inter / den;
+    aoe = orient_term(g[6], p[6]);
 }
 
 struct MatchArgs {
@@ -543,6 +550,151 @@ __global__ __launch_bounds__(64) void assign_plain_kernel(int G, int P, int M, c
     if (lane == 0) count[cell] = kept;
 }
 
+// ---- nuScenes detection metrics, the per-frame part (include/liso_nusc_metrics.h) -----------------------------------------------------
+// One wavefront per (frame, threshold) cell.  Unlike match_kernel the walk reads no pair matrix: a lane keeps x, y and class of its
+// ground-truth slots in registers next to the "member and free" bits and computes the centre distance of a step on the fly; the
+// member predictions are compacted into visiting order in LDS first, so the serial loop has no skipped iterations.  The best
+// candidate of a step is a 64-bit key maximum (~bits of the distance, ~slot): distances are >= +0 and never NaN here, so their bit
+// patterns order like their values -- smallest distance, lowest slot on ties.
+struct NuscArgs {
+    int G, P, T, M, n_classes, as_one;
+    const float* gt;
+    const uint8_t* gv;
+    const int32_t* gc;
+    const float* pred;
+    const uint8_t* pv;
+    const int32_t* pc;
+    const int32_t* order;
+    const float* radius;
+    float thr[LISO_NUSC_MAX_THRESHOLDS];
+    int32_t* count;
+    int16_t* pairs;
+    float* err;
+    uint8_t* gt_in;
+    uint8_t* pred_in;
+};
+
+// the header's membership; `cls` is already 0 when every box counts as one class
+__device__ __forceinline__ bool nusc_member(float x, float y, uint8_t valid, int cls, int n_classes, const float* __restrict__ radius) {
+    if (!valid || cls < 0 || cls >= n_classes) return false;
+    return sqrtf(x * x + y * y) <= radius[cls];  // NaN fails
+}
+
+// the header's scale term: the prediction's sizes raised to 1e-4f, no clamp on the union
+__host__ __device__ inline float nusc_scale_term(const float* g, const float* p) {
+    const float sx = p[3] < 1e-4f ? 1e-4f : p[3], sy = p[4] < 1e-4f ? 1e-4f : p[4], sz = p[5] < 1e-4f ? 1e-4f : p[5];
+    const float inter = (nan_min(g[3], sx) * nan_min(g[4], sy)) * nan_min(g[5], sz);
+    const float uni = (g[3] * g[4]) * g[5] + (sx * sy) * sz - inter;
+    return 1.0f - inter / uni;
+}
+
+__global__ __launch_bounds__(64) void nusc_kernel(NuscArgs a) {
+    __shared__ float s_px[kMaxBoxes], s_py[kMaxBoxes];
+    __shared__ int s_pc[kMaxBoxes];
+    __shared__ int s_pair[kMaxBoxes];     // (gt slot << 16) | pred slot
+    __shared__ int16_t s_vis[kMaxBoxes];  // the member predictions in visiting order
+    __shared__ uint8_t s_pin[kMaxBoxes];
+    const int lane = threadIdx.x;
+    const size_t cell = blockIdx.x;
+    const int f = (int)(cell / (size_t)a.T), t = (int)(cell - (size_t)f * a.T);
+    const int G = a.G, P = a.P, M = a.M;
+    const float thr = a.thr[t];
+    const float* gt = a.gt + (size_t)f * G * 7;
+    const float* pred = a.pred + (size_t)f * P * 7;
+    const int owned = (G + 63) >> 6;
+    float gx[kOwned], gy[kOwned];
+    int gc[kOwned];
+    uint32_t avail = 0u;
+#pragma unroll
+    for (int r = 0; r < kOwned; ++r) {
+        const int g = lane + 64 * r;
+        float x = 0.f, y = 0.f;
+        int c = -1;
+        bool in = false;
+        if (g < G) {
+            const size_t s = (size_t)f * G + g;
+            c = a.as_one ? 0 : a.gc[s];
+            x = gt[(size_t)g * 7], y = gt[(size_t)g * 7 + 1];
+            in = nusc_member(x, y, a.gv[s], c, a.n_classes, a.radius);
+            if (t == 0) a.gt_in[s] = in ? 1 : 0;  // the same for every threshold: the frame's first cell writes it
+        }
+        gx[r] = x, gy[r] = y, gc[r] = c;  // (assigned outside the branch: the arrays stay plain registers)
+        avail |= (in ? 1u : 0u) << r;
+    }
+    for (int p = lane; p < P; p += 64) {
+        const size_t s = (size_t)f * P + p;
+        const int c = a.as_one ? 0 : a.pc[s];
+        const float x = pred[(size_t)p * 7], y = pred[(size_t)p * 7 + 1];
+        const bool in = nusc_member(x, y, a.pv[s], c, a.n_classes, a.radius);
+        if (t == 0) a.pred_in[s] = in ? 1 : 0;
+        s_pin[p] = in ? 1 : 0;
+        s_px[p] = x, s_py[p] = y, s_pc[p] = c;
+    }
+    __syncthreads();
+    int n_vis = 0;
+    for (int base = 0; base < P; base += 64) {
+        const int k = base + lane;
+        int p = -1;
+        if (k < P) {
+            p = a.order[(size_t)f * P + k];
+            if (p < 0 || p >= P || !s_pin[p]) p = -1;
+        }
+        const unsigned long long b = __ballot(p >= 0);
+        if (p >= 0) s_vis[n_vis + __popcll(b & ((1ull << lane) - 1ull))] = (int16_t)p;
+        n_vis += __popcll(b);
+    }
+    __syncthreads();
+    int m = 0;
+#pragma unroll 1
+    for (int k = 0; k < n_vis; ++k) {
+        const int p = s_vis[k];
+        const float px = s_px[p], py = s_py[p];
+        const int pc = s_pc[p];
+        unsigned long long key = 0;
+#pragma unroll
+        for (int r = 0; r < kOwned; ++r) {
+            if (r >= owned) break;
+            if (!((avail >> r) & 1u) || gc[r] != pc) continue;
+            const float dx = gx[r] - px, dy = gy[r] - py;
+            const float d = sqrtf(dx * dx + dy * dy);
+            if (d < thr) {  // NaN never passes
+                const unsigned long long kk =
+                    ((unsigned long long)(0xFFFFFFFFu - __float_as_uint(d)) << 32) | (0xFFFFFFFFu - (uint32_t)(lane + 64 * r));
+                key = kk > key ? kk : key;
+            }
+        }
+        if (__ballot(key != 0ull) == 0ull) continue;
+        const unsigned long long top = wave_max_u64(key);
+        const int bi = (int)(0xFFFFFFFFu - (uint32_t)top);
+        if ((bi & 63) == lane) avail &= ~(1u << (bi >> 6));
+        if (lane == 0 && m < M) s_pair[m] = (bi << 16) | p;
+        ++m;
+    }
+    if (m > M) m = M;  // (only an `order` that names a slot twice gets here)
+    __syncthreads();
+    int16_t* pairs = a.pairs + cell * (size_t)M * 2;
+    float* err = a.err + cell * (size_t)M * 3;
+#pragma unroll 1
+    for (int i = lane; i < M; i += 64) {
+        int g = -1, p = -1;
+        float e_t = 0.f, e_s = 0.f, e_o = 0.f;
+        if (i < m) {
+            g = s_pair[i] >> 16, p = s_pair[i] & 0xFFFF;
+            const float* gb = gt + (size_t)g * 7;
+            const float* pb = pred + (size_t)p * 7;
+            e_t = centre_dist(gb, pb);
+            e_s = nusc_scale_term(gb, pb);
+            e_o = orient_term(gb[6], pb[6]);
+            const float qnan = __uint_as_float(0x7FC00000u);  // one NaN pattern, whatever operation made it
+            if (e_s != e_s) e_s = qnan;
+            if (e_o != e_o) e_o = qnan;
+        }
+        pairs[2 * i] = (int16_t)g, pairs[2 * i + 1] = (int16_t)p;
+        err[3 * i] = e_t, err[3 * i + 1] = e_s, err[3 * i + 2] = e_o;
+    }
+    if (lane == 0) a.count[cell] = m;
+}
+
 bool bad_shape(int frames, int G, int P) { return frames < 0 || G < 0 || P < 0 || G > kMaxBoxes || P > kMaxBoxes; }
 
 }  // namespace
@@ -667,6 +819,27 @@ int liso_match_assign_f32(const float* value_pred_major, long batch, int n_gt, i
     if (M > 0 && (!value_pred_major || !pairs)) return LISO_EINVAL;
     hipLaunchKernelGGL(assign_plain_kernel, dim3((unsigned)batch), dim3(64), 0, (hipStream_t)stream, n_gt, n_pred, M, value_pred_major,
                        threshold, count, pairs);
+    return check_launch();
+}
+
+int liso_det_val_nusc_f32(int frames, int n_gt, int n_pred, const float* gt, const uint8_t* gt_valid, const int32_t* gt_class,
+                          const float* pred, const uint8_t* pred_valid, const int32_t* pred_class, const int32_t* order,
+                          const float* radius, int n_classes, int as_one, const float* thresholds, int n_thresholds, int32_t* count,
+                          int16_t* pairs, float* err, uint8_t* gt_in, uint8_t* pred_in, void* stream) {
+    if (bad_shape(frames, n_gt, n_pred) || n_classes < 1 || n_thresholds < 1 || n_thresholds > LISO_NUSC_MAX_THRESHOLDS) return LISO_EINVAL;
+    if (frames == 0) return LISO_OK;
+    if (!radius || !thresholds || !count) return LISO_EINVAL;
+    if (n_gt > 0 && (!gt || !gt_valid || !gt_in || (!as_one && !gt_class))) return LISO_EINVAL;
+    if (n_pred > 0 && (!pred || !pred_valid || !order || !pred_in || (!as_one && !pred_class))) return LISO_EINVAL;
+    const int M = n_gt < n_pred ? n_gt : n_pred;
+    if (M > 0 && (!pairs || !err)) return LISO_EINVAL;
+    if ((long long)frames * n_thresholds > 0x7FFFFFFFLL) return LISO_EINVAL;
+    NuscArgs a;
+    a.G = n_gt, a.P = n_pred, a.T = n_thresholds, a.M = M, a.n_classes = n_classes, a.as_one = as_one ? 1 : 0;
+    a.gt = gt, a.gv = gt_valid, a.gc = gt_class, a.pred = pred, a.pv = pred_valid, a.pc = pred_class, a.order = order, a.radius = radius;
+    for (int i = 0; i < LISO_NUSC_MAX_THRESHOLDS; ++i) a.thr[i] = i < n_thresholds ? thresholds[i] : 0.f;
+    a.count = count, a.pairs = pairs, a.err = err, a.gt_in = gt_in, a.pred_in = pred_in;
+    hipLaunchKernelGGL(nusc_kernel, dim3((unsigned)(frames * n_thresholds)), dim3(64), 0, (hipStream_t)stream, a);
     return check_launch();
 }
 

@@ -23,6 +23,12 @@ taken is this package's own rule, the one `assign_host` states (rows in ascendin
 column first, then the lowest column position); scipy's linear_sum_assignment, which the reference and the per-frame path call, leaves it unspecified.
 The ground truth's `difficulty` travels as one byte per box (difficulty > 0) and reaches the host with the one flush.  Optimal
 assignment on the centre distance is not built.
+
+nuScenes collections (`Collection(..., kind="nusc")`, liso_amd/eval/nuscenes_metrics.py: mAP over centre-distance thresholds, the
+true-positive errors, NDS) use neither the job tables nor the pair matrices: each costs one more launch per batch,
+liso_det_val_nusc_f32 (include/liso_nusc_metrics.h), on the class-transferred predictions, and its outputs ride in the one flush.  A
+collection with `sigmoid_scores=True` walks in the stable order of the fp32 sigmoid of the scores (one sigmoid and one
+`det_nms.order` more per batch, shared by all such collections).
 """
 import ctypes
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
@@ -31,6 +37,8 @@ import numpy as np
 import torch
 
 from liso_amd import _lib as L
+from liso_amd.eval.nuscenes_metrics import NUSC_MOVABLE_CLASSES, NuscenesObjectDetectionMetrics, nusc_match_host, nusc_match_packed
+from liso_amd.eval.nuscenes_metrics import OUT_KEYS as NUSC_OUT_KEYS
 from liso_amd.eval.od_metrics import ObjectDetectionMetrics, WaymoObjectDetectionMetrics
 from liso_amd.kabsch.shape_utils import Shape
 from liso_amd.utils.device_args import opt_ptr as _p
@@ -453,7 +461,8 @@ class Collection(NamedTuple):
     """One `ObjectDetectionMetrics`: its tag under `<prefix>` (compute() appends `/<criterion>/...`), the ground-truth set it reads
     ("gt": the visible boxes, "benchmark": the benchmark's), and the constructor arguments.  kind "waymo": one
     `WaymoObjectDetectionMetrics` (optimal assignment, L1 / L2); its compute() appends `<criterion>/...` to the tag with no
-    separator, as the reference's log() does."""
+    separator, as the reference's log() does.  kind "nusc": one `NuscenesObjectDetectionMetrics`; its compute() appends `/mAP`, `/NDS`,
+    `/<class>/AP`, ... to the tag stripped of trailing slashes."""
     tag: str
     gt_set: str
     kwargs: dict
@@ -461,6 +470,7 @@ class Collection(NamedTuple):
 
 
 RANGE_BINS = ((0.0, 1000.0), (0.0, 20.0), (20.0, 40.0), (40.0, 60.0))  # run_val :162
+KINDS = {"od": ObjectDetectionMetrics, "waymo": WaymoObjectDetectionMetrics, "nusc": NuscenesObjectDetectionMetrics}
 
 
 class DetectionValidator:
@@ -474,9 +484,9 @@ class DetectionValidator:
                  generator=None):
         self.collections = [c if isinstance(c, Collection) else Collection(*c) for c in collections]
         for c in self.collections:
-            if c.kind not in ("od", "waymo"):
-                raise ValueError(f"kind must be 'od' or 'waymo', got {c.kind!r}")
-        self.metrics = [(WaymoObjectDetectionMetrics if c.kind == "waymo" else ObjectDetectionMetrics)(**c.kwargs) for c in self.collections]
+            if c.kind not in KINDS:
+                raise ValueError(f"kind must be one of {sorted(KINDS)}, got {c.kind!r}")
+        self.metrics = [KINDS[c.kind](**c.kwargs) for c in self.collections]
         self.transfer_classes, self.n_classes, self.class_frequencies, self.generator = transfer_classes, int(n_classes), class_frequencies, generator
         self.tables = {"gt": JobTable(), "benchmark": JobTable()}
         self.assign_tables = {"gt": JobTable(assignment=True), "benchmark": JobTable(assignment=True)}  # the Waymo-style collections' jobs
@@ -485,6 +495,9 @@ class DetectionValidator:
         for c, m in zip(self.collections, self.metrics):
             if c.gt_set not in self.tables:
                 raise ValueError(f"gt_set must be 'gt' or 'benchmark', got {c.gt_set!r}")
+            if c.kind == "nusc":  # no jobs: a launch of its own per batch
+                self.job_of.append({})
+                continue
             if c.kind == "waymo":
                 t, jobs = self.assign_tables[c.gt_set], {}
                 area = tuple(m.bev_range_min_xy_m.tolist() + m.bev_range_max_xy_m.tolist())
@@ -514,10 +527,18 @@ class DetectionValidator:
     # -- run_val :162-248 ------------------------------------------------------------------------------------------------------
     @classmethod
     def for_run_val(cls, dataset_kind: str, movable_class_names: Sequence[str] = (), class_idxs: Sequence[int] = (),
-                    moving_velocity_thresh: float = 0.1, class_frequencies=None, generator=None, waymo_metrics: bool = False):
+                    moving_velocity_thresh: float = 0.1, class_frequencies=None, generator=None, waymo_metrics: bool = False,
+                    nuscenes_metrics: bool = False, sigmoid_scores: bool = False):
         """visible / benchmark / waymo_cropped x 4 range bins x {iou_3d, iou_bev}, and the per-class collection of a KITTI
-        ("kitti") or AV2 ("av2") validation set, with the per-dataset `min_precision`.  The nuScenes devkit wrapper is out of scope
-        (its package is absent).
+        ("kitti") or AV2 ("av2") validation set, with the per-dataset `min_precision`.
+
+        nuscenes_metrics=True adds the reference's `nusc_metrics` (:209, 493-514, 729-734), which it feeds on EVERY data set: one
+        `NuscenesObjectDetectionMetrics(eval_movable_classes_as_one=True)` on the visible ground truth under
+        `final_result/NUSC_OFFICIAL/detection_metrics/` (mAP, mATE ... mAAE, NDS, movable/AP ...).  It also makes "nuscenes" buildable:
+        the 24 range collections with `min_precision=0.1`, plus the per-class `NuscenesObjectDetectionMetrics` (:210-214) under
+        `final_result/NUSC_OFFICIAL/per_class/detection_metrics/`, classes looked up by class id: `movable_class_names` at
+        `class_idxs` (default: the reference's nuScenes order).  `sigmoid_scores`: both read the fp32 sigmoid of the scores
+        (:494-509; `run_val` decides).  With the default every existing collection, tag and value is unchanged.
 
         waymo_metrics=True adds the reference's `waymo_metrics` (:249-255, 487-492, 741-747): one `WaymoObjectDetectionMetrics` per
         range bin on the BENCHMARK ground truth, matched by optimal assignment on the device.  Their tags are
@@ -526,9 +547,10 @@ class DetectionValidator:
         `min_precision=0.1` as for KITTI, plus the per-class `WaymoObjectDetectionMetrics` on the visible ground truth under
         `final_result/WAYMO/per_class/detection_metrics/`.  That collection takes the predictions' scores as the other per-class
         collections do: the reference's sigmoid on them (:494-509) is monotone, changes no order and no matching, and stays out."""
-        if dataset_kind not in ("kitti", "av2") and not (dataset_kind == "waymo" and waymo_metrics):
-            raise NotImplementedError(f"{dataset_kind}: only the KITTI and AV2 collection sets are built, and Waymo's with waymo_metrics=True "
-                                      "(the nuScenes devkit is absent)")
+        if (dataset_kind not in ("kitti", "av2") and not (dataset_kind == "waymo" and waymo_metrics)
+                and not (dataset_kind == "nuscenes" and nuscenes_metrics)):
+            raise NotImplementedError(f"{dataset_kind}: only the KITTI and AV2 collection sets are built, Waymo's with waymo_metrics=True "
+                                      "and nuScenes' with nuscenes_metrics=True")
         cols = []
         for cat in ("visible", "benchmark", "waymo_cropped"):
             for lo, hi in RANGE_BINS:
@@ -548,6 +570,14 @@ class DetectionValidator:
         elif dataset_kind == "waymo":
             cols.append(Collection("final_result/WAYMO/per_class/detection_metrics/", "gt", dict(
                 eval_movable_classes_as_one=False, class_names=tuple(movable_class_names), class_idxs=tuple(class_idxs)), "waymo"))
+        elif dataset_kind == "nuscenes":
+            names = tuple(movable_class_names) or NUSC_MOVABLE_CLASSES
+            idxs = tuple(class_idxs) or tuple(range(len(names)))
+            if sorted(idxs) != list(range(len(names))):
+                raise ValueError(f"the nuScenes per-class radii are looked up by class id: class_idxs must number the names 0..{len(names) - 1}, got {idxs}")
+            by_id = tuple(n for _, n in sorted(zip(idxs, names)))
+            cols.append(Collection("final_result/NUSC_OFFICIAL/per_class/detection_metrics/", "gt", dict(
+                eval_movable_classes_as_one=False, class_names=by_id, sigmoid_scores=sigmoid_scores), "nusc"))
         else:
             cols.append(Collection("final_result/AV2/per_class/detection_metrics/", "gt", dict(
                 moving_velocity_thresh=moving_velocity_thresh, use_slow_nuscenes_matching=True, min_recall=0.0, min_precision=0.0,
@@ -556,8 +586,11 @@ class DetectionValidator:
             for lo, hi in RANGE_BINS:
                 cols.append(Collection(f"final_result/WAYMO/detection_metrics/{int(lo)}_{int(hi)}m", "benchmark",
                                        dict(min_eval_range_m=lo, max_eval_range_m=hi), "waymo"))
-        return cls(cols, transfer_classes=True, n_classes=max(len(movable_class_names), 1), class_frequencies=class_frequencies,
-                   generator=generator)
+        if nuscenes_metrics:
+            cols.append(Collection("final_result/NUSC_OFFICIAL/detection_metrics/", "gt",
+                                   dict(eval_movable_classes_as_one=True, sigmoid_scores=sigmoid_scores), "nusc"))
+        n_classes = len(movable_class_names) or (len(NUSC_MOVABLE_CLASSES) if dataset_kind == "nuscenes" else 1)
+        return cls(cols, transfer_classes=True, n_classes=n_classes, class_frequencies=class_frequencies, generator=generator)
 
     # -- accumulation -----------------------------------------------------------------------------------------------------------
     def _draws(self, F, P, device):
@@ -573,7 +606,15 @@ class DetectionValidator:
         builds nothing on the host and performs no host sync."""
         L.require_cuda(pred.valid)
         run = lambda name, *args, **kw: match_detections_packed(*args, **kw)  # noqa: E731
-        self._pending.append(self._match_batch(gt, benchmark_gt, pred, counts, class_draws, run, lambda t: t))
+
+        def run_nusc(g, p, order, m, pred_class):
+            return nusc_match_packed(g, p, order, m.radius_on(p["rows"].device), m.eval_movable_classes_as_one, m.matching_thresholds, pred_class)
+
+        def order_of(score, valid):
+            from liso_amd import det_nms as D
+
+            return D.order(score.contiguous(), None, valid, None)[1] if score.numel() else torch.zeros(score.shape, dtype=torch.int32, device=score.device)
+        self._pending.append(self._match_batch(gt, benchmark_gt, pred, counts, class_draws, run, lambda t: t, run_nusc, order_of))
 
     @torch.no_grad()
     def update_batch_host(self, gt: Shape, benchmark_gt: Optional[Shape], pred: Shape, counts=None, class_draws=None, pairs=None):
@@ -585,10 +626,16 @@ class DetectionValidator:
             g, p = ({k: to_np(v) for k, v in d.items()} for d in (g, p))
             return match_detections_host(g, p, t, to_np(draws), order, None if pairs is None else pairs.get(name), pred_class=pred_class,
                                          assign=assign)
-        rec = self._match_batch(gt, benchmark_gt, pred, counts, class_draws, run, to_np)
+
+        def run_nusc(g, p, order, m, pred_class):
+            g, p = ({k: to_np(v) for k, v in d.items()} for d in (g, p))
+            return nusc_match_host(g["rows"], g["valid"], g["cls"], p["rows"], p["valid"], to_np(pred_class), to_np(order), m.radius,
+                                   m.eval_movable_classes_as_one, m.matching_thresholds)
+        rec = self._match_batch(gt, benchmark_gt, pred, counts, class_draws, run, to_np, run_nusc,
+                                lambda score, valid: stable_order_host(to_np(score), to_np(valid)))
         self._host.append(rec)
 
-    def _match_batch(self, gt, benchmark_gt, pred, counts, class_draws, run, keep):
+    def _match_batch(self, gt, benchmark_gt, pred, counts, class_draws, run, keep, run_nusc, order_of):
         p = pack_boxes(pred)
         F, P = p["valid"].shape
         dev = p["valid"].device
@@ -596,14 +643,18 @@ class DetectionValidator:
             live = torch.arange(P, device=dev)[None, :] < counts.to(dev)[:, None]
             p["valid"] = (p["valid"].view(torch.bool) & live).view(torch.uint8)
         draws = None
-        if self.transfer_classes and any(t.needs_classes for t in list(self.tables.values()) + list(self.assign_tables.values())):
+        nusc = [(i, m) for i, (c, m) in enumerate(zip(self.collections, self.metrics)) if c.kind == "nusc"]
+        if self.transfer_classes and (any(t.needs_classes for t in list(self.tables.values()) + list(self.assign_tables.values()))
+                                      or any(not m.eval_movable_classes_as_one for _, m in nusc)):
             draws = class_draws if class_draws is not None else self._draws(F, P, dev)
         order = pred_class = None
         rec = {}
+        seen = {}  # sigmoid_scores -> (the scores a nuScenes collection reads, their stable order)
         for name, boxes in (("gt", gt), ("benchmark", benchmark_gt)):
             t, at = self.tables[name], self.assign_tables[name]
             at = at if at.jobs else None
-            if not t.jobs and at is None:
+            nusc_here = [(i, m) for i, m in nusc if self.collections[i].gt_set == name]
+            if not t.jobs and at is None and not nusc_here:
                 continue
             if boxes is None:
                 raise ValueError(f"collections read the {name!r} ground truth, none was given")
@@ -618,6 +669,15 @@ class DetectionValidator:
             if at is not None:
                 rec[name].update({k: o[k] for k in ("assign_count", "assign_pairs", "assign_gt_in", "assign_pred_in")})
                 rec[name]["hard"] = keep(g["hard"])
+            if nusc_here:
+                rec[name]["cls"], rec[name]["pred_class"] = keep(g["cls"]), o["pred_class"]
+            for i, m in nusc_here:
+                if m.sigmoid_scores not in seen:
+                    sc = m.scores_seen(p["score"])
+                    seen[m.sigmoid_scores] = (sc, order_of(sc, p["valid"]) if m.sigmoid_scores else order)
+                    rec.setdefault("nusc_score", {})[str(int(m.sigmoid_scores))] = keep(sc)
+                n = run_nusc(g, p, seen[m.sigmoid_scores][1], m, o["pred_class"])
+                rec[name].update({f"nusc{i}_{k}": v for k, v in n.items()})
         rec["score"] = keep(p["score"])
         return rec
 
@@ -647,7 +707,12 @@ class DetectionValidator:
 
     def _feed(self, rec):
         score = rec["score"]
-        for c, m, jobs in zip(self.collections, self.metrics, self.job_of):
+        for i, (c, m, jobs) in enumerate(zip(self.collections, self.metrics, self.job_of)):
+            if c.kind == "nusc":  # one call per batch: vectorised over the frames
+                r = rec[c.gt_set]
+                m.accumulate_matches(rec["nusc_score"][str(int(m.sigmoid_scores))], r["pred_class"], r["cls"],
+                                     **{k: r[f"nusc{i}_{k}"] for k in NUSC_OUT_KEYS})
+                continue
             if c.kind == "waymo":
                 self._feed_waymo(rec[c.gt_set], self.assign_tables[c.gt_set], m, jobs, score)
                 continue

@@ -48,7 +48,7 @@ def kitti_annotated_fov_mask(pred_boxes: Shape, pcl_full_w_ground):
 @torch.no_grad()
 def run_val(cfg, val_batches, box_predictor, writer_prefix: str = "", max_num_steps=None, logit_threshold=-1.0e32, dataset_kind="kitti",
             movable_class_names=("car", "pedestrian", "cyclist"), class_idxs=None, class_frequencies=None, generator=None,
-            filter_to_kitti_annotated_fov=None, validator=None, waymo_metrics=False):
+            filter_to_kitti_annotated_fov=None, validator=None, waymo_metrics=False, nuscenes_metrics=False, sigmoid_scores=None):
     """The detector's validation pass (reference :120-757).  Per batch of `val_batches` -- dictionaries with `pcls` (the list of
     clouds the detector takes), `gt_boxes` and `benchmark_gt_boxes` (padded Shapes [B,G*] on the device) and optionally
     `pcl_full_w_ground` [B,N,>=3] -- it runs `box_predictor.predict_boxes` with run_val's defaults (:361-386), the optional KITTI rule
@@ -62,16 +62,25 @@ def run_val(cfg, val_batches, box_predictor, writer_prefix: str = "", max_num_st
     `<writer_prefix>final_result/WAYMO/detection_metrics/<lo>_<hi>m<criterion>/overall/<L1|L2>/AP@0.4`, ...: the reference writes no
     separator before the criterion), matched by optimal assignment on the device in one more launch per ground-truth set, and makes
     dataset_kind="waymo" buildable (`DetectionValidator.for_run_val`).  With the default the result's keys are unchanged.
-    Out of scope: the nuScenes devkit wrapper (the package is absent), flow metrics (liso_amd/slim/validation.py has
-    them), images, exports and TensorBoard writers."""
+    nuscenes_metrics=True adds the reference's nuScenes detection metrics (`NuscenesObjectDetectionMetrics`, :209, 493-519, 729-740;
+    liso_amd/eval/nuscenes_metrics.py) for any dataset kind: `<writer_prefix>final_result/NUSC_OFFICIAL/detection_metrics/mAP`,
+    `/mATE` ... `/mAAE`, `/NDS`, `/movable/AP` ..., one more launch per batch, and makes dataset_kind="nuscenes" buildable with its
+    per-class collection under `.../NUSC_OFFICIAL/per_class/detection_metrics/`.  `sigmoid_scores`: these collections read the fp32
+    sigmoid of the scores; default: the reference's rule (:494-509) for the detector trained here,
+    cfg.box_prediction.activations.probs == "none" (pass False for a predictor whose scores are probabilities already, as the
+    reference does for its flow-cluster detector).  With the default the result's keys and values are unchanged.
+    Out of scope: flow metrics (liso_amd/slim/validation.py has them), images, PDFs, exports and TensorBoard writers."""
     from liso_amd.eval.det_validation import DetectionValidator
 
     moving = cfg.get("validation", {}).get("obj_is_moving_velocity_thresh", 0.1)  # reference :145-149
     if validator is None:
         if class_idxs is None:
             class_idxs = tuple(range(len(movable_class_names)))
+        if sigmoid_scores is None:
+            sigmoid_scores = cfg.get("box_prediction", {}).get("activations", {}).get("probs") == "none"
         validator = DetectionValidator.for_run_val(dataset_kind, movable_class_names, class_idxs, moving, class_frequencies, generator,
-                                                   waymo_metrics=waymo_metrics)
+                                                   waymo_metrics=waymo_metrics, nuscenes_metrics=nuscenes_metrics,
+                                                   sigmoid_scores=bool(sigmoid_scores))
     for val_step, batch in enumerate(val_batches):
         if max_num_steps is not None and val_step > max_num_steps:  # (the reference's own off-by-one, :260)
             break

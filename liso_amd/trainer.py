@@ -357,7 +357,8 @@ class DetectorTrainer:
     def eval_model(self, val_batches, max_iterations=None, **run_val_args):
         """The detector's counterpart of `SlimTrainer.eval_model`: liso_amd.eval.eval_ours.run_val over `val_batches` (dictionaries
         with `pcls`, `gt_boxes`, `benchmark_gt_boxes` and optionally `pcl_full_w_ground`) in eval mode, then the previous mode again.
-        -> the metric dictionary.  No parameter or buffer changes."""
+        -> the metric dictionary.  No parameter or buffer changes.  `run_val_args` go to run_val as they are (`dataset_kind`,
+        `waymo_metrics=True`, `nuscenes_metrics=True` for the nuScenes mAP / NDS under `final_result/NUSC_OFFICIAL/`, ...)."""
         from liso_amd.eval.eval_ours import run_val
 
         was_training = self.net.training
