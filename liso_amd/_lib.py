@@ -334,6 +334,11 @@ SIGNATURES = {
     "liso_bev_free_mask": (_i, [_vp, ctypes.c_long, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "liso_bev_select_free_cells": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "liso_snippet_paste": (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _i, _vp, _vp, _vp, _vp]),
+    "liso_bev_free_mask_batch_workspace_bytes": (_sz, [_i, _i, _i]),
+    "liso_bev_free_mask_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "liso_snippet_augment_batch_workspace_bytes": (_sz, [_vp]),
+    "liso_snippet_augment_batch": (_i, [_vp] * 23 + [_sz, _vp]),
+    "liso_cloud_append_batch": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 3),
     # include/liso_sample_prep.h
     "liso_sample_transform_f32": (_i, [_i, _i, _i] + [_vp] * 7),
     "liso_sample_transform_poses_f64": (_i, [_i, _vp, _vp, _i, _vp, _i, _vp]),
@@ -488,6 +493,13 @@ class SlimNpLossCfg(ctypes.Structure):
 class BoxPtsCfg(ctypes.Structure):
     """mirror of liso_boxpts_cfg (include/liso_tracking.h)"""
     _fields_ = [("batch", _i), ("n", ctypes.c_long), ("k", _i), ("point_stride", _i), ("precision", _i), ("dims_bloat", _f)]
+
+
+class AugmentBatchCfg(ctypes.Structure):
+    """mirror of liso_augment_batch_cfg (include/liso_augment.h)"""
+    _fields_ = [("batch", _i), ("n_max", _i), ("h", _i), ("w", _i), ("radius", _i), ("max_num_objs", _i), ("num_snippets", _i),
+                ("db_rows", ctypes.c_long), ("extra_capacity", _i), ("selection", _i), ("range_x", _d), ("range_y", _d), ("cell_x", _d),
+                ("cell_y", _d), ("max_scale_delta", _d), ("max_points_dropout", _d), ("vmin", _d), ("vmax", _d)]
 
 
 class FramePrepCfg(ctypes.Structure):

@@ -60,6 +60,7 @@ class BoxSnippetDb:
         assert torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float32, "from_device takes the device buffer"
         assert points.dim() == 2 and points.shape[1] == 4 and points.is_contiguous(), points.shape
         db = cls.__new__(cls)
+        device_rows = lidar_rows if torch.is_tensor(lidar_rows) and lidar_rows.is_cuda else None
         db.offsets = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets).astype(np.int64)
         db.counts = np.diff(db.offsets)
         assert len(db.counts) > 0 and db.offsets[0] == 0 and db.offsets[-1] == points.shape[0] and np.all(db.counts >= 0), db.offsets
@@ -73,7 +74,25 @@ class BoxSnippetDb:
             lidar_rows = [rows[db.offsets[i]:db.offsets[i + 1]] for i in range(len(db.counts))]
         db.lidar_rows = [np.asarray(r) for r in lidar_rows] if lidar_rows is not None else None
         db.box_T_sensor = box_T_sensor
+        if device_rows is not None:  # (device_tables keeps the rows it was given instead of uploading the host copy)
+            db._device_rows = device_rows.to(torch.int32).contiguous()
         return db
+
+    def device_tables(self):
+        """-> dict(offsets int64 [M + 1], dims float32 [M, 3], pos_z float32 [M], lidar_rows int32 [P] or None) on the device of the
+        points, uploaded on the first call and kept: what the batched augmentation (datasets/batch_augmentation.py) reads."""
+        tables = getattr(self, "_device_tables", None)
+        if tables is None:
+            dev = self.points.device
+            rows = getattr(self, "_device_rows", None)
+            if rows is None and self.lidar_rows is not None:
+                flat = np.concatenate([np.asarray(r).reshape(-1) for r in self.lidar_rows]) if len(self.lidar_rows) else np.zeros(0)
+                rows = torch.from_numpy(flat.astype(np.int32)).to(dev)
+            tables = {"offsets": torch.from_numpy(self.offsets.astype(np.int64)).to(dev),
+                      "dims": self.boxes.dims.to(torch.float32).contiguous().to(dev),
+                      "pos_z": self.boxes.pos[:, 2].to(torch.float32).contiguous().to(dev), "lidar_rows": rows}
+            self._device_tables = tables
+        return tables
 
     def __len__(self):
         return len(self.counts)
