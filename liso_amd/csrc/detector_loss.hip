@@ -201,6 +201,15 @@ __device__ __forceinline__ float cell_center(int i, int n, float range) {
     return (float)((((double)i + 0.5) / (double)n) * (double)range - 0.5 * (double)range);
 }
 
+// the smallest fp32 not below the cell border i * range / n - range / 2: an fp32 coordinate p lies in cell i, floor((p + range / 2) * n /
+// range) == i in exact arithmetic, iff border(i) <= p < border(i + 1).  (Forming (p + range / 2) * (n / range) in fp32 rounded the largest
+// coordinate below range / 2 up to the border: that box marked no cell.)
+__device__ __forceinline__ float cell_border(int i, int n, float range) {
+    const double b = ((double)i * (double)range) / (double)n - 0.5 * (double)range;
+    const float f = (float)b;
+    return (double)f < b ? nextafterf(f, INFINITY) : f;
+}
+
 __device__ __forceinline__ float box_heat(float cx, float cy, float bx, float by, float c, float s, float len, float wid) {
     const float dx = cx - bx, dy = cy - by;
     const float u = dx * c + dy * s, v = -dx * s + dy * c;
@@ -239,6 +248,9 @@ __global__ __launch_bounds__(256) void targets_render_kernel(liso_targets_cfg c,
     const int rem = (int)(i - (long)b * c.h * c.w);
     const int y = rem / c.w, x = rem - y * c.w;
     const float cx = cell_center(y, c.h, c.range_x), cy = cell_center(x, c.w, c.range_y);
+    // the box centres this cell contains, as fp32 bounds [lo, hi) (create_occupancy_pcl_image of the centres, :309-314)
+    const float lo_y = cell_border(y, c.h, c.range_x), hi_y = cell_border(y + 1, c.h, c.range_x);
+    const float lo_x = cell_border(x, c.w, c.range_y), hi_x = cell_border(x + 1, c.w, c.range_y);
     const float* P = box_pos + (size_t)b * c.n_boxes * 3;
     const float* D = box_dims + (size_t)b * c.n_boxes * 3;
     const float* R = box_rot + (size_t)b * c.n_boxes;
@@ -250,10 +262,7 @@ __global__ __launch_bounds__(256) void targets_render_kernel(liso_targets_cfg c,
         if (!V[k]) continue;
         const float h = box_heat(cx, cy, P[3 * k], P[3 * k + 1], cosf(R[k]), sinf(R[k]), D[3 * k], D[3 * k + 1]) / M[k];
         best = fmaxf(best, h);
-        // the cell that contains the box centre (create_occupancy_pcl_image of the centres, :309-314)
-        const int iy = (int)((P[3 * k] + 0.5f * c.range_x) * ((float)c.h / c.range_x));
-        const int ix = (int)((P[3 * k + 1] + 0.5f * c.range_y) * ((float)c.w / c.range_y));
-        center |= (iy == y && ix == x && P[3 * k] + 0.5f * c.range_x >= 0.f && P[3 * k + 1] + 0.5f * c.range_y >= 0.f);
+        center |= (P[3 * k] >= lo_y && P[3 * k] < hi_y && P[3 * k + 1] >= lo_x && P[3 * k + 1] < hi_x);
     }
     float ad[3] = {0.f, 0.f, 0.f}, ap[3] = {0.f, 0.f, 0.f}, ar[2] = {0.f, 0.f};
     if (best > 0.01f) {  // occupancy threshold, :212-215; the hottest box(es) of the cell give it their attributes

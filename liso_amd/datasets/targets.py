@@ -73,8 +73,12 @@ def render_center_targets_torch(boxes_pos, boxes_dims, boxes_rot, boxes_valid, g
         "rot": (hottest * sincos[:, :, None, None, :]).sum(1),
     }
     # centre mask: the cell that contains the box centre (create_occupancy_pcl_image of the centres, commons.py:309-314)
-    res = torch.tensor([H / bev_range_m[0], W / bev_range_m[1]], device=dev)
-    ij = ((boxes_pos[..., :2] + torch.tensor(bev_range_m, device=dev) / 2) * res).long()
+    # in fp64 and with floor(): an fp32 sum rounds the largest coordinate below range / 2 up to the border, and a truncation pulls a
+    # centre just outside the low border into cell 0
+    res = torch.tensor([H / bev_range_m[0], W / bev_range_m[1]], dtype=torch.float64, device=dev)
+    half = torch.tensor([0.5 * bev_range_m[0], 0.5 * bev_range_m[1]], dtype=torch.float64, device=dev)
+    ij = torch.floor((boxes_pos[..., :2].double() + half) * res)
+    ij = torch.where(boxes_valid.bool()[..., None], ij, torch.zeros_like(ij)).clamp(-1.0, float(max(H, W))).long()  # (padding may hold NaN)
     ok = boxes_valid & (ij[..., 0] >= 0) & (ij[..., 0] < H) & (ij[..., 1] >= 0) & (ij[..., 1] < W)
     hits = torch.zeros((B, H * W), dtype=torch.int32, device=dev)
     lin = (ij[..., 0].clamp(0, H - 1) * W + ij[..., 1].clamp(0, W - 1))
