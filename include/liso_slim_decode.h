@@ -53,7 +53,8 @@ typedef struct {
  *   raw     float32 [S,N,8]   network output at every point's pillar: 4 logits | static flow xy | dynamic flow xy (0 at invalid rows)
  *   lin     int32 [S*N]       flattened cell (s*h*w + r*w + c) of every point, < 0 = invalid row
  *   filled  uint8 [S*h*w]     filled-pillar mask
- *   extrema float32 [8]       max[4] | min[4] of the raw logit channels over the whole BEV batch (read only if a class logit is ON / OFF)
+ *   extrema float32 [8]       max[4] | min[4] of the raw logit channels over the whole BEV batch: read only if a class logit
+ *                             (logit_mode[1..3]) is ON / OFF, and then required -- the four decode calls return LISO_EINVAL for NULL
  */
 
 /* Pass 1 (static_aggregation.py:34-68): x = point (0 at invalid rows), y = x + (static flow, 0), w = staticness * filled.
@@ -111,6 +112,7 @@ int liso_slim_knn_queries(int samples, int clouds, long n, int types, const floa
 /* Nearest-point loss with the padding mask, the query order and the masked mean in one pass (knn_wrapper.py:58-135,186-217 +
  * slim_loss_adaptor.py:239-251): index int64 [S,N] is in QUERY order (index[s,j] answers point order[s % clouds][j]).
  *   -> dist_sqr [S,N] in point order (0 at invalid rows), out[0] = sum of loss over valid rows / number of valid rows.
+ *   A valid row whose squared distance is NaN contributes NaN to the sum (as torch, and as liso_nearest_point_loss_fwd_f32) and gets a zero gradient.
  * Backward: grad_out [1] (+ optional grad_dist_sqr [S,N]) -> grad_flow [S,N,3]. */
 typedef struct {
     int samples, clouds;

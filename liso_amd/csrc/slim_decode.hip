@@ -445,6 +445,10 @@ __device__ __forceinline__ NpEval np_eval(const liso_slim_nploss_cfg& c, float q
     e.loss = l * w;
     e.scale = -2.f * dl * w;
     e.ok = isfinite(e.d2);
+    if (!(e.d2 == e.d2)) {  // NaN row: torch propagates NaN through clamp / sqrt / NaN * 0 and so does slim_loss.hip; fminf / fmaxf would not
+        e.loss = nanf("");
+        e.scale = 0.f;
+    }
     return e;
 }
 
@@ -560,6 +564,11 @@ inline bool cfg_ok(const liso_slim_decode_cfg* c) {
     return (long)c->samples * c->h * c->w < (1L << 31);
 }
 
+// the kernels read `extrema` exactly when a class logit is forced (logit_consts)
+inline bool extrema_ok(const liso_slim_decode_cfg* c, const float* extrema) {
+    return extrema || (c->logit_mode[1] == LISO_DECODE_NET && c->logit_mode[2] == LISO_DECODE_NET && c->logit_mode[3] == LISO_DECODE_NET);
+}
+
 inline unsigned blocks_for(long rows) { return (unsigned)((rows + kThreads - 1) / kThreads); }
 
 }  // namespace
@@ -571,7 +580,7 @@ int liso_slim_decode_weights_fwd(const liso_slim_decode_cfg* cfg, const float* r
     if (!cfg_ok(cfg) || pc_stride < 3) return LISO_EINVAL;
     const long rows = (long)cfg->samples * cfg->n;
     if (rows == 0) return LISO_OK;
-    if (!raw || !lin || !filled || !pc || !x || !y || !w) return LISO_EINVAL;
+    if (!raw || !lin || !filled || !pc || !x || !y || !w || !extrema_ok(cfg, extrema)) return LISO_EINVAL;
     decode_weights_fwd_kernel<<<blocks_for(rows), kThreads, 0, (hipStream_t)stream>>>(*cfg, raw, lin, filled, extrema, pc, pc_stride, x,
                                                                                       y, w);
     return check_launch();
@@ -582,7 +591,7 @@ int liso_slim_decode_weights_bwd(const liso_slim_decode_cfg* cfg, const float* r
     if (!cfg_ok(cfg)) return LISO_EINVAL;
     const long rows = (long)cfg->samples * cfg->n;
     if (rows == 0) return LISO_OK;
-    if (!raw || !lin || !filled || !grad_raw) return LISO_EINVAL;
+    if (!raw || !lin || !filled || !grad_raw || !extrema_ok(cfg, extrema)) return LISO_EINVAL;
     decode_weights_bwd_kernel<<<blocks_for(rows), kThreads, 0, (hipStream_t)stream>>>(*cfg, raw, lin, filled, extrema, grad_y, grad_w,
                                                                                       grad_raw);
     return check_launch();
@@ -594,7 +603,7 @@ int liso_slim_decode_points_fwd(const liso_slim_decode_cfg* cfg, const float* ra
     if (!cfg_ok(cfg) || !out) return LISO_EINVAL;
     const long rows = (long)cfg->samples * cfg->n;
     if (rows == 0) return LISO_OK;
-    if (!raw || !lin || !filled || !threshold || !trafo) return LISO_EINVAL;
+    if (!raw || !lin || !filled || !threshold || !trafo || !extrema_ok(cfg, extrema)) return LISO_EINVAL;
     decode_points_fwd_kernel<<<blocks_for(rows), kThreads, 0, (hipStream_t)stream>>>(*cfg, raw, lin, filled, extrema, threshold, trafo,
                                                                                      *out);
     return check_launch();
@@ -606,7 +615,7 @@ int liso_slim_decode_points_bwd(const liso_slim_decode_cfg* cfg, const float* ra
     if (!cfg_ok(cfg) || !grad) return LISO_EINVAL;
     const long rows = (long)cfg->samples * cfg->n;
     if (rows == 0) return LISO_OK;
-    if (!raw || !lin || !filled || !threshold || !trafo || !grad_raw) return LISO_EINVAL;
+    if (!raw || !lin || !filled || !threshold || !trafo || !grad_raw || !extrema_ok(cfg, extrema)) return LISO_EINVAL;
     decode_points_bwd_kernel<<<blocks_for(rows), kThreads, 0, (hipStream_t)stream>>>(*cfg, raw, lin, filled, extrema, threshold, trafo,
                                                                                      *grad, grad_raw, grad_saf_eff);
     return check_launch();
