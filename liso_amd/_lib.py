@@ -379,6 +379,15 @@ SIGNATURES = {
     "liso_flow_labels_workspace_bytes": (_sz, [_i, _i]),
     "liso_flow_labels_f32": (_i, [_vp] * 18 + [_sz, _vp]),
     "liso_kitti_rows_cols_f32": (_i, [_i, _i, _i, _vp, _vp, _d, _i, _i, _vp, _vp, _vp]),
+    # include/liso_visu.h
+    "liso_visu_flow_wheel_f32": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "liso_visu_topdown_workspace_bytes": (_sz, [_i, _i, _i]),
+    "liso_visu_topdown_f32": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "liso_visu_occupancy_f64": (_i, [_i, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp]),
+    "liso_visu_box_corners_bev": (_i, [_i, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "liso_visu_box_colors": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "liso_visu_lines_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "liso_visu_draw_lines_f32": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

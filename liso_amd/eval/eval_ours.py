@@ -45,10 +45,23 @@ def kitti_annotated_fov_mask(pred_boxes: Shape, pcl_full_w_ground):
     return points_in_boxes(boxes7, pts)["count"] >= MIN_NUM_PTS_PER_BOX
 
 
+def _log_val_images(cfg, writer, writer_prefix, step, batch, pred):
+    from liso_amd.visu.bbox_image import log_box_movement
+    from liso_amd.visu.pcl_image import create_occupancy_pcl_image
+
+    canvas = batch.get("occupancy_f32_ta")
+    if canvas is None:
+        canvas = torch.stack([create_occupancy_pcl_image(p, cfg.data.bev_range_m, cfg.data.img_grid_size) for p in batch["pcls"]]).permute(0, 3, 1, 2)
+    log_box_movement(cfg=cfg, writer=writer, global_step=step, sample_data_a={"occupancy_f32_ta": canvas, "gt": {"boxes": batch["gt_boxes"]}},
+                     sample_data_b={"occupancy_f32_ta": batch.get("occupancy_f32_tb"), "gt": {"boxes": batch.get("gt_boxes_tb")}}, pred_boxes=pred,
+                     writer_prefix=writer_prefix)
+
+
 @torch.no_grad()
 def run_val(cfg, val_batches, box_predictor, writer_prefix: str = "", max_num_steps=None, logit_threshold=-1.0e32, dataset_kind="kitti",
             movable_class_names=("car", "pedestrian", "cyclist"), class_idxs=None, class_frequencies=None, generator=None,
-            filter_to_kitti_annotated_fov=None, validator=None, waymo_metrics=False, nuscenes_metrics=False, sigmoid_scores=None):
+            filter_to_kitti_annotated_fov=None, validator=None, waymo_metrics=False, nuscenes_metrics=False, sigmoid_scores=None,
+            image_writer=None, num_image_steps=0):
     """The detector's validation pass (reference :120-757).  Per batch of `val_batches` -- dictionaries with `pcls` (the list of
     clouds the detector takes), `gt_boxes` and `benchmark_gt_boxes` (padded Shapes [B,G*] on the device) and optionally
     `pcl_full_w_ground` [B,N,>=3] -- it runs `box_predictor.predict_boxes` with run_val's defaults (:361-386), the optional KITTI rule
@@ -69,7 +82,14 @@ def run_val(cfg, val_batches, box_predictor, writer_prefix: str = "", max_num_st
     sigmoid of the scores; default: the reference's rule (:494-509) for the detector trained here,
     cfg.box_prediction.activations.probs == "none" (pass False for a predictor whose scores are probabilities already, as the
     reference does for its flow-cluster detector).  With the default the result's keys and values are unchanged.
-    Out of scope: flow metrics (liso_amd/slim/validation.py has them), images, PDFs, exports and TensorBoard writers."""
+    image_writer (any object with `add_images(tag, array, global_step=, dataformats=)`) with num_image_steps > 0: each of the first
+    `num_image_steps` batches also makes the box-movement picture (reference :615-625; liso_amd/visu/bbox_image.py
+    `log_box_movement`) of its ground truth and the predictions the metrics see, on the device, under
+    `<writer_prefix>RECONSTRUCTION_TARGETS_t0_t1` with the batch's index as the step.  The canvas is the batch's `occupancy_f32_ta`
+    [B,1,H,W] when it carries one, else the occupancy image of its clouds on cfg.data.img_grid_size.  A batch that also carries
+    `occupancy_f32_tb` (and `gt_boxes_tb`) gets the third canvas, the next sweep's ground truth over this one's in light blue.  With the defaults nothing is
+    drawn: the result and the launches of a batch are unchanged.
+    Out of scope: flow metrics (liso_amd/slim/validation.py has them), the range-view image, PDFs, exports and TensorBoard writers."""
     from liso_amd.eval.det_validation import DetectionValidator
 
     moving = cfg.get("validation", {}).get("obj_is_moving_velocity_thresh", 0.1)  # reference :145-149
@@ -90,4 +110,6 @@ def run_val(cfg, val_batches, box_predictor, writer_prefix: str = "", max_num_st
         if use_fov:
             pred.valid = pred.valid & kitti_annotated_fov_mask(pred, full)
         validator.update_batch(batch["gt_boxes"], batch.get("benchmark_gt_boxes"), pred)
+        if image_writer is not None and val_step < num_image_steps:
+            _log_val_images(cfg, image_writer, writer_prefix, val_step, batch, pred)
     return validator.compute(writer_prefix)

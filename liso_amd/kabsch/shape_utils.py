@@ -1,5 +1,5 @@
 """`Shape`: the box container of the hot path.  Mirror of liso/kabsch/shape_utils.py (API subset used by the
-rows of SURVEY.md section 8; shapely contours and plotting corners are out of scope).
+rows of SURVEY.md section 8; shapely contours are out of scope; the corners a picture draws are liso_amd/visu/bbox_image.py's).
 
 Fields (reference :19-93): pos[...,{2,3}], dims[...,{1,2,3}], rot[...,1], probs[...,1], velo[...,{1,2,3}],
 valid[...] bool, class_id[...,1] int32, difficulty[...,1] int32.

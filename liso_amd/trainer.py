@@ -368,6 +368,36 @@ class DetectorTrainer:
         finally:
             self.net.train(was_training)
 
+    @torch.no_grad()
+    def summary_images(self, pcls, targets, pred_boxes=None):
+        """The training loop's pictures of a batch (reference liso/kabsch/main_utils.py:464-503), as a dictionary of device tensors
+        made without a host read; `step` never calls it.  For the first n = min(B, cfg.logging.max_log_img_batches) samples:
+        `_post_nms_SHAPES_COMPARISON_PRED_GT` fp32 [n, H, W, 3]: the occupancy image of the clouds on cfg.data.img_grid_size with the
+        predictions over it, coloured by confidence, after the picture's NMS (liso_amd/visu/bbox_image.py `draw_box_image`);
+        `TARGET_CENTER_HEATMAP` fp32 [n, h, w, 1]: the centre heat map the step regresses against (`targets["probs"]`), a picture as
+        it stands.  `pred_boxes` (a padded Shape [B, P]) defaults to `self.net.predict_boxes` on the clouds in eval mode, the
+        previous mode set again afterwards, no parameter or buffer changed; their probs go through the sigmoid when
+        cfg.box_prediction.activations.probs == "none", as the reference does for the picture."""
+        from liso_amd.visu.bbox_image import draw_box_image
+        from liso_amd.visu.pcl_image import create_occupancy_pcl_image
+
+        cfg = self.cfg
+        if pred_boxes is None:
+            was_training = self.net.training
+            self.net.eval()
+            try:
+                pred_boxes, _, _ = self.net.predict_boxes(None, pcls)
+            finally:
+                self.net.train(was_training)
+        preds = pred_boxes.clone()
+        if cfg.box_prediction.activations.probs == "none":
+            preds.probs = torch.sigmoid(preds.probs)
+        canvas = torch.stack([create_occupancy_pcl_image(p, cfg.data.bev_range_m, cfg.data.img_grid_size) for p in pcls]).permute(0, 3, 1, 2)
+        n = min(canvas.shape[0], int(cfg.logging.max_log_img_batches))
+        return {"_post_nms_SHAPES_COMPARISON_PRED_GT": draw_box_image(cfg=cfg, pred_boxes=preds, gt_boxes=None, canvas_f32=canvas,
+                                                                       gt_background_boxes=None, perform_nms=True),
+                "TARGET_CENTER_HEATMAP": targets["probs"][:n].to(torch.float32)}
+
     def _pillars(self, pcls, out=None, prep=None):
         """`out`: (canvas rows [B, gx, gy, 64], occupancy) to write into -- the graph's static inputs (no copy afterwards)"""
         return self.net.model.pfn(pcl_t0=pcls, img_t0=None, out=out, prep=prep)

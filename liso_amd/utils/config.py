@@ -41,6 +41,7 @@ def default_cfg(grid=512, bev_range_m=100.0, use_lidar_intensity=True):
     """CenterPoint-pillar detector + SLIM settings of the reference's KITTI/nuScenes overlays."""
     return to_attr({
         "nms_iou_threshold": 0.1,                           # liso_config.yml:4
+        "logging": {"max_log_img_batches": 4},              # :15
         "data": {
             "shapes": {"name": "boxes"},
             "use_ground_for_network": False,
