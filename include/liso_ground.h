@@ -8,7 +8,14 @@
  * The result of liso_ground_jcp_f32 is defined as the reference's JPCGroundRemove applied to the float64 widening of the
  * cloud: all projection, threshold and weight arithmetic is fp64 in the reference's operation order (the source file is
  * compiled without FMA contraction), with the reference's quirks kept (its never-true bounds tests, last-writer-wins pixels,
- * the transposed cloud_index_ read of the candidate filter, raster-order in-place JCP).
+ * the transposed cloud_index_ read of the candidate filter, raster-order in-place JCP).  Two more follow from its indexing:
+ *   - A point with y == -0.0 and x < 0 has the angle -pi and, `y < 0` being false, the negative column trunc(-(W-1)/2).  The
+ *     reference keeps it out of the projection (col < 0: no winner, no region_minz update) and reads its label with numpy's
+ *     negative index, from pixel (row, W + col).  So do the device and the host path.
+ *   - The flat region index col * length + region of a point with r_xy == 70 exactly is the next column's region 0.  In the last
+ *     column that is one past the table, where the reference (compiled without bounds checks) writes out of bounds.  Defined
+ *     here: such a point leaves region_minz alone, still becomes its pixel's winner, and is classified against the table's
+ *     last entry.
  *
  * Stages of liso_ground_jcp_f32, each one or two launches on the caller's stream:
  *   0 init        workspace tables
@@ -43,6 +50,7 @@ extern "C" {
 #define LISO_GROUND_MAX_N (1 << 24)       /* rows per cloud */
 #define LISO_GROUND_LDS_BYTES (160 * 1024) /* label images up to this size are resolved in LDS, larger ones in global memory */
 #define LISO_GROUND_N_STAGES 7
+#define LISO_GROUND_N_LAYOUT 11           /* entries of liso_ground_jcp_workspace_layout */
 
 typedef struct {
     int batch;            /* B >= 1 */
@@ -61,7 +69,24 @@ size_t liso_ground_jcp_workspace_bytes(const liso_ground_cfg* cfg);
 int liso_ground_jcp_f32(const liso_ground_cfg* cfg, const float* pcl, const int32_t* counts, uint8_t* is_ground, void* workspace,
                         size_t workspace_bytes, void* stream);
 
-/* the stages [stage_begin, stage_end) only, on a workspace the earlier stages have filled (per-stage timing). */
+/* Byte offsets of the workspace tables into offsets[LISO_GROUND_N_LAYOUT], from the carver the kernels use, each 256-byte aligned
+ * (for tests that look at a stage's tables).  Per cloud b, in order:
+ *   0 ele_key  uint64 [B][2]        ordered keys of the min / max finite elevation (key = bits ^ sign-extended mask, see below)
+ *   1 ele      fp64   [B][n_max]    elevation of every valid row
+ *   2 pix      int32  [B][n_max]    col * H + row of the pixel a row's label is read from, -1 for invalid rows
+ *   3 widx     int32  [B][W*H]      winner row per pixel at col * H + row, -1 = none
+ *   4 minz_key uint32 [B][W*length] ordered fp32 key of the smallest z per (column, region); the key of 100.0f = untouched
+ *   5 minz     fp64   [B][W*length] the same widened, then RECM's thresholds (stage 3)
+ *   6 lab0     uint8  [B][S]        labels after RECM, row * W + col; S = W*H rounded up to 16; 0 empty, 1 ground, 2 obstacle
+ *   7 lab1     uint8  [B][S]        labels after the candidate filter (3 = candidate, stage 4), then resolved (stage 5)
+ *   8 row_cnt  int32  [B][H]        candidates per row
+ *   9 cols     int32  [B][H][W]     their columns, ascending, the first row_cnt of each row
+ *  10 wts      fp64   [B][H][W][24] their weights in the same slots
+ * An ordered key of a value with bits u is ~u for a negative value and u with the sign bit set for the others.
+ * LISO_EINVAL for a configuration liso_ground_jcp_workspace_bytes refuses or a null pointer. */
+int liso_ground_jcp_workspace_layout(const liso_ground_cfg* cfg, size_t* offsets);
+
+/* the stages [stage_begin, stage_end) only, on a workspace the earlier stages have filled (per-stage timing, stage tests). */
 int liso_ground_jcp_stages_f32(const liso_ground_cfg* cfg, const float* pcl, const int32_t* counts, uint8_t* is_ground,
                                void* workspace, size_t workspace_bytes, int stage_begin, int stage_end, void* stream);
 

@@ -324,6 +324,7 @@ SIGNATURES = {
     "liso_det_val_nusc_f32": (_i, [_i, _i, _i] + [_vp] * 8 + [_i, _i, _vp, _i] + [_vp] * 6),
     # include/liso_ground.h
     "liso_ground_jcp_workspace_bytes": (_sz, [_vp]),
+    "liso_ground_jcp_workspace_layout": (_i, [_vp, _vp]),
     "liso_ground_jcp_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "liso_ground_jcp_stages_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "liso_ground_cone_f32": (_i, [_i, _i, _i, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]),

@@ -37,7 +37,7 @@ enum : uint8_t { kEmpty = 0, kGround = 1, kObstacle = 2, kCandidate = 3 };
 struct Tables {
     unsigned long long* ele_key;  // [B][2] ordered keys of min / max finite elevation
     double* ele;                  // [B][N]
-    int32_t* pix;                 // [B][N] col * H + row, -1 for invalid rows
+    int32_t* pix;                 // [B][N] col * H + row of the pixel the point's label is read from, -1 for invalid rows
     int32_t* widx;                // [B][W*H] winner point per pixel, -1 = none
     uint32_t* minz_key;           // [B][W*L] ordered fp32 key of the smallest z per (column, region)
     double* minz;                 // [B][W*L] the same as fp64, then RECM's thresholds
@@ -183,11 +183,15 @@ __global__ __launch_bounds__(kThreads) void project_kernel(Tables t, Dims d, con
     double ang = atan2(y, x);
     if (y < 0.0) ang = ang + 2.0 * M_PI;
     const int col = to_i32(((double)(d.W - 1) * (ang * 180.0 / M_PI)) / 360.0);
-    if (col < 0 || col >= d.W) {  // not reachable with a finite angle
+    // y == -0.0 with x < 0: atan2 gives -pi, `y < 0` is false, the column is trunc(-(W-1)/2).  The reference keeps such a point
+    // out of the projection (col < 0) and reads its label with numpy's negative index, at column W + col.
+    const int read_col = col < 0 ? col + d.W : col;
+    if (read_col < 0 || read_col >= d.W) {  // not reachable: the angle lies in [-pi, 2 pi]
         *pix = -1;
         return;
     }
-    *pix = col * d.H + row;
+    *pix = read_col * d.H + row;
+    if (col < 0) return;
     const double r = sqrt(x * x + y * y);
     // the reference's bounds tests on col / row (> W, > H) and its z clause never hold
     if (r < kMinRange || r > kMaxRange || ((x < 3.0 && x > -2.0) && (y < 1.5 && y > -1.5))) return;
@@ -458,6 +462,15 @@ size_t liso_ground_jcp_workspace_bytes(const liso_ground_cfg* cfg) {
     Dims d;
     if (read_cfg(cfg, &d) != LISO_OK) return 0;
     return carve(d, nullptr).bytes;
+}
+
+int liso_ground_jcp_workspace_layout(const liso_ground_cfg* cfg, size_t* offsets) {
+    Dims d;
+    if (read_cfg(cfg, &d) != LISO_OK || !offsets) return LISO_EINVAL;
+    const Tables t = carve(d, nullptr);
+    const void* at[LISO_GROUND_N_LAYOUT] = {t.ele_key, t.ele, t.pix, t.widx, t.minz_key, t.minz, t.lab0, t.lab1, t.row_cnt, t.cols, t.wts};
+    for (int i = 0; i < LISO_GROUND_N_LAYOUT; ++i) offsets[i] = (size_t)(uintptr_t)at[i];
+    return LISO_OK;
 }
 
 int liso_ground_jcp_stages_f32(const liso_ground_cfg* cfg, const float* pcl, const int32_t* counts, uint8_t* is_ground,

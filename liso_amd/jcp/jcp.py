@@ -48,18 +48,20 @@ def _check_image(width, height):
     return width, height
 
 
-def _frac_dist(v, skip=None):
-    """smallest distance of the finite values of `v` from an integer (inf when there is none)"""
-    v = v[np.isfinite(v)]
-    if skip is not None:
-        v = v[~skip(v)]
-    return float(np.abs(v - np.rint(v)).min()) if v.size else float("inf")
+def _frac_dist(v, use):
+    """per element the distance of `v` from an integer; inf where `use` is False or `v` is not finite"""
+    with np.errstate(invalid="ignore"):
+        d = np.abs(v - np.rint(v))
+    return np.where(use & np.isfinite(v), d, np.inf)
 
 
 def jcp_host(pcl, range_img_width, range_img_height, sensor_height, delta_R, debug=False):
     """numpy [N,3] (any float dtype, widened to float64) -> bool [N]; with `debug` also a dict of intermediates in the numbering
     of the valid (NaN-free) rows: cloud_index [W*H] (col * H + row), region_minz [W*length] after RECM, candidates [K,2] (row, col)
-    in visiting order, labels image, margins |score_r - score_g| per candidate, RECM branch counts and the near-tie figures."""
+    in visiting order, labels image, margins |score_r - score_g| per candidate, RECM branch counts and the near-tie figures
+    (index_frac [n]: per row the distance of its row / column / region value from an integer); and stage by stage: row / col [n]
+    (col negative for y == -0.0, x < 0), kept (the rows that take part in the projection), min_ele / max_ele, region_minz_raw
+    (before RECM), labels_recm (before the dilation), labels_candidates (after the candidate filter), weights [K,24]."""
     W, H = _check_image(range_img_width, range_img_height)
     delta_R, sensor_height = float(delta_R), float(sensor_height)
     length = _region_length(delta_R)
@@ -92,8 +94,9 @@ def jcp_host(pcl, range_img_width, range_img_height, sensor_height, delta_R, deb
         row = np.clip(row_f.astype(np.int32), 0, H - 1).astype(np.int64)
         col = col_f.astype(np.int32).astype(np.int64)
 
-    # ---- RangeProjection (:26-56): the never-true bounds tests and z clause are left out
-    skip = (r_xy < MIN_RANGE) | (r_xy > MAX_RANGE) | ((x < 3) & (x > -2) & (y < 1.5) & (y > -1.5))
+    # ---- RangeProjection (:26-56): the never-true bounds tests and z clause are left out.  col < 0 holds for y == -0.0 with
+    # x < 0 (angle -pi, not lifted by 2 pi): no projection, and the label is read below at column W + col.
+    skip = (r_xy < MIN_RANGE) | (r_xy > MAX_RANGE) | (col < 0) | ((x < 3) & (x > -2) & (y < 1.5) & (y > -1.5))
     kept = np.nonzero(~skip)[0]
     region_f = (r_xy[kept] - MIN_RANGE) / delta_R
     region = region_f.astype(np.int64)
@@ -101,7 +104,9 @@ def jcp_host(pcl, range_img_width, range_img_height, sensor_height, delta_R, deb
     np.maximum.at(cloud_index, col[kept] * H + row[kept], kept)  # last writer in index order
     minz = np.full(W * length, 100.0)
     ri = col[kept] * length + region  # flat: region == length (r == 70) lands in the next column, as in the reference
-    np.minimum.at(minz, ri, z[kept])
+    in_table = ri < W * length  # in the last column that is one past the table: no update (include/liso_ground.h)
+    np.minimum.at(minz, ri[in_table], z[kept][in_table])
+    minz_raw = minz.copy()
 
     # ---- RECM (:75-105), all columns at once, positions in order
     m = minz.reshape(W, length)
@@ -142,6 +147,7 @@ def jcp_host(pcl, range_img_width, range_img_height, sensor_height, delta_R, deb
     win_region = ((r_xy[win] - MIN_RANGE) / delta_R).astype(np.int64)
     th = minz[np.minimum(cc * length + win_region, W * length - 1)]
     lab[rr, cc] = np.where(z[win] >= th + TH_G, OBSTACLE, GROUND)
+    lab_recm = lab.copy()
 
     # ---- 5x5 cross dilation of the obstacle channel, candidates, the transposed filter (:339-367)
     obst = lab == OBSTACLE
@@ -157,6 +163,7 @@ def jcp_host(pcl, range_img_width, range_img_height, sensor_height, delta_R, deb
     cand_r, cand_c = rel_r[has_valid], rel_c[has_valid]
     lab[cand_r, cand_c] = CANDIDATE
     K = cand_r.shape[0]
+    lab_cand = lab.copy()
 
     # ---- the 24 weights of every candidate (:184-230): they do not depend on the labels
     ny = cand_r[:, None] + NEIGHBOR_DROW[None]
@@ -196,18 +203,21 @@ def jcp_host(pcl, range_img_width, range_img_height, sensor_height, delta_R, deb
             margins[k] = -1.0  # an exact tie that is not 0 vs 0
     lab = np.asarray(flat, np.uint8).reshape(H + 4, W + 4)[2:-2, 2:-2]
 
-    out[valid] = lab[row, col] == GROUND
+    out[valid] = lab[row, col] == GROUND  # a negative column wraps, as in the reference
     if not debug:
         return out
     nonzero = margins[margins > 0]
+    # pre-truncation row / column / region values; rows within 1e-9 of 0 or H clip to the same index from either side
+    index_frac = np.minimum(_frac_dist(row_f, ~((np.abs(row_f) < 1e-9) | (np.abs(row_f - H) < 1e-9))), _frac_dist(col_f, col_f > 1e-9))
+    index_frac[kept] = np.minimum(index_frac[kept], _frac_dist(region_f, region_f > 1e-9))
     info = {
         "cloud_index": cloud_index, "region_minz": minz, "candidates": np.stack([cand_r, cand_c], -1), "labels": lab,
         "margins": margins, "branch": branch,
+        "row": row, "col": col, "kept": kept, "min_ele": float(min_ele), "max_ele": float(max_ele), "region_minz_raw": minz_raw,
+        "labels_recm": lab_recm, "labels_candidates": lab_cand, "weights": Wt,
         "min_nonzero_margin": float(nonzero.min()) if nonzero.size else float("inf"),
         "exact_ties": int((margins == 0).sum()), "bad_ties": int((margins < 0).sum()),
-        # pre-truncation row / column / region values; rows within 1e-9 of 0 or H clip to the same index from either side
-        "min_index_frac": min(_frac_dist(row_f, lambda v: (np.abs(v) < 1e-9) | (np.abs(v - H) < 1e-9)), _frac_dist(col_f[col_f > 1e-9]),
-                              _frac_dist(region_f[region_f > 1e-9])),
+        "index_frac": index_frac, "min_index_frac": float(index_frac.min()),
     }
     return out, info
 
@@ -240,6 +250,50 @@ def jcp_device(pcl, range_img_width, range_img_height, sensor_height, delta_R, c
         return out, ws
     res = out.view(torch.bool)
     return res if pcl.dim() == 3 else res[0]
+
+
+LAYOUT = ("ele_key", "ele", "pix", "widx", "minz_key", "minz", "lab0", "lab1", "row_cnt", "cols", "wts")  # LISO_GROUND_N_LAYOUT entries
+
+
+def jcp_tables(state, pcl, range_img_width, range_img_height, sensor_height, delta_R):
+    """(labels, workspace) as `jcp_device(..., stages=...)` returns them, for the same cloud and parameters -> dict of tensor views
+    into the workspace, named and shaped as include/liso_ground.h lists them (liso_ground_jcp_workspace_layout), plus "labels"
+    uint8 [B,N].  The label images come as [B,H,W] without the padding behind them."""
+    p3 = cloud3(pcl)
+    B, N = p3.shape[0], p3.shape[1]
+    W, H = int(range_img_width), int(range_img_height)
+    length = _region_length(float(delta_R))
+    cfg = _cfg(p3, W, H, sensor_height, delta_R)
+    offsets = (ctypes.c_size_t * len(LAYOUT))()
+    L.check(L.lib().liso_ground_jcp_workspace_layout(ctypes.byref(cfg), offsets), "ground jcp workspace layout")
+    labels, ws = state
+    lab_stride = (W * H + 15) // 16 * 16
+    shapes = {"ele_key": (torch.int64, (B, 2)), "ele": (torch.float64, (B, N)), "pix": (torch.int32, (B, N)), "widx": (torch.int32, (B, W * H)),
+              "minz_key": (torch.int32, (B, W * length)), "minz": (torch.float64, (B, W * length)), "lab0": (torch.uint8, (B, lab_stride)),
+              "lab1": (torch.uint8, (B, lab_stride)), "row_cnt": (torch.int32, (B, H)), "cols": (torch.int32, (B, H, W)),
+              "wts": (torch.float64, (B, H, W, 24))}
+    out = {"labels": labels}
+    for name, off in zip(LAYOUT, offsets):
+        dtype, shape = shapes[name]
+        nbytes = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
+        out[name] = ws[off:off + nbytes].view(dtype).view(shape)
+    for name in ("lab0", "lab1"):
+        out[name] = out[name][:, : W * H].view(B, H, W)
+    return out
+
+
+def unkey_f64(keys):
+    """ordered uint64 keys (read as int64 numpy) -> the float64 values"""
+    k = np.asarray(keys).astype(np.int64).view(np.uint64)
+    neg = (k >> np.uint64(63)) == 0  # the key of a negative value has its top bit clear
+    return np.where(neg, ~k, k & np.uint64(0x7FFFFFFFFFFFFFFF)).astype(np.uint64).view(np.float64)
+
+
+def unkey_f32(keys):
+    """ordered uint32 keys (read as int32 numpy) -> the float32 values"""
+    k = np.asarray(keys).astype(np.int32).view(np.uint32)
+    neg = (k >> np.uint32(31)) == 0
+    return np.where(neg, ~k, k & np.uint32(0x7FFFFFFF)).astype(np.uint32).view(np.float32)
 
 
 def cone_device(pcl, cone_z_threshold__m, cone_angle__deg, counts=None, or_with=None):

@@ -18,6 +18,12 @@ of the rest (the sector is azimuth 0..17 degrees: the reference's transposed clo
 permutation of the KITTI cloud that it is.  Per cloud the generator asserts the near-tie condition -- smallest nonzero
 |score_r - score_g| and smallest distance of a pre-truncation row / column / region value from an integer both >= 1e-9, every exact tie 0 vs 0 -- and records, for information,
 how many labels differ between the reference on the float32 cloud and on its float64 widening.
+
+A second file, ground_seg_edges_reference.npz, records the reference on the small edge clouds of tests/ground_stage_cases.py
+(GOLDEN_CASES: images smaller than the 5x5 window, a 65-row image, one and 255 regions, the hand-placed degenerate rows without
+the r_xy == 70 row in the last column, on which the reference's region_minz_ index leaves the table and numpy raises): the
+float32 cloud, labels, cloud_index_, region_minz_ after RECM and the candidate list.  The near-tie condition of these clouds is
+asserted by tests/test_ground_stage_cases.py.
 Run in the build container only:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_ground_seg_golden.py"""
 import os
 import sys
@@ -156,6 +162,36 @@ def main():
         out[f"{name}_min_index_frac"] = np.array(info["min_index_frac"])
         out[f"{name}_f32_label_diff"] = np.array(int((labels32 != labels_clean).sum()))
     path = os.path.join(HERE, "ground_seg_reference.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+    edges(ref, jcp_host)
+
+
+def edges(ref, jcp_host):
+    sys.path.insert(0, os.path.dirname(HERE))
+    import ground_stage_cases as C
+
+    out = {"names": np.array(C.GOLDEN_CASES)}
+    for name in C.GOLDEN_CASES:
+        pts32, prm = C.cloud(name)
+        ok = ~np.isnan(pts32).any(-1)
+        labels = np.zeros(pts32.shape[0], bool)
+        with np.errstate(all="ignore"):
+            labels[ok] = ref.JPCGroundRemove(pcl=pts32[ok].astype(np.float64), **prm)
+        cap = {k: v.copy() for k, v in CAPTURE.items()}
+        mine, info = jcp_host(pts32, debug=True, **prm)
+        same = (np.array_equal(mine, labels), np.array_equal(info["cloud_index"], cap["cloud_index"]),
+                np.array_equal(info["region_minz"], cap["region_minz"]), np.array_equal(info["candidates"], cap["candidates"].reshape(-1, 2)))
+        print(name, "points", pts32.shape[0], "ground", int(labels.sum()), "candidates", cap["candidates"].shape[0],
+              "host path equal (labels, cloud_index, region_minz, candidates):", same)
+        assert all(same), name
+        out[f"{name}_pcl"] = np.asarray(pts32)
+        out[f"{name}_params"] = np.array([prm["range_img_width"], prm["range_img_height"], prm["sensor_height"], prm["delta_R"]], np.float64)
+        out[f"{name}_labels"] = labels
+        out[f"{name}_cloud_index"] = cap["cloud_index"].astype(np.int32)
+        out[f"{name}_region_minz"] = cap["region_minz"]
+        out[f"{name}_candidates"] = cap["candidates"].astype(np.int32)
+    path = os.path.join(HERE, "ground_seg_edges_reference.npz")
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes")
 

@@ -34,7 +34,7 @@ def test_symbols_and_signatures_match_the_header():
     L = _lib()
     lib = L.lib()
     decl = _declarations()
-    assert set(decl) == {"liso_ground_jcp_workspace_bytes", "liso_ground_jcp_f32", "liso_ground_jcp_stages_f32", "liso_ground_cone_f32",
+    assert set(decl) == {"liso_ground_jcp_workspace_bytes", "liso_ground_jcp_workspace_layout", "liso_ground_jcp_f32", "liso_ground_jcp_stages_f32", "liso_ground_cone_f32",
                          "liso_ground_compact_workspace_bytes", "liso_ground_compact_f32"}
     for name, (res, args) in decl.items():
         assert hasattr(lib, name), name
@@ -46,6 +46,7 @@ def test_symbols_and_signatures_match_the_header():
 
     assert f"#define LISO_GROUND_N_STAGES {jcp.N_STAGES}" in hdr and len(jcp.STAGES) == jcp.N_STAGES
     assert f"#define LISO_GROUND_MAX_HEIGHT {jcp.MAX_HEIGHT}" in hdr
+    assert re.search(rf"#define LISO_GROUND_N_LAYOUT {len(jcp.LAYOUT)}\b", hdr)
 
 
 def _cfg(L, b=2, n=1000, stride=3, w=2083, h=64, sh=1.73, dr=1.0):
@@ -60,11 +61,49 @@ def test_workspace_query():
     one, two = q(b=1), q(b=2)
     assert one >= 2083 * 64 * 24 * 8 and 2 * one - 4096 <= two <= 2 * one  # dominated by the per-slot weights
     assert q(n=2000) > q(n=1000)
-    for bad in (dict(b=0), dict(n=-1), dict(stride=2), dict(w=0), dict(h=0), dict(h=1025), dict(dr=0.0), dict(dr=-1.0), dict(dr=0.26),
-                dict(w=32, h=64), dict(dr=68.0), dict(sh=float("nan"))):
+    for bad in BAD_CFGS:
         assert q(**bad) == 0, bad
     assert lib.liso_ground_compact_workspace_bytes(0, 10) == 0 and lib.liso_ground_compact_workspace_bytes(1, 0) == 0
     assert lib.liso_ground_compact_workspace_bytes(2, 1000) >= 2 * 2 * 1000 * 4
+
+
+BAD_CFGS = (dict(b=0), dict(n=-1), dict(stride=2), dict(w=0), dict(h=0), dict(h=1025), dict(dr=0.0), dict(dr=-1.0), dict(dr=0.26), dict(w=32, h=64),
+            dict(dr=68.0), dict(sh=float("nan")))
+
+
+def test_workspace_layout():
+    L = _lib()
+    lib = L.lib()
+    from liso_amd.jcp import jcp
+
+    n = len(jcp.LAYOUT)
+    assert jcp.LAYOUT == ("ele_key", "ele", "pix", "widx", "minz_key", "minz", "lab0", "lab1", "row_cnt", "cols", "wts")
+    hdr = open(os.path.join(ROOT, "include", "liso_ground.h")).read()
+    assert tuple(re.findall(r"^ \*\s+\d+ (\w+)\s+(?:uint64|fp64|int32|uint32|uint8)\s+\[B\]", hdr, flags=re.M)) == jcp.LAYOUT  # the header's list
+    for kw in (dict(), dict(b=1, n=0), dict(b=3, n=777, stride=5, w=70, h=65), dict(w=1, h=1, n=1), dict(w=1025, h=1024, dr=67.0 / 255.0),
+               dict(w=300, h=33, dr=40.0)):
+        cfg = _cfg(L, **kw)
+        offsets = (ctypes.c_size_t * (n + 1))(*([12345] * (n + 1)))
+        assert lib.liso_ground_jcp_workspace_layout(ctypes.byref(cfg), offsets) == 0
+        off = list(offsets)
+        assert off[n] == 12345  # LISO_GROUND_N_LAYOUT entries, not one more
+        off = off[:n]
+        total = lib.liso_ground_jcp_workspace_bytes(ctypes.byref(cfg))
+        assert off[0] == 0 and all(o % 256 == 0 for o in off) and off == sorted(off) and off[-1] <= total
+        # every table fits in front of the next one, the last one in front of the end
+        B, N, W, H = cfg.batch, cfg.n_max, cfg.width, cfg.height
+        length = int(67.0 / cfg.delta_r)
+        stride = (W * H + 15) // 16 * 16
+        sizes = [B * 2 * 8, B * N * 8, B * N * 4, B * W * H * 4, B * W * length * 4, B * W * length * 8, B * stride, B * stride, B * H * 4, B * W * H * 4,
+                 B * W * H * 24 * 8]
+        for i in range(n):
+            assert off[i] + sizes[i] <= (off[i + 1] if i + 1 < n else total), (kw, jcp.LAYOUT[i])
+        assert total - off[-1] - sizes[-1] < 256
+    good = (ctypes.c_size_t * n)()
+    for bad in BAD_CFGS:
+        assert lib.liso_ground_jcp_workspace_layout(ctypes.byref(_cfg(L, **bad)), good) == EINVAL, bad
+    assert lib.liso_ground_jcp_workspace_layout(None, good) == EINVAL
+    assert lib.liso_ground_jcp_workspace_layout(ctypes.byref(_cfg(L)), None) == EINVAL
 
 
 def test_jcp_refuses_bad_arguments_before_launching():
